@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- hot-path benchmark (contract: one JSON line on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|hist]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|hist] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` (images/s), `ms_per_step` (wall time of
+one timed step) and what the timed steps themselves show (per-kind step times, host enqueue time).  `--full` adds
+everything that takes runs of its own: the stand-alone kernel timings (`roofline`), the data-parallel probe (`ddp`),
+the CPU baselines and the reference's op chain on stock PyTorch-ROCm eager.  `--dump-outputs DIR` writes what the
+last timed step computed as DIR/<name>.npy (`dump_outputs`); every generator is seeded, so with the same arguments the
+inputs are the same from run to run and two builds can be compared output for output.
 
 `--gpus N` with N > 1 and no launcher environment (WORLD_SIZE unset) starts N ranks itself, one per GPU (`launch_ranks`);
 under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it is one of the N ranks.
@@ -38,6 +45,41 @@ sys.path.insert(0, ROOT)
 METRIC = 'train images/sec (G+D step, 256², h=64) at 1/2/4/8 MI355X; hist-kernel HBM GB/s'
 FP32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: FP32 vector == FP32 MFMA (v_mfma_f32_32x32x2_f32)
 HBM_PEAK_GBPS = 8000.0
+BENCH_SEED = 1234          # + rank: ranks draw different latents; the parameters are broadcast from rank 0 anyway
+DUMP_MAX_ELEMS = 1 << 21   # per dumped array (8 MB in float32); no workload dumps more than five arrays
+
+
+def seed_everything(seed):
+    """Weights, synthetic data and every latent / noise draw come from these generators."""
+    import random
+    import numpy as np
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+
+
+def dump_outputs(dirpath, arrays, seed=BENCH_SEED):
+    """Write {name: tensor or array} as DIR/<name>.npy: float64 stays float64, everything else becomes float32.  An array
+    of more than DUMP_MAX_ELEMS elements is replaced by a sample of its flattened elements, in ascending index order; the
+    indices depend only on the element count and `seed`, so two builds sample the same elements.  Returns the bytes written."""
+    import numpy as np
+    sample = lambda n: np.sort(np.random.default_rng(seed).choice(n, DUMP_MAX_ELEMS, replace=False))
+    os.makedirs(dirpath, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):      # sampled where it lives: a flat parameter buffer is hundreds of MB
+            a = a.detach()
+            if a.numel() > DUMP_MAX_ELEMS:
+                a = a.reshape(-1)[torch.from_numpy(sample(a.numel())).to(a.device)]
+            a = a.cpu().numpy()
+        a = np.asarray(a)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[sample(a.size)]
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(dirpath, name + '.npy'), a)
+        total += a.nbytes
+    assert total <= 64 << 20, f'dumped {total} bytes: more than 64 MB'
+    return total
 
 
 def hist_workload(args, dev, rank, world):
@@ -50,10 +92,16 @@ def hist_workload(args, dev, rank, world):
     with torch.no_grad():
         target = rgbuv_hist(torch.rand(B, 3, S, S, generator=g).to(dev), cfg)
 
+    last = {}
+
     def step():
         x.grad = None
         hist = rgbuv_hist(x, cfg)
-        hellinger_loss(target, hist, alpha=2.0).backward()
+        loss = hellinger_loss(target, hist, alpha=2.0)
+        loss.backward()
+        last.update(hist=hist, loss=loss)
+    # what the caller of the last step holds: the histogram, the loss and the gradient with respect to the images
+    step.outputs = lambda: dict(hist=last['hist'], loss=last['loss'], x_grad=x.grad)
 
     def time_kernels(iters, method=None):
         """HIP events (on the stream the kernels are launched on) around the forward and the backward
@@ -411,6 +459,16 @@ def reference_eager_rocm(args, dev):
         return dict(value=None, error=f'{type(e).__name__}: {str(e)[:200]}')
 
 
+def trainer_outputs(tr, losses):
+    """What a caller of train() holds after the last step: the losses it reports (the statistics read back as float64) and
+    the updated networks, whose parameters and `.grad` views live in the flat buffers of G (+ style and histogram
+    vectorizers) and of D."""
+    import numpy as np
+    GAN = tr.GAN
+    return dict(losses=np.array([getattr(tr, k) for k in losses], dtype=np.float64),
+                g_params=GAN._flat_g.data, g_grads=GAN._flat_g.grad, d_params=GAN._flat_d.data, d_grads=GAN._flat_d.grad)
+
+
 def train_workload(args, dev, rank, world):
     from histoGAN import Trainer
     tr = Trainer('bench', '/tmp/hg_bench_results', '/tmp/hg_bench_models', args.size, args.capacity,
@@ -423,6 +481,7 @@ def train_workload(args, dev, rank, world):
     def step():
         tr.train(alpha=2)
     step.trainer = tr
+    step.outputs = lambda: trainer_outputs(tr, ('d_loss', 'g_loss', 'h_loss', 'last_gp_loss', 'pl_mean'))
 
     info = dict(workload=f'HistoGAN G+D train step {args.size}x{args.size} capacity={args.capacity} '
                          f'batch={args.batch}/GPU h={args.bins} insz=150 inverse-quadratic (GP every 4th, PL every 32nd step)'
@@ -447,6 +506,7 @@ def rehistogan_workload(args, dev, rank, world):
     def step():
         tr.train(alpha=32, beta=1.5, gamma=4)
     step.trainer = tr
+    step.outputs = lambda: trainer_outputs(tr, ('d_loss', 'g_loss', 'r_loss', 'h_loss', 'last_gp_loss'))
 
     n = lambda m: sum(p.numel() for p in m.parameters())
     info = dict(workload=f'ReHistoGAN recolouring train step {args.size}x{args.size} capacity={args.capacity} '
@@ -526,6 +586,100 @@ def ddp_probe(dist, dev, rank, world, tr):
     info['allreduce'] = res
     info['allreduce_ms_per_step'] = sum(v['ms'] for v in res.values())
     return info
+
+
+def full_measurements(args, dev, rank, world):
+    """--full, after the timed steps: the stand-alone kernel timings (`roofline`) on every rank; on rank 0 of a one-GPU run
+    also the CPU baselines and the reference's op chain on stock PyTorch-ROCm eager.  Returns the entries of rank 0's line."""
+    _, time_kernels, work, _, _ = hist_workload(args, dev, rank, world)
+    t_fwd, t_bwd = time_kernels(min(max(args.steps, 5), 20))
+    hist_roof = {'kernel': 'k_hist_bwd', 'bound': 'mfma', 'achieved': work['flops_bwd'] / t_bwd / 1e12,
+                 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': work['flops_bwd'] / t_bwd / 1e12 / FP32_PEAK_TFLOPS,
+                 'traffic': recorded_traffic('k_hist_bwd_c2')[0] if (args.batch, args.size, args.bins) == (32, 256, 64) else None,
+                 'traffic_source': recorded_traffic('k_hist_bwd_c2')[1],
+                 'launch_ms': t_bwd * 1e3,
+                 'fwd': {'kernel': 'k_hist_fwd', 'achieved': work['flops_fwd'] / t_fwd / 1e12,
+                         'frac': work['flops_fwd'] / t_fwd / 1e12 / FP32_PEAK_TFLOPS, 'launch_ms': t_fwd * 1e3}}
+    # the HBM-side method of the same block: thresholding on the scatter-add / gather kernels (DESIGN.md section 4)
+    tt_f, tt_b = time_kernels(min(max(args.steps, 5), 20), 'thresholding')
+    thr_gbps = (work['bytes_fwd'] + work['bytes_bwd']) / (tt_f + tt_b) / 1e9
+    hist_roof['thresholding'] = {'kernels': 'k_thr_fwd_lean + k_hist_finish / k_thr_bwd_lean', 'bound': 'hbm',
+                                 'fwd_ms': tt_f * 1e3, 'bwd_ms': tt_b * 1e3, 'achieved': thr_gbps, 'peak': HBM_PEAK_GBPS,
+                                 'unit': 'GB/s', 'frac': thr_gbps / HBM_PEAK_GBPS,
+                                 'traffic': recorded_traffic('thr_fwd_bwd_c2')[0] if (args.batch, args.size, args.bins) == (32, 256, 64) else None,
+                                 'traffic_source': recorded_traffic('thr_fwd_bwd_c2')[1],
+                                 'north_star_hbm_target': 0.6, 'north_star_hbm_target_met': bool(thr_gbps / HBM_PEAK_GBPS >= 0.6),
+                                 'note': 'three launches of 17 + 5 + 23 us at batch 32: launch-latency regime (78.6 MB = 9.8 us at peak)'}
+    if rank == 0 and world == 1 and (args.size, args.bins) == (256, 64) and args.batch < 256:
+        # the same kernels where the launches are long enough to stream: batch 256 (629 MB per forward + backward)
+        hist_roof['thresholding']['batch256'] = thr_probe_batch(dev, 256, args.size, args.bins)
+    if args.workload in ('train', 'rehistogan'):
+        ct = conv_kernel_times(dev, args.batch, layers=g_layers(args.size, args.capacity))
+        rl = (16 * args.capacity, 8 * args.capacity, args.size // 4)        # 256 -> 128 channels at a quarter of the image size
+        fl = ct[rl]['flops']
+        tf, td, tw = ct[rl]['direct']
+        wf_, wd_, ww_ = ct[rl]['wino']
+        where = 'at %d->%d ch, %dx%d, batch %d' % (rl[0], rl[1], rl[2], rl[2], args.batch)
+        direct_line = {'kernel': 'k_conv<128ch x 128px tile, 3x3, stride 1> (hg_conv2d_fwd, direct implicit GEMM: the kernel the '
+                                 'Winograd form replaced on this layer) ' + where, 'bound': 'mfma',
+                       'achieved': fl / tf / 1e12, 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                       'frac': fl / tf / 1e12 / FP32_PEAK_TFLOPS, 'launch_ms': tf * 1e3, 'flops_per_launch': fl,
+                       'traffic': recorded_traffic('k_conv_fwd_256_128_64_b32')[0] if (args.batch, rl) == (32, (256, 128, 64)) else None,
+                       'traffic_source': recorded_traffic('k_conv_fwd_256_128_64_b32')[1],
+                       'wgrad': {'kernel': 'k_wgrad (hg_conv2d_wgrad), same layer', 'achieved': fl / tw / 1e12,
+                                 'frac': fl / tw / 1e12 / FP32_PEAK_TFLOPS, 'launch_ms': tw * 1e3,
+                                 'traffic': recorded_traffic('k_wgrad_256_128_64_b32')[0] if (args.batch, rl) == (32, (256, 128, 64)) else None}}
+        alg_bytes = 4.0 * (args.batch * rl[0] * rl[2] ** 2 + args.batch * rl[1] * rl[2] ** 2 + 16 * rl[0] * rl[1])
+        if wf_ is not None:
+            roof = wino_line('k_wino<64 ch x 64 tiles x 16 positions> (hg_wino_conv2d: Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32) ' + where,
+                             fl, wf_, {
+                'traffic': recorded_traffic('k_wino_fwd_256_128_64_b32')[0] if (args.batch, rl) == (32, (256, 128, 64)) else None,
+                'traffic_unit': 'bytes/launch (FETCH_SIZE + WRITE_SIZE)',
+                'traffic_source': recorded_traffic('k_wino_fwd_256_128_64_b32')[1],
+                'algorithmic_bytes_per_launch': alg_bytes})
+            if ww_ is not None:
+                roof['wgrad'] = wino_line('k_wino_wgrad + k_wino_wgrad_reduce (hg_wino_wgrad), same layer', fl, ww_, {
+                    'traffic': recorded_traffic('k_wino_wgrad_256_128_64_b32')[0] if (args.batch, rl) == (32, (256, 128, 64)) else None,
+                    'traffic_unit': 'bytes/launch of k_wino_wgrad alone (the reduce reads its 67 MB of slabs once more)'})
+            if wd_ is not None:
+                roof['dgrad'] = wino_line('k_wino (hg_wino_conv2d on the data-gradient operand), same layer', fl, wd_)
+            roof['direct_kernel'] = direct_line
+        else:
+            roof = direct_line
+            roof['algorithmic_bytes_per_launch'] = alg_bytes
+        # the generator's fourteen 3x3 layers as the library dispatches them (Winograd where hg_wino_*_supported, else direct)
+        disp = [sum((v['wino'][i] if v['wino'][i] is not None else v['direct'][i]) for v in ct.values()) for i in range(3)]
+        dire = [sum(v['direct'][i] for v in ct.values()) for i in range(3)]
+        flp = sum(v['flops'] for v in ct.values())
+        roof['generator_3x3_layers'] = {
+            'direct_conv_flops_per_pass': flp,
+            'as_dispatched': {'fwd_ms': disp[0] * 1e3, 'dgrad_ms': disp[1] * 1e3, 'wgrad_ms': disp[2] * 1e3,
+                              'fwd_direct_equivalent_tflops': flp / disp[0] / 1e12, 'dgrad_direct_equivalent_tflops': flp / disp[1] / 1e12,
+                              'wgrad_direct_equivalent_tflops': flp / disp[2] / 1e12,
+                              'layers_on_winograd': {'fwd': sum(v['wino'][0] is not None for v in ct.values()),
+                                                     'dgrad': sum(v['wino'][1] is not None for v in ct.values()),
+                                                     'wgrad': sum(v['wino'][2] is not None for v in ct.values()), 'of': len(ct)}},
+            'direct_kernels': {'fwd_ms': dire[0] * 1e3, 'dgrad_ms': dire[1] * 1e3, 'wgrad_ms': dire[2] * 1e3,
+                               'fwd_tflops': flp / dire[0] / 1e12, 'dgrad_tflops': flp / dire[1] / 1e12,
+                               'wgrad_tflops': flp / dire[2] / 1e12}}
+        roof['hist'] = hist_roof
+        try:
+            roof['leading_kernels'] = leading_kernel_lines(dev, args.batch, ct, args.size, args.capacity)
+        except Exception as e:
+            roof['leading_kernels'] = {'error': f'{type(e).__name__}: {str(e)[:160]}'}
+    else:
+        roof = hist_roof
+
+    full = {'roofline': roof,
+            'hist_hbm_gbps_algorithmic': (work['bytes_fwd'] + work['bytes_bwd']) / (t_fwd + t_bwd) / 1e9,
+            'hist_hbm_frac_of_peak': (work['bytes_fwd'] + work['bytes_bwd']) / (t_fwd + t_bwd) / 1e9 / HBM_PEAK_GBPS}
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.workload != 'rehistogan':      # the CPU baseline is quoted for the headline workloads only
+            full['cpu_baseline'] = cpu_baseline_train(args) if args.workload == 'train' else cpu_baseline(args)
+            full['cpu_baseline_hist_c1'] = cpu_baseline_hist_c1(args)
+        if args.workload == 'train' and not args.no_reference_eager:
+            full['reference_eager_rocm'] = reference_eager_rocm(args, dev)
+    return full
 
 
 def claim_stdout():
@@ -620,13 +774,19 @@ def main():
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--bins', type=int, default=64)
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true', help='also the stand-alone kernel timings (roofline), the data-parallel '
+                    'probe, the CPU baselines and the reference-eager timing, each outside the timed steps')
     ap.add_argument('--cpu-images', type=int, default=4)
     ap.add_argument('--cpu-reps', type=int, default=5)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-reference-eager', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true', help='skip the stand-alone kernel timings (tests only)')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the stand-alone kernel timings and the '
+                    'CPU / reference baselines (tests only)')
     ap.add_argument('--no-alt-precision', action='store_true', help='(accepted and ignored: the bf16x6 secondary line was removed in round 6)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.workload == 'c5':
         # BASELINE.json configs[4]: HistoGAN 1024^2 (capacity 16, discriminator attention on), batch 8 per GPU, h = 128
@@ -662,16 +822,16 @@ def main():
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
 
-    hstep, time_kernels, work, hinfo, units = hist_workload(args, dev, rank, world)
+    seed_everything(BENCH_SEED + rank)
     if args.workload == 'train':
         step, info, units = train_workload(args, dev, rank, world)
     elif args.workload == 'rehistogan':
         step, info, units = rehistogan_workload(args, dev, rank, world)
     else:
-        step, info = hstep, hinfo
+        step, _, _, info, units = hist_workload(args, dev, rank, world)
 
     ddp_info = None
-    if dist:
+    if dist and args.full:
         ddp_info = ddp_probe(dist, dev, rank, world, getattr(step, 'trainer', None))
     for _ in range(args.warmup):
         step()
@@ -737,93 +897,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    if args.no_roofline:
-        if rank == 0:
-            print(json.dumps({'metric': METRIC, 'value': units * world * args.steps / dt, 'unit': 'images/s', 'n_gpus': world,
-                              'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
-                              'config': info, 'ddp': ddp_info, 'roofline': None,
-                              'graph_replayed_steps': int(sum(graphed))}), file=json_out, flush=True)
-        if dist:
-            dist.destroy_process_group()
-        return
-    t_fwd, t_bwd = time_kernels(min(max(args.steps, 5), 20))
-    hist_roof = {'kernel': 'k_hist_bwd', 'bound': 'mfma', 'achieved': work['flops_bwd'] / t_bwd / 1e12,
-                 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': work['flops_bwd'] / t_bwd / 1e12 / FP32_PEAK_TFLOPS,
-                 'traffic': recorded_traffic('k_hist_bwd_c2')[0] if (args.batch, args.size, args.bins) == (32, 256, 64) else None,
-                 'traffic_source': recorded_traffic('k_hist_bwd_c2')[1],
-                 'launch_ms': t_bwd * 1e3,
-                 'fwd': {'kernel': 'k_hist_fwd', 'achieved': work['flops_fwd'] / t_fwd / 1e12,
-                         'frac': work['flops_fwd'] / t_fwd / 1e12 / FP32_PEAK_TFLOPS, 'launch_ms': t_fwd * 1e3}}
-    # the HBM-side method of the same block: thresholding on the scatter-add / gather kernels
-    tt_f, tt_b = time_kernels(min(max(args.steps, 5), 20), 'thresholding')
-    thr_gbps = (work['bytes_fwd'] + work['bytes_bwd']) / (tt_f + tt_b) / 1e9
-    hist_roof['thresholding'] = {'kernels': 'k_thr_fwd_lean + k_hist_finish / k_thr_bwd_lean', 'bound': 'hbm',
-                                 'fwd_ms': tt_f * 1e3, 'bwd_ms': tt_b * 1e3, 'achieved': thr_gbps, 'peak': HBM_PEAK_GBPS,
-                                 'unit': 'GB/s', 'frac': thr_gbps / HBM_PEAK_GBPS,
-                                 'traffic': recorded_traffic('thr_fwd_bwd_c2')[0] if (args.batch, args.size, args.bins) == (32, 256, 64) else None,
-                                 'traffic_source': recorded_traffic('thr_fwd_bwd_c2')[1],
-                                 'north_star_hbm_target': 0.6, 'north_star_hbm_target_met': bool(thr_gbps / HBM_PEAK_GBPS >= 0.6),
-                                 'note': 'three launches of 17 + 5 + 23 us at batch 32: launch-latency regime (78.6 MB = 9.8 us at peak)'}
-    if rank == 0 and world == 1 and (args.size, args.bins) == (256, 64) and args.batch < 256:
-        # the same kernels where the launches are long enough to stream: batch 256 (629 MB per forward + backward)
-        hist_roof['thresholding']['batch256'] = thr_probe_batch(dev, 256, args.size, args.bins)
-    if args.workload in ('train', 'rehistogan'):
-        ct = conv_kernel_times(dev, args.batch, layers=g_layers(args.size, args.capacity))
-        rl = (16 * args.capacity, 8 * args.capacity, args.size // 4)        # 256 -> 128 channels at a quarter of the image size
-        fl = ct[rl]['flops']
-        tf, td, tw = ct[rl]['direct']
-        wf_, wd_, ww_ = ct[rl]['wino']
-        where = 'at %d->%d ch, %dx%d, batch %d' % (rl[0], rl[1], rl[2], rl[2], args.batch)
-        direct_line = {'kernel': 'k_conv<128ch x 128px tile, 3x3, stride 1> (hg_conv2d_fwd, direct implicit GEMM: the kernel the '
-                                 'Winograd form replaced on this layer) ' + where, 'bound': 'mfma',
-                       'achieved': fl / tf / 1e12, 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                       'frac': fl / tf / 1e12 / FP32_PEAK_TFLOPS, 'launch_ms': tf * 1e3, 'flops_per_launch': fl,
-                       'traffic': recorded_traffic('k_conv_fwd_256_128_64_b32')[0] if (args.batch, rl) == (32, (256, 128, 64)) else None,
-                       'traffic_source': recorded_traffic('k_conv_fwd_256_128_64_b32')[1],
-                       'wgrad': {'kernel': 'k_wgrad (hg_conv2d_wgrad), same layer', 'achieved': fl / tw / 1e12,
-                                 'frac': fl / tw / 1e12 / FP32_PEAK_TFLOPS, 'launch_ms': tw * 1e3,
-                                 'traffic': recorded_traffic('k_wgrad_256_128_64_b32')[0] if (args.batch, rl) == (32, (256, 128, 64)) else None}}
-        alg_bytes = 4.0 * (args.batch * rl[0] * rl[2] ** 2 + args.batch * rl[1] * rl[2] ** 2 + 16 * rl[0] * rl[1])
-        if wf_ is not None:
-            roof = wino_line('k_wino<64 ch x 64 tiles x 16 positions> (hg_wino_conv2d: Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32) ' + where,
-                             fl, wf_, {
-                'traffic': recorded_traffic('k_wino_fwd_256_128_64_b32')[0] if (args.batch, rl) == (32, (256, 128, 64)) else None,
-                'traffic_unit': 'bytes/launch (FETCH_SIZE + WRITE_SIZE)',
-                'traffic_source': recorded_traffic('k_wino_fwd_256_128_64_b32')[1],
-                'algorithmic_bytes_per_launch': alg_bytes})
-            if ww_ is not None:
-                roof['wgrad'] = wino_line('k_wino_wgrad + k_wino_wgrad_reduce (hg_wino_wgrad), same layer', fl, ww_, {
-                    'traffic': recorded_traffic('k_wino_wgrad_256_128_64_b32')[0] if (args.batch, rl) == (32, (256, 128, 64)) else None,
-                    'traffic_unit': 'bytes/launch of k_wino_wgrad alone (the reduce reads its 67 MB of slabs once more)'})
-            if wd_ is not None:
-                roof['dgrad'] = wino_line('k_wino (hg_wino_conv2d on the data-gradient operand), same layer', fl, wd_)
-            roof['direct_kernel'] = direct_line
-        else:
-            roof = direct_line
-            roof['algorithmic_bytes_per_launch'] = alg_bytes
-        # the generator's fourteen 3x3 layers as the library dispatches them (Winograd where hg_wino_*_supported, else direct)
-        disp = [sum((v['wino'][i] if v['wino'][i] is not None else v['direct'][i]) for v in ct.values()) for i in range(3)]
-        dire = [sum(v['direct'][i] for v in ct.values()) for i in range(3)]
-        flp = sum(v['flops'] for v in ct.values())
-        roof['generator_3x3_layers'] = {
-            'direct_conv_flops_per_pass': flp,
-            'as_dispatched': {'fwd_ms': disp[0] * 1e3, 'dgrad_ms': disp[1] * 1e3, 'wgrad_ms': disp[2] * 1e3,
-                              'fwd_direct_equivalent_tflops': flp / disp[0] / 1e12, 'dgrad_direct_equivalent_tflops': flp / disp[1] / 1e12,
-                              'wgrad_direct_equivalent_tflops': flp / disp[2] / 1e12,
-                              'layers_on_winograd': {'fwd': sum(v['wino'][0] is not None for v in ct.values()),
-                                                     'dgrad': sum(v['wino'][1] is not None for v in ct.values()),
-                                                     'wgrad': sum(v['wino'][2] is not None for v in ct.values()), 'of': len(ct)}},
-            'direct_kernels': {'fwd_ms': dire[0] * 1e3, 'dgrad_ms': dire[1] * 1e3, 'wgrad_ms': dire[2] * 1e3,
-                               'fwd_tflops': flp / dire[0] / 1e12, 'dgrad_tflops': flp / dire[1] / 1e12,
-                               'wgrad_tflops': flp / dire[2] / 1e12}}
-        roof['hist'] = hist_roof
-        try:
-            roof['leading_kernels'] = leading_kernel_lines(dev, args.batch, ct, args.size, args.capacity)
-        except Exception as e:
-            roof['leading_kernels'] = {'error': f'{type(e).__name__}: {str(e)[:160]}'}
-    else:
-        roof = hist_roof
-
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.outputs())
     if rank == 0:
         out = {
             'metric': METRIC, 'value': units * world * args.steps / dt, 'unit': 'images/s',
@@ -831,9 +906,7 @@ def main():
             'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
             'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'config': info,
-            'roofline': roof,
-            'hist_hbm_gbps_algorithmic': (work['bytes_fwd'] + work['bytes_bwd']) / (t_fwd + t_bwd) / 1e9,
-            'hist_hbm_frac_of_peak': (work['bytes_fwd'] + work['bytes_bwd']) / (t_fwd + t_bwd) / 1e9 / HBM_PEAK_GBPS,
+            'graph_replayed_steps': int(sum(graphed)),
         }
         if kinds:
             mean = lambda k: (sum(t for t, kk in zip(per_step, kinds) if kk == k) / max(1, kinds.count(k))) * 1e3
@@ -854,14 +927,13 @@ def main():
                            'graph_replayed_steps': int(sum(graphed)),
                            'launches_per_plain_step_eager': recorded_value('launches_per_plain_step'),
                            'host_calls_per_graphed_step': 1 if any(graphed) else None}
-        if dist:
+        if dist and args.full:
             out['ddp'] = ddp_info
-        if world == 1 and not args.no_cpu_baseline:
-            if args.workload != 'rehistogan':      # the CPU baseline is quoted for the headline workloads only
-                out['cpu_baseline'] = cpu_baseline_train(args) if args.workload == 'train' else cpu_baseline(args)
-                out['cpu_baseline_hist_c1'] = cpu_baseline_hist_c1(args)
-            if args.workload == 'train' and not args.no_reference_eager:
-                out['reference_eager_rocm'] = reference_eager_rocm(args, dev)
+    if args.full:
+        full = {'roofline': None} if args.no_roofline else full_measurements(args, dev, rank, world)
+        if rank == 0:
+            out.update(full)
+    if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)
     if dist:
         dist.destroy_process_group()

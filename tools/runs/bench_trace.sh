@@ -5,7 +5,7 @@ set -u
 TAG=${1:-bench_trace}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-(cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python $ROOT/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-reference-eager --no-alt-precision > $OUT/bench.json 2> $OUT/bench.err)
+(cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python $ROOT/bench.py --steps 8 --warmup 2 --full --no-cpu-baseline --no-reference-eager --no-alt-precision > $OUT/bench.json 2> $OUT/bench.err)
 python tools/kstats.py $OUT/trace | head -40 > $OUT/bench_kernel_stats.txt
 python - $OUT/bench.json <<'PY'
 import json,sys

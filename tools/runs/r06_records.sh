@@ -33,12 +33,12 @@ bash tools/conv_traffic.sh gpurun_out/$TAG/conv_traffic > $OUT/conv_traffic.log 
 HG_HIST_METHOD=thresholding bash tools/hist_traffic.sh gpurun_out/$TAG/thr_traffic > $OUT/thr_traffic.log 2>&1; tail -5 $OUT/thr_traffic.log
 fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-timeout 600 python bench.py --workload hist > $OUT/bench_hist.json 2> $OUT/bench_hist.err
-timeout 600 python bench.py --workload rehistogan --no-cpu-baseline > $OUT/bench_rehistogan.json 2> $OUT/bench_rehistogan.err
-timeout 900 python bench.py --workload c5 --no-cpu-baseline --no-reference-eager > $OUT/bench_c5.json 2> $OUT/bench_c5.err
-HG_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 12 --warmup 4 --no-roofline > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.json 2> $OUT/bench_driver.err
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 600 python bench.py --workload hist --full > $OUT/bench_hist.json 2> $OUT/bench_hist.err
+timeout 600 python bench.py --workload rehistogan --no-cpu-baseline --full > $OUT/bench_rehistogan.json 2> $OUT/bench_rehistogan.err
+timeout 900 python bench.py --workload c5 --no-cpu-baseline --no-reference-eager --full > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+HG_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 12 --warmup 4 --full --no-roofline > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
 bash tools/runs/bench_trace.sh $TAG/bench_trace > $OUT/bench_trace.log 2>&1; tail -2 $OUT/bench_trace.log
 for f in bench_driver bench_default bench_hist bench_rehistogan bench_c5 bench_n2_gloo; do python - $OUT/$f.json <<'PY'
 import json,sys

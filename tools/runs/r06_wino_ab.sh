@@ -5,7 +5,7 @@ set -u
 TAG=${1:-r06wino}; LT=${2:-nobp}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 timeout 600 python -m pytest tests/test_wino_gpu.py tests/test_conv_gpu.py -x -q -p no:cacheprovider 2>&1 | tail -2
-B="--gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-reference-eager"
+B="--gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-reference-eager"
 for rep in 1 2; do
 timeout 600 python bench.py $B > $OUT/bench_new_$rep.json 2> /dev/null
 HG_LIB_TAG=$LT timeout 600 python bench.py $B > $OUT/bench_old_$rep.json 2> /dev/null

@@ -20,10 +20,10 @@ python tools/trace_timeline.py $DB 12 > $OUT/step_timeline.txt 2>&1
 python tools/rocpd_stats.py $DB $OUT/kernel_stats.md > /dev/null 2>&1
 rm -rf $OUT/trace
 head -7 $OUT/step_timeline.txt
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err
-timeout 600 python bench.py --workload hist > $OUT/bench_hist.json 2> $OUT/bench_hist.err
-timeout 600 python bench.py --workload rehistogan --no-cpu-baseline > $OUT/bench_rehistogan.json 2> $OUT/bench_rehistogan.err
-HG_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 12 --warmup 4 --no-roofline > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.json 2> $OUT/bench_driver.err
+timeout 600 python bench.py --workload hist --full > $OUT/bench_hist.json 2> $OUT/bench_hist.err
+timeout 600 python bench.py --workload rehistogan --no-cpu-baseline --full > $OUT/bench_rehistogan.json 2> $OUT/bench_rehistogan.err
+HG_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 12 --warmup 4 --full --no-roofline > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
 for f in bench_driver bench_hist bench_rehistogan bench_n2_gloo; do python - $OUT/$f.json <<'PY'
 import json,sys
 L=[l for l in open(sys.argv[1]).read().splitlines() if l.strip()]
