@@ -3,7 +3,6 @@ chain it replaces (GeneratorBlock.forward / Conv2DMod / RGBBlock, histoGAN/histo
 one-node generator (histogan_amd/gfused.py) against the per-block autograd path."""
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import relmax
 
@@ -28,30 +27,12 @@ CASES = [
 
 @pytest.mark.parametrize('B,Cc,H,S,up,rgb', CASES)
 def test_gstage_bwd_matches_fp64_autograd(B, Cc, H, S, up, rgb, gpu_device):
-    from histogan_amd.gfused import gstage_bwd
+    from gstage_ref import gstage_fp64, gstage_inputs, run_gstage
     g = torch.Generator().manual_seed(B * 1000 + Cc * 10 + H)
-    dev = gpu_device
-    rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
-    conv, d = rnd(B, Cc, H, H), torch.rand(B, Cc, generator=g, dtype=torch.float64) + 0.5
-    nzt, wn, bn = torch.rand(B, S, S, generator=g, dtype=torch.float64), rnd(Cc) * 0.5, rnd(Cc) * 0.2
-    sa, srgb, w = rnd(B, Cc) * 0.5, rnd(B, Cc) * 0.5, rnd(3, Cc)
     has_a = up is not None
-    ga = rnd(B, Cc, 2 * H, 2 * H) if up else (rnd(B, Cc, H, H) if has_a else None)
-    g_rgb = rnd(B, 3, H, H) if rgb else None
-    leaves = [t.requires_grad_(True) for t in (conv, d, wn, bn, sa, srgb, w)]
-    pre = conv * d[:, :, None, None] + wn[None, :, None, None] * nzt[:, None, :H, :H] + bn[None, :, None, None]
-    out = F.leaky_relu(pre, 0.2)
-    loss = 0.0
-    if has_a:
-        xa = F.interpolate(out, scale_factor=2, mode='bilinear', align_corners=False) if up else out
-        loss = loss + (xa * (sa + 1)[:, :, None, None] * ga).sum()
-    if rgb:
-        loss = loss + (torch.einsum('kc,bcij->bkij', w, out * (srgb + 1)[:, :, None, None]) * g_rgb).sum()
-    want = torch.autograd.grad(loss, leaves, allow_unused=True)
-    f = lambda t: None if t is None else t.detach().float().to(dev).contiguous()
-    gconv, gs_a, gs_rgb, gw_rgb, gd, gwn, gbn = gstage_bwd(f(out), f(ga), f(sa) if has_a else None, bool(up), f(g_rgb),
-                                                           f(w) if rgb else None, f(srgb) if rgb else None, f(d), f(nzt),
-                                                           f(wn), f(bn))
+    inp = gstage_inputs(B, Cc, H, S, up, rgb, g)
+    out, want = gstage_fp64(inp, up, rgb)
+    gconv, gs_a, gs_rgb, gw_rgb, gd, gwn, gbn = run_gstage(out, inp, up, rgb, gpu_device)
     torch.cuda.synchronize()
     tol = 2e-5
     assert relmax(gconv.cpu().numpy(), want[0].numpy()) <= tol
