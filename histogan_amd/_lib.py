@@ -189,12 +189,31 @@ def _load():
     lib.hg_sample_mean.argtypes = [vp, vp, i32, i64, vp, sz, vp]
     lib.hg_augment_color.restype = ctypes.c_int
     lib.hg_augment_color.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    # include/hg_post.h
+    lib.hg_resize_axis.restype = ctypes.c_int
+    lib.hg_resize_axis.argtypes = [vp, i32, i64, i64, i64, i32, vp, i32, i64, i64, i64, i32, i32, i32, i32, vp, vp, i32,
+                                   i32, vp]
+    lib.hg_pyr_down.restype = ctypes.c_int
+    lib.hg_pyr_down.argtypes = [vp, vp, i32, i32, i32, vp]
+    lib.hg_pyr_up_add.restype = ctypes.c_int
+    lib.hg_pyr_up_add.argtypes = [vp, vp, vp, f32, vp, vp, f32, vp, i32, i32, i32, vp]
+    lib.hg_color_moments_workspace_bytes.restype = sz
+    lib.hg_color_moments_workspace_bytes.argtypes = [i64]
+    lib.hg_color_moments.restype = ctypes.c_int
+    lib.hg_color_moments.argtypes = [vp, i64, i64, i64, vp, vp, sz, vp]
+    lib.hg_color_affine.restype = ctypes.c_int
+    lib.hg_color_affine.argtypes = [vp, i64, i64, i64, ctypes.POINTER(f32), vp, i32, vp]
+    lib.hg_u8_hwc_to_f32.restype = ctypes.c_int
+    lib.hg_u8_hwc_to_f32.argtypes = [vp, vp, i32, i64, vp]
+    lib.hg_f32_to_u8_hwc.restype = ctypes.c_int
+    lib.hg_f32_to_u8_hwc.argtypes = [vp, vp, i32, i64, vp]
     return lib
 
 
 lib = _load()
 
-# every symbol include/hg_hist.h, hg_nets.h, hg_conv.h, hg_recolor.h, hg_augment.h, hg_linear.h and hg_wino.h declare
+# every symbol include/hg_hist.h, hg_nets.h, hg_conv.h, hg_recolor.h, hg_augment.h, hg_linear.h, hg_wino.h and hg_post.h
+# declare
 EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg_rgbuv_hist_uses_proj_cache', 'hg_rgbuv_hist_fwd',
            'hg_rgbuv_hist_bwd', 'hg_hellinger_workspace_bytes', 'hg_hellinger_fwd_bwd', 'hg_selftest_fastlog',
            'hg_modulate_fwd', 'hg_modulate_bwd', 'hg_demod_noise_lrelu_fwd', 'hg_demod_noise_lrelu_bwd',
@@ -208,7 +227,9 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
            'hg_grouped_linear_bwd_input', 'hg_grouped_linear_bwd_params',
            'hg_wino_supported', 'hg_wino_packed_elems', 'hg_wino_pack_weights', 'hg_wino_pack_blocks', 'hg_wino_pack_weights_multi', 'hg_wino_workspace_bytes', 'hg_wino_conv2d',
            'hg_wino_wgrad_supported', 'hg_wino_wgrad_workspace_bytes', 'hg_wino_wgrad',
-           'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd')
+           'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd',
+           'hg_resize_axis', 'hg_pyr_down', 'hg_pyr_up_add', 'hg_color_moments_workspace_bytes', 'hg_color_moments',
+           'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc')
 
 
 class HgError(RuntimeError):

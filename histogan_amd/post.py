@@ -1,0 +1,340 @@
+"""Full-resolution output of ReHistoGAN on the MI355X kernels of include/hg_post.h.
+
+The reference's `rehistoGAN.py --generate` offers two ways to carry its 256x256 result back to the photo
+(ReHistoGAN/rehistoGAN.py:1135-1165): the Laplacian-pyramid detail swap of utils/pyramid_upsampling.py on top of the
+MATLAB-bicubic utils/imresize.py, and the Monge-Kantorovich linear colour transfer of utils/color_transfer_MKL.py.  Both
+are numpy / OpenCV in float64 there; here every pass over the image is a HIP kernel on the caller's stream, and only the
+host-built resize tables (fp64, passed as fp32) and the 3x3 algebra of MKL stay on the host.
+
+Device layouts: float images are (C, H, W) -- any strides -- and come back contiguous; uint8 images are (H, W, C), as
+PIL and the reference's uint8 path hold them.  The drop-ins at the reference's import paths (utils/imresize.py,
+utils/pyramid_upsampling.py, utils/color_transfer_MKL.py) convert to and from the reference's host types around these.
+"""
+import ctypes
+from functools import lru_cache
+from math import ceil
+
+import numpy as np
+import torch
+
+from ._lib import check, lib, on_device, raw_stream
+
+EPS = 2.2204e-16          # utils/color_transfer_MKL.py:3
+
+
+# ---- host: the resize tables (utils/imresize.py:21-55) ----------------------------------------------------------------
+def cubic(x):
+    """Keys' cubic with a = -0.5, MATLAB's bicubic kernel."""
+    a = np.abs(np.asarray(x, dtype=np.float64))
+    a2, a3 = a * a, a * a * a
+    return (1.5 * a3 - 2.5 * a2 + 1) * (a <= 1) + (-0.5 * a3 + 2.5 * a2 - 4 * a + 2) * ((a > 1) & (a <= 2))
+
+
+def triangle(x):
+    """The bilinear ('triangle') kernel, 1 - |x| on [-1, 1]."""
+    x = np.asarray(x, dtype=np.float64)
+    return (x + 1) * ((x >= -1) & (x < 0)) + (1 - x) * ((x >= 0) & (x <= 1))
+
+
+KERNELS = {'bicubic': cubic, 'bilinear': triangle}
+KERNEL_WIDTH = 4.0        # the reference widens every kernel to 4 taps, the triangle included
+
+
+def contributions(in_length, out_length, scale, kernel, k_width):
+    """(weights, indices), each (out_length, taps): output sample i is sum_t weights[i, t] * x[indices[i, t]].
+    Output centre i (1-based) maps to u = i/scale + (1 - 1/scale)/2 in the input; P = ceil(width) + 2 taps start at
+    floor(u - width/2); down-scaling (scale < 1) stretches the kernel by 1/scale.  Rows are normalised, indices outside
+    [0, in_length) fold with period 2*in_length repeating the edge sample, and taps that are zero for every output
+    are dropped.  fp64 throughout."""
+    if scale < 1:
+        width = k_width / scale
+        h = lambda t: scale * kernel(scale * t)  # noqa: E731
+    else:
+        width, h = k_width, kernel
+    u = np.arange(1, out_length + 1, dtype=np.float64) / scale + 0.5 * (1 - 1 / scale)
+    first = np.floor(u - width / 2)
+    taps = int(ceil(width)) + 2
+    idx = (first[:, None] + np.arange(taps) - 1).astype(np.int32)
+    w = h(u[:, None] - idx - 1)
+    w = w / w.sum(axis=1, keepdims=True)
+    fold = np.concatenate([np.arange(in_length), np.arange(in_length - 1, -1, -1)]).astype(np.int32)
+    idx = fold[np.mod(idx, fold.size)]
+    keep = np.any(w != 0, axis=0)
+    return w[:, keep], idx[:, keep]
+
+
+def resize_plan(in_hw, output_shape=None, scalar_scale=None):
+    """(out_hw, scale): the reference's deriveSizeFromScale / deriveScaleFromSize (utils/imresize.py:8-19)."""
+    if scalar_scale is not None:
+        s = float(scalar_scale)
+        return [int(ceil(s * in_hw[k])) for k in range(2)], [s, s]
+    if output_shape is None:
+        raise ValueError('imresize: give output_shape or scalar_scale')
+    out = [int(output_shape[0]), int(output_shape[1])]
+    return out, [1.0 * out[k] / in_hw[k] for k in range(2)]
+
+
+@lru_cache(maxsize=64)
+def _tables(n_in, n_out, scale, method, device):
+    w, i = contributions(n_in, n_out, scale, KERNELS[method], KERNEL_WIDTH)
+    dev = torch.device(device)
+    return (torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(dev),
+            torch.from_numpy(np.ascontiguousarray(i, dtype=np.int32)).to(dev), w.shape[1])
+
+
+def _need_cuda(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f'{what}: expects a tensor on the GPU; the MI355X-native path has no CPU implementation')
+
+
+# ---- device: resize ---------------------------------------------------------------------------------------------------
+def _resize_axis(x, x_u8, xs, C, H, W, axis, out, out_u8, os_, n_out, scale, method, clamp):
+    wt, ind, taps = _tables(H if axis == 0 else W, n_out, scale, method, str(x.device))
+    check(lib.hg_resize_axis(x.data_ptr(), int(x_u8), xs[0], xs[1], xs[2], int(clamp), out.data_ptr(), int(out_u8),
+                             os_[0], os_[1], os_[2], C, H, W, axis, wt.data_ptr(), ind.data_ptr(), n_out, taps,
+                             raw_stream(x.device)), 'hg_resize_axis')
+
+
+def imresize(x, output_shape=None, scalar_scale=None, method='bicubic', clamp=False):
+    """MATLAB imresize (utils/imresize.py:98-136) on the GPU.  x: float (C, H, W) / (H, W), any strides, or uint8
+    (H, W, C) / (H, W).  Returns fp32 (C, H', W') / (H', W') contiguous, or uint8 (H', W', C) / (H', W') with the
+    reference's clip + round-half-to-even after EACH pass (its uint8 path rounds the intermediate too).  The axis with
+    the smaller scale is resized first (the reference's argsort).  clamp: clamp the input to [0, 1] as it is read."""
+    _need_cuda(x, 'imresize')
+    if method not in KERNELS:
+        raise ValueError(f"imresize: method must be 'bicubic' or 'bilinear', not {method!r}")
+    u8 = x.dtype == torch.uint8
+    if not u8 and x.dtype != torch.float32:
+        x = x.float()
+    if x.dim() not in (2, 3):
+        raise ValueError(f'imresize: expects a 2-D or 3-D image, got shape {tuple(x.shape)}')
+    flat = x.dim() == 2
+    if u8:
+        v = x.unsqueeze(2) if flat else x
+        H, W, C = v.shape
+        xs = (v.stride(2), v.stride(0), v.stride(1))
+    else:
+        v = x.unsqueeze(0) if flat else x
+        C, H, W = v.shape
+        xs = (v.stride(0), v.stride(1), v.stride(2))
+    (Ho, Wo), scale = resize_plan((H, W), output_shape, scalar_scale)
+    order = [0, 1] if scale[0] <= scale[1] else [1, 0]
+    cur = [H, W]
+    src, src_s = v, xs
+    with on_device(x.device):
+        for step, axis in enumerate(order):
+            ih, iw = cur
+            cur[axis] = (Ho, Wo)[axis]
+            h, w = cur
+            if u8:
+                dst = torch.empty((h, w, C), dtype=torch.uint8, device=x.device)
+                ds = (1, w * C, C)
+            else:
+                dst = torch.empty((C, h, w), dtype=torch.float32, device=x.device)
+                ds = (h * w, w, 1)
+            _resize_axis(src, u8, src_s, C, ih, iw, axis, dst, u8, ds, cur[axis], scale[axis], method,
+                         clamp and step == 0)
+            src, src_s = dst, ds
+    if flat:
+        return src[:, :, 0] if u8 else src[0]
+    return src
+
+
+# ---- device: layout conversions -----------------------------------------------------------------------------------------
+def u8_hwc_to_float(x):
+    """uint8 (H, W, C) -> fp32 (C, H, W) = x / 255 (torchvision ToTensor)."""
+    _need_cuda(x, 'u8_hwc_to_float')
+    x = x.contiguous()
+    H, W, C = x.shape
+    out = torch.empty((C, H, W), dtype=torch.float32, device=x.device)
+    with on_device(x.device):
+        check(lib.hg_u8_hwc_to_f32(x.data_ptr(), out.data_ptr(), C, H * W, raw_stream(x.device)), 'hg_u8_hwc_to_f32')
+    return out
+
+
+def float_to_u8_hwc(x):
+    """fp32 (C, H, W) -> uint8 (H, W, C) = clamp(x*255 + 0.5, 0, 255) truncated (torchvision save_image)."""
+    _need_cuda(x, 'float_to_u8_hwc')
+    x = x.float().contiguous()
+    C, H, W = x.shape
+    out = torch.empty((H, W, C), dtype=torch.uint8, device=x.device)
+    with on_device(x.device):
+        check(lib.hg_f32_to_u8_hwc(x.data_ptr(), out.data_ptr(), C, H * W, raw_stream(x.device)), 'hg_f32_to_u8_hwc')
+    return out
+
+
+# ---- device: pyramids -------------------------------------------------------------------------------------------------
+def pyr_down(x):
+    """OpenCV pyrDown of fp32 (C, H, W): (C, (H+1)//2, (W+1)//2)."""
+    x = x.contiguous()
+    C, H, W = x.shape
+    out = torch.empty((C, (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=x.device)
+    check(lib.hg_pyr_down(x.data_ptr(), out.data_ptr(), C, H, W, raw_stream(x.device)), 'hg_pyr_down')
+    return out
+
+
+def pyr_up_add(prev, fine_a=None, coarse_a=None, wa=0.0, fine_b=None, coarse_b=None, wb=0.0):
+    """pyrUp(prev) + wa*(fine_a - pyrUp(coarse_a)) + wb*(fine_b - pyrUp(coarse_b)), one launch (include/hg_post.h)."""
+    C, h, w = prev.shape
+    out = torch.empty((C, 2 * h, 2 * w), dtype=torch.float32, device=prev.device)
+    ptr = lambda t, wt: t.data_ptr() if (t is not None and wt != 0) else None  # noqa: E731
+    check(lib.hg_pyr_up_add(prev.data_ptr(), ptr(fine_a, wa), ptr(coarse_a, wa), float(wa), ptr(fine_b, wb),
+                            ptr(coarse_b, wb), float(wb), out.data_ptr(), C, h, w, raw_stream(prev.device)),
+          'hg_pyr_up_add')
+    return out
+
+
+def _as_chw3(t, what):
+    if t.dim() == 4:
+        if t.shape[0] != 1:
+            raise ValueError(f'pyramid_upsampling: {what} must be a single image, got batch {t.shape[0]}')
+        t = t[0]
+    if t.dim() != 3 or t.shape[0] != 3:
+        raise ValueError(f'pyramid_upsampling: {what} must be a 3-channel (3, H, W) image, got {tuple(t.shape)}')
+    return t
+
+
+def level_weights(levels, swapping_levels, blending):
+    """(a_k, b_k) for k = 0..levels-1: the Laplacian used at level k is a_k * target's + b_k * reference's
+    (utils/pyramid_upsampling.py:76-81).  Raises IndexError where the reference does."""
+    if levels < 1:
+        raise ValueError(f'pyramid_upsampling: levels must be >= 1, got {levels}')
+    if swapping_levels < 0:
+        raise ValueError(f'pyramid_upsampling: swapping_levels must be >= 0, got {swapping_levels}')
+    if swapping_levels > levels:
+        raise IndexError(f'pyramid_upsampling: swapping_levels={swapping_levels} exceeds levels={levels} (the '
+                         'reference indexes past its pyramid)')
+    ab = [(1.0, 0.0) if k < swapping_levels else (0.0, 1.0) for k in range(levels)]
+    if blending and swapping_levels < levels:
+        wts = np.linspace(0.0, 1.0, levels - swapping_levels + 1)
+        if levels - 1 >= wts.size:
+            raise IndexError(f'pyramid_upsampling: blending with swapping_levels={swapping_levels} >= 2 indexes '
+                             f'past its {wts.size} blending weights (as the reference does)')
+        for k in range(swapping_levels, levels):
+            ab[k] = (1.0 - float(wts[k]), float(wts[k]))
+    return ab
+
+
+def padded_size(h, w, levels):
+    """The reference's padding (utils/pyramid_upsampling.py:18-30): each side up to the next multiple of 2**levels."""
+    m = 2 ** levels
+    return (h if h % m == 0 else h + m - h % m), (w if w % m == 0 else w + m - w % m)
+
+
+def pyramid_upsampling(target, reference, levels=5, swapping_levels=1, blending=False):
+    """utils/pyramid_upsampling.py on the GPU.  target: float (1, 3, h, w) / (3, h, w), clamped to [0, 1] as it is read
+    (the caller's tensor is not modified); reference: float (1, 3, H, W) / (3, H, W), or uint8 (H, W, 3) read as x/255.
+    Returns fp32 (1, 3, H', W') on the device, where (H', W') is the reference's size padded up to multiples of
+    2**levels: a reference whose side is not such a multiple is bicubic-resized up to it and the OUTPUT KEEPS THE
+    PADDED SIZE, as the reference's does.  The Laplacian pyramid of the target (resized to that size) replaces the
+    reference's first `swapping_levels` entries [gp[levels-1], L_{levels-1}, ..., L_1]; with `blending` the remaining
+    entries are mixed with linspace(0, 1, levels - swapping_levels + 1) weights."""
+    ab = level_weights(levels, swapping_levels, blending)
+    _need_cuda(target, 'pyramid_upsampling')
+    _need_cuda(reference, 'pyramid_upsampling')
+    with on_device(reference.device):
+        if reference.dtype == torch.uint8:
+            if reference.dim() != 3 or reference.shape[2] != 3:
+                raise ValueError('pyramid_upsampling: a uint8 reference must be (H, W, 3), got '
+                                 f'{tuple(reference.shape)}')
+            ref = u8_hwc_to_float(reference)
+        else:
+            ref = _as_chw3(reference, 'reference').float()
+        tgt = _as_chw3(target, 'target').float()
+        _, H, W = ref.shape
+        Hp, Wp = padded_size(H, W, levels)
+        if (Hp, Wp) != (H, W):
+            ref = imresize(ref, output_shape=(Hp, Wp))
+        ref = ref.contiguous()
+        tgt = imresize(tgt, output_shape=(Hp, Wp), clamp=True)
+        need_a = any(a != 0 for a, _ in ab)
+        need_b = any(b != 0 for _, b in ab)
+        gpa, gpb = [tgt], [ref]
+        for _ in range(levels - 1):          # gp[levels] is never used
+            if need_a:
+                gpa.append(pyr_down(gpa[-1]))
+            if need_b:
+                gpb.append(pyr_down(gpb[-1]))
+        top = levels - 1
+        out = gpa[top] if ab[0][0] != 0 else gpb[top]
+        for k in range(1, levels):
+            a, b = ab[k]
+            fine, coarse = top - k, top - k + 1
+            out = pyr_up_add(out, gpa[fine] if a else None, gpa[coarse] if a else None, a,
+                             gpb[fine] if b else None, gpb[coarse] if b else None, b)
+        if out.data_ptr() == reference.data_ptr():
+            out = out.clone()                # levels == 1 without swap: never hand back the caller's own storage
+    return out.unsqueeze(0)
+
+
+# ---- colour transfer (utils/color_transfer_MKL.py) ------------------------------------------------------------------
+def MKL(A, B):
+    """The Monge-Kantorovich linear map T with T A T = B for 3x3 covariances (fp64, host).  Negative eigenvalues are
+    clamped to 0, and EPS is added to EVERY entry of the diagonal eigenvalue matrices before their square root,
+    off-diagonal entries included (a ~1e-8 term, kept as the reference has it).  That term makes T depend on the
+    eigenvector signs LAPACK returns, at a relative size of about sqrt(EPS / smallest eigenvalue of A); for a
+    near-grey image (eigenvalue ~1e-5) a last-digit change of A moves T by ~3e-5, in the reference as here."""
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    ea, Ua = np.linalg.eig(A)
+    Da2 = np.diag(ea)
+    Da2[Da2 < 0] = 0
+    Da = np.sqrt(Da2 + EPS)
+    C = Da @ Ua.T @ B @ Ua @ Da
+    ec, Uc = np.linalg.eig(C)
+    Dc2 = np.diag(ec)
+    Dc2[Dc2 < 0] = 0
+    Dc = np.sqrt(Dc2 + EPS)
+    Da_inv = np.diag(1.0 / np.diag(Da))
+    return Ua @ Da_inv @ Uc @ Dc @ Uc.T @ Da_inv @ Ua.T
+
+
+def _pixels(t, what):
+    """(tensor, n, pix_stride, chan_stride) of an (H, W, 3) fp32 view (a CHW image's .permute(1, 2, 0) is one)."""
+    _need_cuda(t, 'color_transfer_mkl')
+    if t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f'color_transfer_mkl: {what} must be an (H, W, 3) image, got {tuple(t.shape)}')
+    t = t.float()
+    if t.stride(0) != t.shape[1] * t.stride(1) or t.stride(1) <= 0 or t.stride(2) <= 0:
+        t = t.contiguous()
+    return t, t.shape[0] * t.shape[1], t.stride(1), t.stride(2)
+
+
+def color_moments(x):
+    """(mean (3,), covariance (3, 3)) in fp64 of an (H, W, 3) device image (np.mean / np.cov over its pixels)."""
+    t, n, ps, cs = _pixels(x, 'image')
+    if n < 2:
+        raise ValueError('color_transfer_mkl: an image needs at least 2 pixels')
+    with on_device(t.device):
+        nb = lib.hg_color_moments_workspace_bytes(n)
+        ws = torch.empty(nb, dtype=torch.uint8, device=t.device)
+        mom = torch.empty(12, dtype=torch.float64, device=t.device)
+        check(lib.hg_color_moments(t.data_ptr(), n, ps, cs, mom.data_ptr(), ws.data_ptr(), nb, raw_stream(t.device)),
+              'hg_color_moments')
+        m = mom.cpu().numpy()
+    return m[:3].copy(), m[3:].reshape(3, 3).copy()
+
+
+def color_transfer_mkl(source, target, quantize=False):
+    """utils/color_transfer_MKL.py on the GPU: maps the colours of `source` onto those of `target` with the linear
+    Monge-Kantorovich transform.  source, target: (H, W, 3) fp32 device views.  Returns (out, T): out is (H, W, 3)
+    fp32 clipped to [0, 1], or uint8 = (uint8)(out*255) (the caller's np.uint8(result*255)) when quantize; T the 3x3
+    fp64 map."""
+    src, n, ps, cs = _pixels(source, 'source')
+    m0, A = color_moments(src)
+    m1, B = color_moments(target)
+    T = MKL(A, B)
+    coef = np.concatenate([m0, T.real.reshape(-1), m1]).astype(np.float32)
+    out = torch.empty(source.shape[:2] + (3,), dtype=torch.uint8 if quantize else torch.float32, device=src.device)
+    with on_device(src.device):
+        check(lib.hg_color_affine(src.data_ptr(), n, ps, cs, coef.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                  out.data_ptr(), int(quantize), raw_stream(src.device)), 'hg_color_affine')
+    return out, T
+
+
+# ---- writer -----------------------------------------------------------------------------------------------------------
+def save_rgb(u8_hwc, path):
+    """Write one uint8 (H, W, 3) image with PIL's defaults -- what torchvision.utils.save_image writes for a batch of
+    one (no grid border)."""
+    from PIL import Image
+    arr = u8_hwc.cpu().numpy() if torch.is_tensor(u8_hwc) else np.asarray(u8_hwc)
+    Image.fromarray(arr).save(path)

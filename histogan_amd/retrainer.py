@@ -443,14 +443,19 @@ class recoloringTrainer():
                  resizing_method=None, swapping_levels=1, pyramid_levels=5, level_blending=False, original_size=None,
                  input_image_name=None, original_image=None, post_recoloring=False, save_input=True):
         """Recolour a batch with its target histograms and write `<num>-generated.jpg` [+ `<num>-input.jpg`]: the
-        reference's parameter list (ReHistoGAN/rehistoGAN.py:1076-1081).  The device part (encoder-decoder + head, the
-        multi-histogram grids, the 'downscaling' resize of the written file) is implemented; the CPU / OpenCV / external
-        post-processing options -- `resizing='upscaling'` (BGU.exe or the Laplacian-pyramid swap of
-        utils/pyramid_upsampling.py) and `post_recoloring` (utils/color_transfer_MKL.py) -- are outside the hot path
-         and raise NotImplementedError when asked for."""
-        if resizing == 'upscaling' or post_recoloring:
-            raise NotImplementedError("recoloringTrainer.evaluate: resizing='upscaling' (BGU / pyramid) and post_recoloring "
-                                      'are CPU post-processing of the reference (utils/) outside the MI355X hot path')
+        reference's parameter list (ReHistoGAN/rehistoGAN.py:1076-1081).  Post-processing as in :1130-1165:
+        `resizing='downscaling'` resizes the written file to `original_size`; `resizing='upscaling'` with
+        `resizing_method='pyramid'` carries the result back to the full-resolution photo `input_image_name` with the
+        Laplacian-pyramid swap (`pyramid_levels`, `swapping_levels`, `level_blending`; histogan_amd/post.py) and writes
+        it at the photo's size padded up to multiples of 2**pyramid_levels, as the reference does; `post_recoloring`
+        then maps `original_image` (the photo, (H, W, 3) in [0, 1]) onto the colours of the unclamped network output
+        with the Monge-Kantorovich transfer and overwrites the same file at the photo's size.  Both need a batch of
+        one (ValueError otherwise).  `resizing_method='BGU'` (an external Windows executable) raises
+        NotImplementedError."""
+        upscale = resizing == 'upscaling'
+        if upscale and resizing_method != 'pyramid':
+            raise NotImplementedError(f"recoloringTrainer.evaluate: resizing_method={resizing_method!r} for 'upscaling' "
+                                      "(only 'pyramid' is implemented; BGU runs an external executable)")
         self.GAN.eval()
         if hist_batch is None or image_batch is None:
             batch = next(self.loader_evaluate)
@@ -465,6 +470,9 @@ class recoloringTrainer():
             img_bt_sz = image_batch.shape[0]
         noise = self.rng.image_noise(hist_batch.shape[0], image_batch.shape[-1])
         generated_images = self._recolor(image_batch, hist_batch, noise)
+        if (upscale or post_recoloring is True) and generated_images.shape[0] != 1:
+            raise ValueError('recoloringTrainer.evaluate: upscaling / post_recoloring need a batch of one image, got '
+                             f'{generated_images.shape[0]}')
         if num is not None and self.is_main:
             from .data import save_image_grid
             ext = 'jpg' if not self.transparent else 'png'
@@ -475,11 +483,33 @@ class recoloringTrainer():
             if resizing == 'downscaling' and original_size is not None:
                 from PIL import Image
                 Image.open(output_name).resize((original_size[0], original_size[1])).save(output_name)
+            if upscale or post_recoloring is True:
+                self._full_resolution(generated_images, output_name, upscale, pyramid_levels, swapping_levels,
+                                      level_blending, input_image_name, original_image, post_recoloring is True)
             if save_input is True:
                 save_image_grid(image_batch[:img_bt_sz] if multi else image_batch,
                                 str(self.results_dir / self.name / f'{str(num)}-input.{ext}'),
                                 nrow=img_bt_sz if multi else num_rows)
         return generated_images
+
+    def _full_resolution(self, generated_images, output_name, upscale, levels, swapping_levels, blending,
+                         input_image_name, original_image, recolor):
+        """The 'upscaling'/'pyramid' and post_recoloring branches of evaluate (ReHistoGAN/rehistoGAN.py:1142-1165) on
+        the kernels of include/hg_post.h; each writes one uint8 image through post.save_rgb."""
+        from PIL import Image
+        from . import post
+        if upscale:
+            with Image.open(input_image_name) as im:
+                ref = torch.from_numpy(np.array(im)).to(self.device)
+            out = post.pyramid_upsampling(generated_images, ref, levels=levels, swapping_levels=swapping_levels,
+                                          blending=blending)
+            post.save_rgb(post.float_to_u8_hwc(out[0]), output_name)
+        if recolor:
+            if original_image is None:
+                raise ValueError('recoloringTrainer.evaluate: post_recoloring needs original_image')
+            src = torch.from_numpy(np.ascontiguousarray(original_image, dtype=np.float32)).to(self.device)
+            out, _ = post.color_transfer_mkl(src, generated_images[0].permute(1, 2, 0), quantize=True)
+            post.save_rgb(out, output_name)
 
     def print_log(self):
         if not self.is_main:

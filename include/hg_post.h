@@ -1,0 +1,77 @@
+/* hg_post.h -- C ABI of the full-resolution post-processing kernels (libhistogan_hip.so): the two ways the reference's
+ * `rehistoGAN.py --generate` carries a 256x256 recoloured image back to the photo at its own resolution.
+ *
+ *   hg_resize_axis            MATLAB-style separable resize along one axis (utils/imresize.py:35-96): any tap count,
+ *                             so down-scaling (kernel widened to 4/scale) is the same launch with a longer table
+ *   hg_pyr_down               OpenCV pyrDown (5x5 binomial, every second row / column, BORDER_REFLECT_101)
+ *   hg_pyr_up_add             one level of the Laplacian reconstruction of utils/pyramid_upsampling.py:74-85:
+ *                             pyrUp(prev) + wa*(fineA - pyrUp(coarseA)) + wb*(fineB - pyrUp(coarseB)), the Laplacians
+ *                             formed on the fly from the two Gaussian pyramids, never written
+ *   hg_color_moments          per-image mean and unbiased 3x3 covariance (utils/color_transfer_MKL.py:13-14, 18-19), fp64
+ *   hg_color_affine           (x - m0) T + m1, clipped to [0, 1], optionally quantised to uint8 by truncation (:20-25 and
+ *                             the caller's np.uint8(result*255))
+ *   hg_u8_hwc_to_f32          uint8 HWC -> fp32 planar, x/255 (torchvision ToTensor)
+ *   hg_f32_to_u8_hwc          fp32 planar -> uint8 HWC, clamp(x*255 + 0.5, 0, 255) truncated (torchvision save_image)
+ *
+ * Conventions as in hg_hist.h: return 0 / negative HG_E* / positive hipError_t; device pointers unless stated; fp32;
+ * enqueue on `stream`; never allocate or synchronise; nothing is launched for invalid arguments.  Planar images are
+ * contiguous (C, H, W).  Every result is deterministic: no atomics, fixed reduction order.
+ */
+#ifndef HG_POST_H
+#define HG_POST_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Resize along one axis of a (C, H, W) image with arbitrary element strides (so uint8 HWC is xs = {1, W*C, C}):
+ *   axis 0:  out[c, i, j] = sum_t weights[i*taps + t] * X[c, indices[i*taps + t], j]      out shape (C, out_len, W)
+ *   axis 1:  out[c, i, j] = sum_t weights[j*taps + t] * X[c, i, indices[j*taps + t]]      out shape (C, H, out_len)
+ * X = x as uint8 (x_u8 != 0) or fp32, clamped to [0, 1] first when clamp_in != 0.  Output uint8 (out_u8 != 0) is the
+ * reference's np.around(np.clip(v, 0, 255)) (round half to even), fp32 otherwise.  weights (fp32) and indices (int32,
+ * already folded into [0, in_len) by the host) are device tables of out_len x taps; an index outside [0, in_len) is
+ * clamped to the edge rather than read.  Strides are in elements.  Requires taps >= 1, all sizes >= 1. */
+int hg_resize_axis(const void *x, int32_t x_u8, int64_t xs_c, int64_t xs_h, int64_t xs_w, int32_t clamp_in, void *out,
+                   int32_t out_u8, int64_t os_c, int64_t os_h, int64_t os_w, int32_t C, int32_t H, int32_t W,
+                   int32_t axis, const float *weights, const int32_t *indices, int32_t out_len, int32_t taps,
+                   void *stream);
+
+/* out (C, (H+1)/2, (W+1)/2) = every second row and column of x (C, H, W) filtered with [1 4 6 4 1]^T [1 4 6 4 1] / 256,
+ * source indices outside the image reflected without repeating the edge (BORDER_REFLECT_101: -1 -> 1, H -> H-2). */
+int hg_pyr_down(const float *x, float *out, int32_t C, int32_t H, int32_t W, void *stream);
+
+/* out (C, 2h, 2w) = U(prev) + wa * (fine_a - U(coarse_a)) + wb * (fine_b - U(coarse_b)),   prev, coarse_*: (C, h, w),
+ * fine_*: (C, 2h, 2w).  U = OpenCV pyrUp: zeros inserted, [1 4 6 4 1]/8 per axis, i.e. per axis with source s[0..n-1]
+ *   U[2i] = (s[i-1] + 6 s[i] + s[i+1]) / 8,   U[2i+1] = (s[i] + s[i+1]) / 2,   s[-1] = s[1], s[n] = s[n-1]
+ * (reflect-101 at the left / top, replicate at the right / bottom).  A term whose weight is 0 is skipped and its two
+ * pointers may be NULL; with wa = wb = 0 the call is a plain pyrUp of prev. */
+int hg_pyr_up_add(const float *prev, const float *fine_a, const float *coarse_a, float wa, const float *fine_b,
+                  const float *coarse_b, float wb, float *out, int32_t C, int32_t h, int32_t w, void *stream);
+
+/* moments[0..2] = per-channel mean, moments[3..11] = the 3x3 covariance (row-major, divided by n - 1) of n 3-channel
+ * pixels, pixel p channel c at x[p*pix_stride + c*chan_stride] (HWC: 3, 1; planar: 1, n).  fp64 device output;
+ * accumulated in fp64 in two passes over per-block partials (workspace: hg_color_moments_workspace_bytes(n)).
+ * Requires n >= 2. */
+size_t hg_color_moments_workspace_bytes(int64_t n);
+int hg_color_moments(const float *x, int64_t n, int64_t pix_stride, int64_t chan_stride, double *moments,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* out[p, :] = clip((x[p, :] - m0) T + m1, 0, 1) for n 3-channel pixels addressed as in hg_color_moments; out is HWC
+ * (n, 3), fp32, or uint8 = (uint8)(v * 255) (truncation) when out_u8 != 0.  coef is a HOST array of 15 floats:
+ * m0[3], T[9] (row-major), m1[3]. */
+int hg_color_affine(const float *x, int64_t n, int64_t pix_stride, int64_t chan_stride, const float *coef, void *out,
+                    int32_t out_u8, void *stream);
+
+/* out (C, HW) fp32 = x (HW, C) uint8 / 255. */
+int hg_u8_hwc_to_f32(const uint8_t *x, float *out, int32_t C, int64_t HW, void *stream);
+
+/* out (HW, C) uint8 = (uint8) clamp(x * 255 + 0.5, 0, 255) of x (C, HW) fp32. */
+int hg_f32_to_u8_hwc(const float *x, uint8_t *out, int32_t C, int64_t HW, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* HG_POST_H */
