@@ -34,6 +34,8 @@ class HgHistParams(ctypes.Structure):
         ('projection', ctypes.c_int32),
         ('pre_relu', ctypes.c_int32),
         ('proj_cache', ctypes.c_void_p),
+        ('weight', ctypes.c_void_p),
+        ('weight_stride_b', ctypes.c_int64), ('weight_stride_h', ctypes.c_int64), ('weight_stride_w', ctypes.c_int64),
     ]
 
 

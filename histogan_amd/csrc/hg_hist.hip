@@ -30,7 +30,7 @@
 #include "../../include/hg_hist.h"
 #include <cstdlib>
 
-#define HG_VERSION_NUM 102   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache
+#define HG_VERSION_NUM 103   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight
 
 #ifndef HG_FWD_SCHED_GROUPS
 #define HG_FWD_SCHED_GROUPS 1
@@ -90,7 +90,9 @@ struct DevParams {
   int h, P, method, intensity, green;
   int proj;                 // HG_PROJ_*: 0 RGB-uv (3 planes), 1 rg-chroma, 2 direct (Lab): one plane, run as `green`
   int pre_relu;             // the caller's F.relu in front of the block (histoGAN.py:955) folded into the clamp mask
-  float4 *cache;            // optional [B][npix][2] float4: (a, b, c, Iy), (r, g, b, -) written by the forward, read by the backward
+  float4 *cache;            // optional [B][npix][2] float4: (a, b, c, Iy), (r, g, b, w) written by the forward, read by the backward
+  const float *weight;      // optional per-pixel weight map (hg_hist_params.weight), element strides wsb / wsh / wsw
+  long long wsb, wsh, wsw;
   int npix;
   double lo, hi, step;      // bins: i*step+lo, last == hi  (np.linspace)
   double inv_sigma_d;       // (double)(float)(1/sigma) -- pairs with inv_sigma
@@ -116,32 +118,42 @@ __device__ __forceinline__ bool grad_mask(const DevParams &P, float raw) {
   return (P.pre_relu ? raw > 0.f : raw >= 0.f) && raw <= 1.f;
 }
 
+// Taps of the bilinear resize of histogram pixel (ys, xs): aten upsample_bilinear2d, align_corners=False:
+// src = scale*(dst+0.5)-0.5, clamped at 0 (mul, then sub, each rounded -- as aten's area_pixel_compute_source_index<float>;
+// an fma here moves lambda by up to 1 ulp(src) ~ 1.5e-5 and the interpolated value by ~5e-6)
+struct Taps { int y0, y1, x0, x1; float ly, lx; };
+
+__device__ __forceinline__ Taps bilinear_taps(const DevParams &P, int ys, int xs) {
+  Taps t;
+  float sy = fmaxf(__fsub_rn(__fmul_rn(P.rscale_h, (float)ys + 0.5f), 0.5f), 0.f);
+  float sx = fmaxf(__fsub_rn(__fmul_rn(P.rscale_w, (float)xs + 0.5f), 0.5f), 0.f);
+  t.y0 = min((int)sy, P.H - 1); t.x0 = min((int)sx, P.W - 1);
+  t.ly = clamp01(sy - (float)t.y0); t.lx = clamp01(sx - (float)t.x0);
+  t.y1 = t.y0 + (t.y0 < P.H - 1 ? 1 : 0); t.x1 = t.x0 + (t.x0 < P.W - 1 ? 1 : 0);
+  return t;
+}
+
+// 4 combined weights, fma chain: the form that reproduces aten's CPU kernel bit-for-bit on ~90 % of pixels (the
+// separable forms match ~60 %; differences are 1 ulp of the pixel value)
+__device__ __forceinline__ float bilinear_mix(float ly, float lx, float p00, float p01, float p10, float p11) {
+  const float wx0 = 1.f - lx, wy0 = 1.f - ly;
+  return fmaf(__fmul_rn(ly, lx), p11, fmaf(__fmul_rn(ly, wx0), p10,
+              fmaf(__fmul_rn(wy0, lx), p01, __fmul_rn(__fmul_rn(wy0, wx0), p00))));
+}
+
 // Stage 0 (clamp + resize), RGBuvHistBlock.py:76-99.  n indexes the Hs x Ws sampled grid.
 __device__ __forceinline__ void sample_rgb(const DevParams &P, const float *xb, int n, float &r,
                                            float &g, float &b) {
   const int ys = n / P.Ws, xs = n - ys * P.Ws;
   if (P.mode == HG_RESIZE_BILINEAR) {
-    // aten upsample_bilinear2d, align_corners=False: src = scale*(dst+0.5)-0.5, clamped at 0
-    // (mul, then sub, each rounded -- as aten's area_pixel_compute_source_index<float>; an fma here
-    //  moves lambda by up to 1 ulp(src) ~ 1.5e-5 and the interpolated value by ~5e-6)
-    float sy = fmaxf(__fsub_rn(__fmul_rn(P.rscale_h, (float)ys + 0.5f), 0.5f), 0.f);
-    float sx = fmaxf(__fsub_rn(__fmul_rn(P.rscale_w, (float)xs + 0.5f), 0.5f), 0.f);
-    const int y0 = min((int)sy, P.H - 1), x0 = min((int)sx, P.W - 1);
-    const float ly = clamp01(sy - (float)y0), lx = clamp01(sx - (float)x0);
-    const int y1 = y0 + (y0 < P.H - 1 ? 1 : 0), x1 = x0 + (x0 < P.W - 1 ? 1 : 0);
-    const long long o00 = y0 * P.sh + x0 * P.sw, o01 = y0 * P.sh + x1 * P.sw;
-    const long long o10 = y1 * P.sh + x0 * P.sw, o11 = y1 * P.sh + x1 * P.sw;
+    const Taps t = bilinear_taps(P, ys, xs);
+    const long long o00 = t.y0 * P.sh + t.x0 * P.sw, o01 = t.y0 * P.sh + t.x1 * P.sw;
+    const long long o10 = t.y1 * P.sh + t.x0 * P.sw, o11 = t.y1 * P.sh + t.x1 * P.sw;
     float v[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float *pc = xb + c * P.sc;
-      const float p00 = clamp01(pc[o00]), p01 = clamp01(pc[o01]);
-      const float p10 = clamp01(pc[o10]), p11 = clamp01(pc[o11]);
-      // 4 combined weights, fma chain: the form that reproduces aten's CPU kernel bit-for-bit on
-      // ~90 % of pixels (the separable forms match ~60 %; differences are 1 ulp of the pixel value)
-      const float wx0 = 1.f - lx, wy0 = 1.f - ly;
-      v[c] = fmaf(__fmul_rn(ly, lx), p11, fmaf(__fmul_rn(ly, wx0), p10,
-                  fmaf(__fmul_rn(wy0, lx), p01, __fmul_rn(__fmul_rn(wy0, wx0), p00))));
+      v[c] = bilinear_mix(t.ly, t.lx, clamp01(pc[o00]), clamp01(pc[o01]), clamp01(pc[o10]), clamp01(pc[o11]));
     }
     r = v[0]; g = v[1]; b = v[2];
   } else {
@@ -150,6 +162,23 @@ __device__ __forceinline__ void sample_rgb(const DevParams &P, const float *xb, 
     const long long o = yy * P.sh + xx * P.sw;
     r = clamp01(xb[o]); g = clamp01(xb[o + P.sc]); b = clamp01(xb[o + 2 * P.sc]);
   }
+}
+
+// Stage 0 of the optional weight map (hg_hist_params.weight): w_n of histogram pixel n of image b -- the map clamped to
+// [0, 1] and resized like a colour channel (the taps, the fma form and the gather of sample_rgb).  1 without a map: a
+// wave-uniform branch, and the multiplications by it below are exact, so the unweighted results do not move by a bit.
+__device__ __forceinline__ float sample_weight(const DevParams &P, int b, int n) {
+  if (!P.weight) return 1.f;
+  const float *wb = P.weight + (long long)b * P.wsb;
+  const int ys = n / P.Ws, xs = n - ys * P.Ws;
+  if (P.mode == HG_RESIZE_BILINEAR) {
+    const Taps t = bilinear_taps(P, ys, xs);
+    return bilinear_mix(t.ly, t.lx, clamp01(wb[t.y0 * P.wsh + t.x0 * P.wsw]), clamp01(wb[t.y0 * P.wsh + t.x1 * P.wsw]),
+                        clamp01(wb[t.y1 * P.wsh + t.x0 * P.wsw]), clamp01(wb[t.y1 * P.wsh + t.x1 * P.wsw]));
+  }
+  int yy = ys, xx = xs;
+  if (P.mode == HG_RESIZE_SAMPLING) { yy = P.rows[ys]; xx = P.cols[xs]; }
+  return clamp01(wb[yy * P.wsh + xx * P.wsw]);
 }
 
 // Stage 1 (projection), RGBuvHistBlock.py:104-115: three logs and three chroma differences.
@@ -184,17 +213,24 @@ __device__ __forceinline__ void project(const DevParams &P, float r, float g, fl
 // Per-pixel state of the backward kernels: from the forward's cache (two 16-byte loads) or recomputed (up to 12 taps of
 // the bilinear resize + three fp64 logarithms: ~370 VALU instructions per pixel that the MFMA-bound kernels pay for in
 // matrix-pipe time -- fp32 MFMA and VALU instructions do not overlap on gfx950, tools/ubench/mfma_valu_overlap.hip).
+// wn: the pixel's value of the weight map (1 without one).  iy stays the UNWEIGHTED Iy: the histogram weight is wn * iy and
+// its derivative with respect to the colour wn * x_c / iy.
+// WGT (compile time, k_hist_fwd / k_hist_bwd / k_hist_bwd_planes): false = there is no map and wn is the constant 1, which
+// the compiler folds away -- the unweighted instantiations are the kernels as they were before the map existed (with a
+// run-time NULL test instead, the forward + backward pair at the benchmark shape measured 0.4 % slower: DESIGN.md section 4).
+template <bool WGT>
 __device__ __forceinline__ void pixel_state(const DevParams &P, const float *xb, int b, int n, bool valid, float &r,
-                                            float &g, float &bl, float &a, float &bb, float &c, float &iy) {
+                                            float &g, float &bl, float &a, float &bb, float &c, float &iy, float &wn) {
   if (P.cache) {
     const float4 *cp = P.cache + ((long long)b * P.npix + (valid ? n : 0)) * 2;
     const float4 u = cp[0], v = cp[1];
     a = u.x; bb = u.y; c = u.z; iy = u.w; r = v.x; g = v.y; bl = v.z;
+    wn = WGT ? v.w : 1.f;
     if (!valid) { r = g = bl = 0.f; project(P, r, g, bl, a, bb, c, iy); }
     return;
   }
-  r = g = bl = 0.f;
-  if (valid) sample_rgb(P, xb, n, r, g, bl);
+  r = g = bl = 0.f; wn = 1.f;
+  if (valid) { sample_rgb(P, xb, n, r, g, bl); if (WGT) wn = sample_weight(P, b, n); }
   project(P, r, g, bl, a, bb, c, iy);
 }
 
@@ -238,7 +274,7 @@ __device__ __forceinline__ void lds_wave_sync() {
 // Each wave owns a contiguous run of `chunk` pixels and accumulates a (3 x BLK x BLK) partial
 // histogram block (BLK = 32*T) in 3*T*T MFMA accumulator tiles; the 4 waves are then summed through
 // LDS in fixed order and written as one slab  slabs[b][s][p][h][h]  (real bin order, flips undone).
-template <int T, int METHOD, bool SYM, bool DIAG, bool GREEN, bool SHARE = false>
+template <int T, int METHOD, bool SYM, bool DIAG, bool GREEN, bool SHARE = false, bool WGT = false>
 __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const float *__restrict__ x,
                                                      float *__restrict__ slabs, double *__restrict__ slab_tot,
                                                      const int chunk) {
@@ -395,21 +431,24 @@ __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const fl
   // this kernel's VALU work -- into a pre-pass kernel of its own: k_hist_fwd got 2 % faster (455 -> 446 us at configs[1]),
   // the pre-pass cost 23 us.  The other wave of the SIMD evidently hides most of it here; it stays in the kernel.)
   float r_ = 0.f, g_ = 0.f, b_ = 0.f;
-  if (start + lane < end) sample_rgb(P, xb, (int)start + lane, r_, g_, b_);
+  [[maybe_unused]] float w_ = 1.f;                            // WGT: the weight map's value
+  if (start + lane < end) { sample_rgb(P, xb, (int)start + lane, r_, g_, b_); if (WGT) w_ = sample_weight(P, b, (int)start + lane); }
   HG_PROBE_T(pt1);
   for (int base = (int)start; base < end; base += 64) {
     HG_PROBE_T(pb0);
     float a, bb, c, iy;
     project(P, r_, g_, b_, a, bb, c, iy);
     const bool valid = base + lane < end;
-    stage[wave * kFwdStage + lane] = valid ? make_float4(a, bb, c, iy) : make_float4(0.f, 0.f, 0.f, 0.f);
+    // the one place the weight map enters: the A-side weight of the contraction is w_n * Iy (one multiply per pixel, outside
+    // the K loop); the cache keeps Iy and w_n apart for the backward
+    stage[wave * kFwdStage + lane] = valid ? make_float4(a, bb, c, WGT ? __fmul_rn(w_, iy) : iy) : make_float4(0.f, 0.f, 0.f, 0.f);
     if (P.cache && valid && blockIdx.y == 0) {          // one writer per pixel (the bin-block replicas skip it)
       float4 *cp = P.cache + ((long long)b * P.npix + base + lane) * 2;
       cp[0] = make_float4(a, bb, c, iy);
-      cp[1] = make_float4(r_, g_, b_, 0.f);
+      cp[1] = make_float4(r_, g_, b_, WGT ? w_ : 0.f);
     }
     // prefetch the next 64 pixels while this batch is in the MFMA loop
-    if (base + 64 + lane < end) sample_rgb(P, xb, base + 64 + lane, r_, g_, b_);
+    if (base + 64 + lane < end) { sample_rgb(P, xb, base + 64 + lane, r_, g_, b_); if (WGT) w_ = sample_weight(P, b, base + 64 + lane); }
     lds_wave_sync();
     // K steps of this batch, rounded up to an even count: entries past the batch hold zero weights (written above), so
     // the padding step adds exact zeros and the loop body needs no branch between its two steps
@@ -594,7 +633,7 @@ __device__ __forceinline__ constexpr int beta0(int s) { return (s & 3) + 8 * ((s
 // as D[bin][pixel] MFMA tiles (A = Ghat from LDS, B = kernel values generated in registers), then
 //   dL/da = Iy * sum_i k'(a-b_i) Wa[i]   (same for b, c),   dL/dIy = 1/2 sum_i (ka Wa + kb Wb + kc Wc)[i]
 //   dL_R = da+db, dL_G = -da+dc, dL_B = -db-dc,   dx_c = dL_c/(x_c+1e-6) + dIy x_c/Iy   
-template <int T, int METHOD, bool GREEN, bool SHARE = false>
+template <int T, int METHOD, bool GREEN, bool SHARE = false, bool WGT = false>
 __global__ __launch_bounds__(256, HG_BWD_WAVES) void k_hist_bwd(const DevParams P, const float *__restrict__ x,
                                                                 const float *__restrict__ gout,
                                                                 const float *__restrict__ hist,
@@ -645,8 +684,8 @@ __global__ __launch_bounds__(256, HG_BWD_WAVES) void k_hist_bwd(const DevParams 
     const int n = (int)n0 + q;
     const bool valid = n < P.npix;
     HG_PROBE_T(pr0);
-    float r_, g_, b_, a, bb, c, iy;
-    pixel_state(P, xb, b, n, valid, r_, g_, b_, a, bb, c, iy);
+    float r_, g_, b_, a, bb, c, iy, wn;
+    pixel_state<WGT>(P, xb, b, n, valid, r_, g_, b_, a, bb, c, iy, wn);
 
     // t_s = (u - lo - 4*half*step)/sigma - beta0(s)*step/sigma, double-single
     float th[3], tl[3];
@@ -988,8 +1027,10 @@ __global__ __launch_bounds__(256, HG_BWD_WAVES) void k_hist_bwd(const DevParams 
     for (int v = 0; v < 3; ++v) gsum[v] += __shfl_xor(gsum[v], 32, 64);
     isum += __shfl_xor(isum, 32, 64);
 
-    const float da = iy * P.dk_scale * gsum[0], db = iy * P.dk_scale * gsum[1], dc = iy * P.dk_scale * gsum[2];
-    const float dIy = P.intensity ? 0.5f * isum : 0.f;
+    // weight map: the pixel entered with w_n * Iy -- that product scales the coordinate gradients, and dL/dIy = w_n dL/d(w_n Iy)
+    const float wiy = __fmul_rn(wn, iy);
+    const float da = wiy * P.dk_scale * gsum[0], db = wiy * P.dk_scale * gsum[1], dc = wiy * P.dk_scale * gsum[2];
+    const float dIy = P.intensity ? __fmul_rn(0.5f * isum, wn) : 0.f;
     if (valid && half == 0) store_pixel_grad(P, xb, b, n, r_, g_, b_, iy, da, db, dc, dIy, gdst);
     if (valid && half == 1 && P.mode == HG_RESIZE_NONE) {
       for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
@@ -1024,7 +1065,7 @@ __global__ __launch_bounds__(256, HG_BWD_WAVES) void k_hist_bwd(const DevParams 
 template <int RT>
 struct POps { float Au[RT], Av[RT]; float ku, kv; };
 
-template <int RT, int METHOD>
+template <int RT, int METHOD, bool WGT = false>
 __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, const float *__restrict__ x,
                                                             const float *__restrict__ gout,
                                                             const float *__restrict__ hist,
@@ -1061,8 +1102,8 @@ __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, c
       if (n0 >= P.npix) break;
       const int n = (int)n0 + q;
       const bool valid = n < P.npix;
-      float r_, g_, b_, a, bb, c, iy;
-      pixel_state(P, xb, b, n, valid, r_, g_, b_, a, bb, c, iy);
+      float r_, g_, b_, a, bb, c, iy, wn;
+      pixel_state<WGT>(P, xb, b, n, valid, r_, g_, b_, a, bb, c, iy, wn);
       const float u = (p == 0) ? a : (p == 1 ? -a : -bb), v = (p == 0) ? bb : (p == 1 ? c : -c);
 
       // t_s = (u - lo - 4*half*step)/sigma - beta0(s)*step/sigma, double-single (beta0(s) < 128: beta0*ds_hi exact)
@@ -1166,7 +1207,8 @@ __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, c
       gu += __shfl_xor(gu, 32, 64);
       gv += __shfl_xor(gv, 32, 64);
       isum += __shfl_xor(isum, 32, 64);
-      const float du = iy * P.dk_scale * gu, dv = iy * P.dk_scale * gv;   // dL/du, dL/dv of this plane
+      const float wiy = __fmul_rn(wn, iy);                                  // the pixel's histogram weight (weight map x Iy)
+      const float du = wiy * P.dk_scale * gu, dv = wiy * P.dk_scale * gv;   // dL/du, dL/dv of this plane
 
       if (valid && half == 0) {
         float da = 0.f, db = 0.f, dc = 0.f, dIy = 0.f;
@@ -1179,9 +1221,9 @@ __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, c
           pb[n] = da; pb[P.npix + n] = db; pb[2LL * P.npix + n] = dc; pb[3LL * P.npix + n] = dIy;
         } else if (P.proj != HG_PROJ_RGBUV) {
           // one plane binned as (u, v) = (-a, c): dL/du = -da, dL/dv = dc
-          store_pixel_grad_proj(P, xb, b, n, r_, g_, b_, iy, -da, dc, P.intensity ? dIy : 0.f, gdst);
+          store_pixel_grad_proj(P, xb, b, n, r_, g_, b_, iy, -da, dc, P.intensity ? __fmul_rn(dIy, wn) : 0.f, gdst);
         } else {
-          store_pixel_grad(P, xb, b, n, r_, g_, b_, iy, da, db, dc, P.intensity ? dIy : 0.f, gdst);
+          store_pixel_grad(P, xb, b, n, r_, g_, b_, iy, da, db, dc, P.intensity ? __fmul_rn(dIy, wn) : 0.f, gdst);
         }
       }
       if (valid && half == 1 && pi + 1 == nplanes && P.mode == HG_RESIZE_NONE) {
@@ -1239,8 +1281,8 @@ __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, cons
   const int n = blockIdx.x * 64 + lane;
   const bool valid = n < P.npix;
   const float *xb = x + (long long)b * P.sb;
-  float r_ = 0.f, g_ = 0.f, b_ = 0.f;
-  if (valid) sample_rgb(P, xb, n, r_, g_, b_);
+  float r_ = 0.f, g_ = 0.f, b_ = 0.f, wn = 1.f;
+  if (valid) { sample_rgb(P, xb, n, r_, g_, b_); wn = sample_weight(P, b, n); }
   float a, bb, c, iy;
   project(P, r_, g_, b_, a, bb, c, iy);
   // plane p: (u, v) = (su*U, sv*V) with U,V in {a,b,c}  (RGBuvHistBlock.py:112-115,150-153,190-193)
@@ -1270,11 +1312,12 @@ __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, cons
     }
   }
   // u0 = a, v0 = b, u1 = -a, v1 = c, u2 = -b, v2 = -c
-  const float da = iy * (gu[0] - gu[1]), db = iy * (gv[0] - gu[2]), dc = iy * (gv[1] - gv[2]);
-  const float dIy = P.intensity ? isum : 0.f;
+  const float wiy = __fmul_rn(wn, iy);             // weight map x Iy: what the pixel entered the histogram with
+  const float da = wiy * (gu[0] - gu[1]), db = wiy * (gv[0] - gu[2]), dc = wiy * (gv[1] - gv[2]);
+  const float dIy = P.intensity ? __fmul_rn(isum, wn) : 0.f;
   if (valid) {
     if (P.proj != HG_PROJ_RGBUV)   // one plane, binned as (u, v) = (-a, c): gu[1] = dL/du, gv[1] = dL/dv (before the weight)
-      store_pixel_grad_proj(P, xb, b, n, r_, g_, b_, iy, iy * gu[1], iy * gv[1], dIy, gdst);
+      store_pixel_grad_proj(P, xb, b, n, r_, g_, b_, iy, wiy * gu[1], wiy * gv[1], dIy, gdst);
     else
       store_pixel_grad(P, xb, b, n, r_, g_, b_, iy, da, db, dc, dIy, gdst);
     if (P.mode == HG_RESIZE_NONE)
@@ -1524,6 +1567,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevPar
       float r, g, bl, a, bb, c, iy;
       sample_rgb(P, xb, n, r, g, bl);
       project(P, r, g, bl, a, bb, c, iy);
+      iy = __fmul_rn(sample_weight(P, b, n), iy);       // weight map, before the fixed-point conversion
       const unsigned long long q = (unsigned long long)((double)iy * kThrScale + 0.5);
       if (P.green) {
         thr_scatter_plane(P, bins, -a, c, inv_step, w, single, q);
@@ -1548,6 +1592,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevPar
         float r, g, bl, a, bb, c, iy;
         sample_rgb(P, xb, n, r, g, bl);
         project(P, r, g, bl, a, bb, c, iy);
+        iy = __fmul_rn(sample_weight(P, b, n), iy);
         const float u = p == 0 ? a : (p == 1 ? -a : -bb), v = p == 0 ? bb : (p == 1 ? c : -c);
         thr_scatter_plane(P, bins, u, v, inv_step, w, single, (unsigned long long)((double)iy * kThrScale + 0.5));
       }
@@ -1598,6 +1643,7 @@ __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const f
       }
     }
   }
+  dIy = __fmul_rn(dIy, sample_weight(P, b, n));       // weight map: dL/dIy = w_n dL/d(w_n Iy)
   if (P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj(P, xb, b, n, r, g, bl, iy, 0.f, 0.f, dIy, gdst);
   else store_pixel_grad(P, xb, b, n, r, g, bl, iy, 0.f, 0.f, 0.f, dIy, gdst);
   if (P.mode == HG_RESIZE_NONE)
@@ -1646,44 +1692,50 @@ __global__ __launch_bounds__(1024) void k_thr_fwd_lean(const DevParams P, const 
   const ThrFast F = make_thr_fast(P);
   // the first tile's loads are in flight while the grids are cleared
   float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f), g4 = r4, b4 = r4;
+  // weight map (DIRECT: contiguous rows like the image, 16-byte loads; 1 without a map -- a workgroup-uniform branch)
+  const float *wb = P.weight ? P.weight + (long long)b * P.wsb : nullptr;
+  float4 w4 = make_float4(1.f, 1.f, 1.f, 1.f);
   int n = n0 + 4 * threadIdx.x;
   if (DIRECT && n < n1) {
     r4 = *reinterpret_cast<const float4 *>(xb + n);
     g4 = *reinterpret_cast<const float4 *>(xb + P.sc + n);
     b4 = *reinterpret_cast<const float4 *>(xb + 2 * P.sc + n);
+    if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n);
   }
   {
     ulonglong2 *b2 = reinterpret_cast<ulonglong2 *>(bins);
     for (int e = threadIdx.x; e < (3 * hh + 1) / 2; e += 1024) b2[e] = make_ulonglong2(0ull, 0ull);  // LDS is sized in 16-byte units
   }
   __syncthreads();
-  auto pixel = [&](float r, float g, float bl) __attribute__((always_inline)) {
+  auto pixel = [&](float r, float g, float bl, float wn) __attribute__((always_inline)) {
     int idx[6];
     float iy;
     thr_lean_classify<SYM>(P, F, r, g, bl, inv_step, exact_only, idx, iy);
-    const unsigned long long q = iy_fixed(iy);
+    // the weight goes in BEFORE the fixed-point conversion: the 64-bit integer sums stay order-independent
+    const unsigned long long q = iy_fixed(__fmul_rn(wn, iy));
     if ((idx[0] | idx[1]) >= 0) atomicAdd(&bins[idx[0] * h + idx[1]], q);
     if ((idx[2] | idx[3]) >= 0) atomicAdd(&bins[hh + idx[2] * h + idx[3]], q);
     if ((idx[4] | idx[5]) >= 0) atomicAdd(&bins[2 * hh + idx[4] * h + idx[5]], q);
   };
   if constexpr (DIRECT) {
     for (; n < n1; n += 4096) {
-      const float4 rc = r4, gc = g4, bc = b4;
+      const float4 rc = r4, gc = g4, bc = b4, wc = w4;
       if (n + 4096 < n1) {                              // next tile's loads before this tile's arithmetic
         r4 = *reinterpret_cast<const float4 *>(xb + n + 4096);
         g4 = *reinterpret_cast<const float4 *>(xb + P.sc + n + 4096);
         b4 = *reinterpret_cast<const float4 *>(xb + 2 * P.sc + n + 4096);
+        if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n + 4096);
       }
-      pixel(clamp01(rc.x), clamp01(gc.x), clamp01(bc.x));
-      pixel(clamp01(rc.y), clamp01(gc.y), clamp01(bc.y));
-      pixel(clamp01(rc.z), clamp01(gc.z), clamp01(bc.z));
-      pixel(clamp01(rc.w), clamp01(gc.w), clamp01(bc.w));
+      pixel(clamp01(rc.x), clamp01(gc.x), clamp01(bc.x), clamp01(wc.x));
+      pixel(clamp01(rc.y), clamp01(gc.y), clamp01(bc.y), clamp01(wc.y));
+      pixel(clamp01(rc.z), clamp01(gc.z), clamp01(bc.z), clamp01(wc.z));
+      pixel(clamp01(rc.w), clamp01(gc.w), clamp01(bc.w), clamp01(wc.w));
     }
   } else {
     for (int m = n0 + threadIdx.x; m < n1; m += 1024) {
       float r, g, bl;
       sample_rgb(P, xb, m, r, g, bl);
-      pixel(r, g, bl);
+      pixel(r, g, bl, sample_weight(P, b, m));
     }
   }
   __syncthreads();
@@ -1744,11 +1796,14 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
   const int n0 = sl * per_block, n1 = min(P.npix, n0 + per_block);
   // the first tile's loads are in flight during the <G, out> prologue
   float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f), g4 = r4, b4 = r4;
+  const float *wb = P.weight ? P.weight + (long long)b * P.wsb : nullptr;   // weight map, as in k_thr_fwd_lean
+  float4 w4 = make_float4(1.f, 1.f, 1.f, 1.f);
   int n = n0 + 4 * threadIdx.x;
   if (DIRECT && n < n1) {
     r4 = *reinterpret_cast<const float4 *>(xb + n);
     g4 = *reinterpret_cast<const float4 *>(xb + P.sc + n);
     b4 = *reinterpret_cast<const float4 *>(xb + 2 * P.sc + n);
+    if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n);
   }
   const bool al16 = (((uintptr_t)g | (uintptr_t)o) & 15) == 0;
   // <G, out> with every load in flight at once: a thread owns groups of four consecutive bins (16-byte loads), keeps
@@ -1791,7 +1846,7 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
   __syncthreads();
   const double inv_step = 1.0 / P.step;
   const ThrFast F = make_thr_fast(P);
-  auto pixel = [&](float r, float gg, float bl, float &dr, float &dg, float &db) __attribute__((always_inline)) {
+  auto pixel = [&](float r, float gg, float bl, float wn, float &dr, float &dg, float &db) __attribute__((always_inline)) {
     int idx[6];
     float iy;
     thr_lean_classify<SYM>(P, F, r, gg, bl, inv_step, exact_only, idx, iy);
@@ -1799,23 +1854,24 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
     if ((idx[0] | idx[1]) >= 0) dIy += gh[idx[0] * h + idx[1]];
     if ((idx[2] | idx[3]) >= 0) dIy += gh[hh + idx[2] * h + idx[3]];
     if ((idx[4] | idx[5]) >= 0) dIy += gh[2 * hh + idx[4] * h + idx[5]];
-    const float wgt = dIy / iy;
+    const float wgt = __fmul_rn(dIy, wn) / iy;           // weight map: dL/dIy = w_n dL/d(w_n Iy)
     dr = wgt * r; dg = wgt * gg; db = wgt * bl;
   };
   if constexpr (DIRECT) {
     float *gb = gdst + ((long long)b * P.C) * P.npix;
     for (; n < n1; n += 4096) {
-      const float4 rc = r4, gc = g4, bc = b4;
+      const float4 rc = r4, gc = g4, bc = b4, wc = w4;
       if (n + 4096 < n1) {                              // next tile's loads before this tile's arithmetic
         r4 = *reinterpret_cast<const float4 *>(xb + n + 4096);
         g4 = *reinterpret_cast<const float4 *>(xb + P.sc + n + 4096);
         b4 = *reinterpret_cast<const float4 *>(xb + 2 * P.sc + n + 4096);
+        if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n + 4096);
       }
       float4 or4, og4, ob4;
-      pixel(clamp01(rc.x), clamp01(gc.x), clamp01(bc.x), or4.x, og4.x, ob4.x);
-      pixel(clamp01(rc.y), clamp01(gc.y), clamp01(bc.y), or4.y, og4.y, ob4.y);
-      pixel(clamp01(rc.z), clamp01(gc.z), clamp01(bc.z), or4.z, og4.z, ob4.z);
-      pixel(clamp01(rc.w), clamp01(gc.w), clamp01(bc.w), or4.w, og4.w, ob4.w);
+      pixel(clamp01(rc.x), clamp01(gc.x), clamp01(bc.x), clamp01(wc.x), or4.x, og4.x, ob4.x);
+      pixel(clamp01(rc.y), clamp01(gc.y), clamp01(bc.y), clamp01(wc.y), or4.y, og4.y, ob4.y);
+      pixel(clamp01(rc.z), clamp01(gc.z), clamp01(bc.z), clamp01(wc.z), or4.z, og4.z, ob4.z);
+      pixel(clamp01(rc.w), clamp01(gc.w), clamp01(bc.w), clamp01(wc.w), or4.w, og4.w, ob4.w);
       // clamp mask of RGBuvHistBlock.py:76, decided on the raw value
       auto m = [&](float raw, float v) { return grad_mask(P, raw) ? v : 0.f; };
       or4 = make_float4(m(rc.x, or4.x), m(rc.y, or4.y), m(rc.z, or4.z), m(rc.w, or4.w));
@@ -1831,7 +1887,7 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
     for (int m = n0 + threadIdx.x; m < n1; m += 1024) {
       float r, gg, bl, dr, dg, db;
       sample_rgb(P, xb, m, r, gg, bl);
-      pixel(r, gg, bl, dr, dg, db);
+      pixel(r, gg, bl, sample_weight(P, b, m), dr, dg, db);
       store_rgb_grad(P, xb, b, m, dr, dg, db, gdst);
       if (P.mode == HG_RESIZE_NONE)
         for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + m] = 0.f;
@@ -1894,6 +1950,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_rbf_fwd(const DevPar
       float r, g, bl, a, bb, c, iy;
       sample_rgb(P, xb, n, r, g, bl);
       project(P, r, g, bl, a, bb, c, iy);
+      iy = __fmul_rn(sample_weight(P, b, n), iy);       // weight map
       if (P.green) {
         scatter(bins, -a, c, iy);
       } else {
@@ -1917,6 +1974,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_rbf_fwd(const DevPar
         float r, g, bl, a, bb, c, iy;
         sample_rgb(P, xb, n, r, g, bl);
         project(P, r, g, bl, a, bb, c, iy);
+        iy = __fmul_rn(sample_weight(P, b, n), iy);
         scatter(bins, p == 0 ? a : (p == 1 ? -a : -bb), p == 0 ? bb : (p == 1 ? c : -c), iy);
       }
       __syncthreads();
@@ -1980,9 +2038,10 @@ __global__ __launch_bounds__(256) void k_hist_rbf_bwd(const DevParams P, const f
 #pragma unroll
     for (int dj = 0; dj < 2 * HG_RBF_RMAX + 1; ++dj) gv[p] = fmaf(dkv[dj], Sx[dj], gv[p]);
   }
-  const float da = iy * (gu[0] - gu[1]), db = iy * (gv[0] - gu[2]), dc = iy * (gv[1] - gv[2]);
-  const float dIy = P.intensity ? isum : 0.f;
-  if (P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj(P, xb, b, n, r, g, bl, iy, iy * gu[1], iy * gv[1], dIy, gdst);
+  const float wn = sample_weight(P, b, n), wiy = __fmul_rn(wn, iy);   // weight map x Iy: the pixel's histogram weight
+  const float da = wiy * (gu[0] - gu[1]), db = wiy * (gv[0] - gu[2]), dc = wiy * (gv[1] - gv[2]);
+  const float dIy = P.intensity ? __fmul_rn(isum, wn) : 0.f;
+  if (P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj(P, xb, b, n, r, g, bl, iy, wiy * gu[1], wiy * gv[1], dIy, gdst);
   else store_pixel_grad(P, xb, b, n, r, g, bl, iy, da, db, dc, dIy, gdst);
   if (P.mode == HG_RESIZE_NONE)
     for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
@@ -2074,6 +2133,7 @@ int validate(const hg_hist_params *p) {
   if (p->struct_size != sizeof(hg_hist_params)) return HG_EINVAL;   // stale header / unzeroed struct (include/hg_hist.h)
   if (p->pre_relu != 0 && p->pre_relu != 1) return HG_EINVAL;
   if (p->proj_cache && ((uintptr_t)p->proj_cache & 15)) return HG_EINVAL;
+  if (p->weight && ((uintptr_t)p->weight & 3)) return HG_EINVAL;     // NULL: no map, the strides are not looked at
   if (p->B <= 0 || p->C < 3 || p->H <= 0 || p->W <= 0 || p->Hs <= 0 || p->Ws <= 0 || p->h <= 0) return HG_EINVAL;
   if (p->method < 0 || p->method > 2) return HG_EMETHOD;
   if (p->resize_mode < 0 || p->resize_mode > 2) return HG_ERESIZE;
@@ -2123,6 +2183,9 @@ inline bool thr_lean(const hg_hist_params *p) {
 // no resize, contiguous planes, 16-byte aligned rows of four pixels: the float4 variant
 inline bool thr_direct(const hg_hist_params *p, const float *x, const float *gx) {
   const long long npix = (long long)p->H * p->W;
+  // a weight map takes the 16-byte loads too: rows contiguous like the image's (a batch stride of 0 is fine)
+  if (p->weight && !(p->weight_stride_w == 1 && p->weight_stride_h == p->W && (p->weight_stride_b & 3) == 0 &&
+                     ((uintptr_t)p->weight & 15) == 0)) return false;
   return p->resize_mode == HG_RESIZE_NONE && p->stride_w == 1 && p->stride_h == p->W && (npix & 3) == 0 &&
          (p->stride_c & 3) == 0 && (p->stride_b & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)gx & 15) == 0;
 }
@@ -2197,6 +2260,8 @@ DevParams make_dev(const hg_hist_params *p) {
   d.proj = p->projection;
   d.pre_relu = p->pre_relu ? 1 : 0;
   d.cache = (float4 *)p->proj_cache;
+  d.weight = p->weight;
+  d.wsb = p->weight ? p->weight_stride_b : 0; d.wsh = p->weight ? p->weight_stride_h : 0; d.wsw = p->weight ? p->weight_stride_w : 0;
   d.h = p->h; d.P = (p->green_only || p->projection) ? 1 : 3; d.method = p->method;
   d.intensity = p->intensity_scale ? 1 : 0; d.green = (p->green_only || p->projection) ? 1 : 0;
   d.npix = p->Hs * p->Ws;
@@ -2243,6 +2308,21 @@ bool bwd_share_rcp_ok(const DevParams &d) {      // the same product-of-four-den
   return den * den * den * den < 1e30;
 }
 
+// the instantiation with or without the weight map (pixel_state: WGT)
+template <int T, int METHOD, bool SYM, bool DIAG, bool GREEN, bool SHARE>
+void launch_fwd_w(const dim3 grid, const dim3 block, size_t lds, hipStream_t st, const DevParams &d, const float *x,
+                  float *slabs, double *slab_tot, int chunk) {
+  if (d.weight) hipLaunchKernelGGL((k_hist_fwd<T, METHOD, SYM, DIAG, GREEN, SHARE, true>), grid, block, lds, st, d, x, slabs, slab_tot, chunk);
+  else hipLaunchKernelGGL((k_hist_fwd<T, METHOD, SYM, DIAG, GREEN, SHARE, false>), grid, block, lds, st, d, x, slabs, slab_tot, chunk);
+}
+
+template <int T, int METHOD, bool GREEN, bool SHARE>
+void launch_bwd_w(const dim3 grid, const dim3 block, size_t lds, hipStream_t st, const DevParams &d, const float *x,
+                  const float *gout, const float *hist, const float *sums, float *gdst, int rounds) {
+  if (d.weight) hipLaunchKernelGGL((k_hist_bwd<T, METHOD, GREEN, SHARE, true>), grid, block, lds, st, d, x, gout, hist, sums, gdst, rounds);
+  else hipLaunchKernelGGL((k_hist_bwd<T, METHOD, GREEN, SHARE, false>), grid, block, lds, st, d, x, gout, hist, sums, gdst, rounds);
+}
+
 template <int T, int METHOD, bool GREEN>
 int launch_fwd_tmg(const DevParams &d, const Plan &pl, bool sym, const float *x, float *slabs, double *slab_tot,
                    hipStream_t st) {
@@ -2251,14 +2331,14 @@ int launch_fwd_tmg(const DevParams &d, const Plan &pl, bool sym, const float *x,
   const bool diag = pl.nbd == 1;
   if constexpr (T == 2 && METHOD == HG_METHOD_INVERSE_QUADRATIC && !GREEN) {
     if (sym && diag && fwd_share_rcp_ok(d)) {
-      hipLaunchKernelGGL((k_hist_fwd<T, METHOD, true, true, GREEN, true>), grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
+      launch_fwd_w<T, METHOD, true, true, GREEN, true>(grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
       HG_LAUNCH_CHECK();
       return HG_OK;
     }
   }
-  if (sym && diag) hipLaunchKernelGGL((k_hist_fwd<T, METHOD, true, true, GREEN>), grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
-  else if (sym) hipLaunchKernelGGL((k_hist_fwd<T, METHOD, true, false, GREEN>), grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
-  else hipLaunchKernelGGL((k_hist_fwd<T, METHOD, false, false, GREEN>), grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
+  if (sym && diag) launch_fwd_w<T, METHOD, true, true, GREEN, false>(grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
+  else if (sym) launch_fwd_w<T, METHOD, true, false, GREEN, false>(grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
+  else launch_fwd_w<T, METHOD, false, false, GREEN, false>(grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
   HG_LAUNCH_CHECK();
   return HG_OK;
 }
@@ -2287,13 +2367,13 @@ int launch_bwd_tm(const DevParams &d, const Plan &pl, const float *x, const floa
   const size_t lds = (size_t)3 * pl.BLK * (pl.BLK + 1) * sizeof(float);
   if constexpr (METHOD == HG_METHOD_INVERSE_QUADRATIC) {
     if (!d.green && bwd_share_rcp_ok(d)) {
-      hipLaunchKernelGGL((k_hist_bwd<T, METHOD, false, true>), grid, block, lds, st, d, x, gout, hist, sums, gdst, pl.rounds);
+      launch_bwd_w<T, METHOD, false, true>(grid, block, lds, st, d, x, gout, hist, sums, gdst, pl.rounds);
       HG_LAUNCH_CHECK();
       return HG_OK;
     }
   }
-  if (d.green) hipLaunchKernelGGL((k_hist_bwd<T, METHOD, true>), grid, block, lds, st, d, x, gout, hist, sums, gdst, pl.rounds);
-  else hipLaunchKernelGGL((k_hist_bwd<T, METHOD, false>), grid, block, lds, st, d, x, gout, hist, sums, gdst, pl.rounds);
+  if (d.green) launch_bwd_w<T, METHOD, true, false>(grid, block, lds, st, d, x, gout, hist, sums, gdst, pl.rounds);
+  else launch_bwd_w<T, METHOD, false, false>(grid, block, lds, st, d, x, gout, hist, sums, gdst, pl.rounds);
   HG_LAUNCH_CHECK();
   return HG_OK;
 }
@@ -2308,23 +2388,30 @@ int launch_bwd_t(const DevParams &d, const Plan &pl, const float *x, const float
   }
 }
 
-template <int RT>
-int launch_bwd_planes_rt(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
-                         const float *sums, float *part, float *gdst, hipStream_t st) {
+template <int RT, bool WGT>
+int launch_bwd_planes_rtw(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
+                          const float *sums, float *part, float *gdst, hipStream_t st) {
   const dim3 grid(pl.S_bwd, d.B), block(256);
   const size_t lds = (size_t)(32 * RT) * (32 * RT + 1) * sizeof(float);
-  const void *kern = (d.method == HG_METHOD_RBF) ? (const void *)k_hist_bwd_planes<RT, HG_METHOD_RBF>
-                                                 : (const void *)k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC>;
+  const void *kern = (d.method == HG_METHOD_RBF) ? (const void *)k_hist_bwd_planes<RT, HG_METHOD_RBF, WGT>
+                                                 : (const void *)k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC, WGT>;
   if (lds > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
   if (d.method == HG_METHOD_RBF)
-    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_RBF>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
+    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_RBF, WGT>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
   else
-    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
+    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC, WGT>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
   HG_LAUNCH_CHECK();
   return HG_OK;
+}
+
+template <int RT>
+int launch_bwd_planes_rt(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
+                         const float *sums, float *part, float *gdst, hipStream_t st) {
+  return d.weight ? launch_bwd_planes_rtw<RT, true>(d, pl, x, gout, hist, sums, part, gdst, st)
+                  : launch_bwd_planes_rtw<RT, false>(d, pl, x, gout, hist, sums, part, gdst, st);
 }
 
 int launch_bwd_planes(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,

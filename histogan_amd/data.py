@@ -74,8 +74,13 @@ def _load_rgb(path, size=None, flip=False, rgba=False, crop_seed=None):
 class FolderData:
     def __init__(self, folder, hist_block, batch_size, image_size, device, transparent=False, seed=0, test=False,
                  hist_sampling=True, workers=8, prefetch=3, cache_hists=True, max_cached=200000, hflip=False,
-                 aug_prob=0.0, max_cache_bytes=2 << 30):
+                 aug_prob=0.0, max_cache_bytes=2 << 30, hist_alpha_weight=False):
         self.rgba = bool(transparent)                            # 4-channel items; the histogram uses channels 0..2
+        # opt-in: the target histograms weigh every pixel by its alpha (channel 3), so the colour stored under transparent
+        # pixels does not count; default: alpha is ignored, as in the reference
+        if hist_alpha_weight and not transparent:
+            raise ValueError('hist_alpha_weight=True needs transparent=True (there is no alpha channel to weigh by)')
+        self.alpha_weight = bool(hist_alpha_weight)
         self.paths = sorted(p for ext in EXTS for p in Path(f'{folder}').glob(f'**/*.{ext}'))
         if not self.paths:
             raise FileNotFoundError(f'no {EXTS} images under {folder}')
@@ -122,7 +127,7 @@ class FolderData:
                 fut = plan['full'].get(i)
                 x = (fut.result() if fut is not None else _load_rgb(self.paths[i], None, False, self.rgba)).unsqueeze(0).to(self.device)
                 with torch.no_grad():
-                    h = self.hist_block(x)[0]
+                    h = (self.hist_block(x, weight=x[:, 3]) if self.alpha_weight else self.hist_block(x))[0]
                 self.misses += 1
                 nbytes = h.numel() * h.element_size()
                 if self.cache is not None and len(self.cache) < self.max_cached and \

@@ -47,7 +47,24 @@ class HistConfig:
         self.lo, self.hi = float(hb[0]), float(hb[1])
 
 
-def _make_params(x, cfg, pre_relu=False):
+def check_weight(x, weight):
+    """Validate a per-pixel weight map for x (B, C, H, W) and return it as a detached fp32 (B, H, W) view (no copy for
+    fp32 input: the kernels take any strides).  (B, 1, H, W) or (B, H, W); it is a constant of the histogram."""
+    if not torch.is_tensor(weight):
+        raise ValueError(f'weight must be a tensor, got {type(weight).__name__}')
+    if weight.requires_grad:
+        raise ValueError('weight requires grad, but the histogram produces no gradient for its weight map '
+                         '(pass weight.detach())')
+    B, _, H, W = x.shape
+    if tuple(weight.shape) == (B, 1, H, W):
+        weight = weight[:, 0]
+    elif tuple(weight.shape) != (B, H, W):
+        raise ValueError(f'weight must have shape {(B, 1, H, W)} or {(B, H, W)} for an input of shape '
+                         f'{tuple(x.shape)}, got {tuple(weight.shape)}')
+    return weight if weight.dtype == torch.float32 else weight.float()
+
+
+def _make_params(x, cfg, pre_relu=False, weight=None):
     if x.dim() != 4 or x.shape[1] < 3:
         raise ValueError(f'expected (B, C>=3, H, W) input, got {tuple(x.shape)}')
     if cfg.method not in _lib.HG_METHOD:
@@ -78,6 +95,9 @@ def _make_params(x, cfg, pre_relu=False):
     p.intensity_scale, p.green_only = int(cfg.intensity_scale), int(cfg.green_only)
     p.projection = _lib.HG_PROJ[cfg.projection]
     p.pre_relu = int(bool(pre_relu))
+    if weight is not None:                      # (B, H, W) fp32 on x's device (check_weight), any strides
+        p.weight = weight.data_ptr()
+        p.weight_stride_b, p.weight_stride_h, p.weight_stride_w = weight.stride()
     return p, keep
 
 
@@ -99,13 +119,15 @@ def _require_gpu(x, what):
 
 class RGBuvHistFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, cfg, pre_relu=False):
+    def forward(ctx, x, cfg, pre_relu=False, weight=None):
+        # weight: None or a map already validated by rgbuv_hist (check_weight): fp32 (B, H, W) on x's device, no grad
         _require_gpu(x, 'RGBuvHistFunction')
         x = x.detach()
         if x.dtype != torch.float32:
             x = x.float()
-        p, keep = _make_params(x, cfg, pre_relu)
+        p, keep = _make_params(x, cfg, pre_relu, weight)
         ctx.pre_relu = pre_relu
+        ctx.weight = weight                   # a constant of the backward (never differentiated): kept alive, not saved
         fwd_b, _ = _ws_bytes(p)
         with on_device(x.device):
             # per-pixel projection cache for the backward (32 B per histogram pixel): only when a gradient will be asked
@@ -131,7 +153,7 @@ class RGBuvHistFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, out, sums = ctx.saved_tensors
         cfg = ctx.cfg
-        p, keep = _make_params(x, cfg, ctx.pre_relu)
+        p, keep = _make_params(x, cfg, ctx.pre_relu, ctx.weight)
         if ctx.cache is not None:
             p.proj_cache = ctx.cache.data_ptr()
         _, bwd_b = _ws_bytes(p)
@@ -145,10 +167,10 @@ class RGBuvHistFunction(torch.autograd.Function):
             check(lib.hg_rgbuv_hist_bwd(ctypes.byref(p), x.data_ptr(), g.data_ptr(), out.data_ptr(),
                                         sums.data_ptr(), gx.data_ptr(), ws.data_ptr(), ws.numel(),
                                         _stream(x.device)), 'hg_rgbuv_hist_bwd')
-        return gx, None, None
+        return gx, None, None, None
 
 
-def run_block(x, cfg, device, what, pre_relu=False):
+def run_block(x, cfg, device, what, pre_relu=False, weight=None):
     """forward() of the drop-in histogram modules: resolves the module's `device` argument the way the reference does
     ('cuda', 'cpu', an ordinal, a torch.device).
 
@@ -159,16 +181,30 @@ def run_block(x, cfg, device, what, pre_relu=False):
     dev = torch.device('cuda', device) if isinstance(device, int) else torch.device(device)
     if dev.type != 'cuda':
         from .hist_cpu import hist_cpu
-        return hist_cpu(x if not x.is_cuda else x.cpu(), cfg, pre_relu)
+        if weight is not None and torch.is_tensor(weight) and weight.is_cuda:
+            weight = weight.cpu()
+        return hist_cpu(x if not x.is_cuda else x.cpu(), cfg, pre_relu, weight)
     if not x.is_cuda:
         x = x.to(dev)
-    return rgbuv_hist(x, cfg, pre_relu)
+    if weight is not None and torch.is_tensor(weight) and weight.device != x.device:
+        weight = weight.to(x.device)          # a CPU weight map follows x to the module's GPU
+    return rgbuv_hist(x, cfg, pre_relu, weight)
 
 
-def rgbuv_hist(x, cfg, pre_relu=False):
+def rgbuv_hist(x, cfg, pre_relu=False, weight=None):
     """Differentiable RGB-uv histogram of x (B,C>=3,H,W) -> (B, 3|1, h, h), on x's GPU.  pre_relu: the result and
-    gradient of `rgbuv_hist(F.relu(x))` (the train step's call, histoGAN/histoGAN.py:955) without the relu launch."""
-    return RGBuvHistFunction.apply(x, cfg, pre_relu)
+    gradient of `rgbuv_hist(F.relu(x))` (the train step's call, histoGAN/histoGAN.py:955) without the relu launch.
+    weight: optional per-pixel weight map (B, 1, H, W) or (B, H, W), taken as clamp(weight, 0, 1) and resized with the
+    image; pixel n counts with weight_n * I_y,n.  A constant: the gradient goes to x only, and a weight that requires
+    grad is refused (ValueError).  None = every pixel counts (bit-identical to a map of ones)."""
+    if weight is None:
+        return RGBuvHistFunction.apply(x, cfg, pre_relu)
+    if x.dim() != 4 or x.shape[1] < 3:
+        raise ValueError(f'expected (B, C>=3, H, W) input, got {tuple(x.shape)}')
+    weight = check_weight(x, weight)
+    if weight.device != x.device:
+        raise ValueError(f'weight is on {weight.device}, the input on {x.device}')
+    return RGBuvHistFunction.apply(x, cfg, pre_relu, weight)
 
 
 class HellingerFunction(torch.autograd.Function):

@@ -19,9 +19,12 @@ EPS = 1e-6
 _CHUNK_BYTES = 256 << 20          # fp64 kernel matrices of one chunk: 2 * chunk * N * h * 8 bytes stay below this
 
 
-def _resize(x, cfg):
-    """clamp + resize stage (RGBuvHistBlock.py:76-99): bilinear to insz x insz, or h x h strided samples."""
+def _resize(x, cfg, weight=None):
+    """clamp + resize stage (RGBuvHistBlock.py:76-99): bilinear to insz x insz, or h x h strided samples.  A weight map
+    (B, H, W) rides along as one more channel -- clamped and resized exactly like a colour -- and comes back as channel 3."""
     x = torch.clamp(x, 0, 1)
+    if weight is not None:
+        x = torch.cat([x[:, :3], torch.clamp(weight, 0, 1).unsqueeze(1)], dim=1)
     if x.shape[2] > cfg.insz or x.shape[3] > cfg.insz:
         if cfg.resizing == 'interpolation':
             x = F.interpolate(x, size=(cfg.insz, cfg.insz), mode='bilinear', align_corners=False)
@@ -32,7 +35,7 @@ def _resize(x, cfg):
         else:
             raise Exception(f'Wrong resizing method. It should be: interpolation or sampling. '
                             f'But the given value is {cfg.resizing}.')
-    return x[:, :3]
+    return x[:, :3] if weight is None else x[:, :4]
 
 
 def _planes(I, cfg):
@@ -68,24 +71,49 @@ def _kernel(coord, bins, cfg):
     return k.to(torch.float32)
 
 
-def hist_cpu(x, cfg, pre_relu=False):
-    """x: CPU float (B, C>=3, H, W) -> CPU float32 (B, 3|1, h, h), L1-normalised per image (:224-228)."""
+def _check_weight(x, weight):
+    """The rules of histogan_amd.hist.check_weight (this module must not import the HIP binding)."""
+    if not torch.is_tensor(weight):
+        raise ValueError(f'weight must be a tensor, got {type(weight).__name__}')
+    if weight.requires_grad:
+        raise ValueError('weight requires grad, but the histogram produces no gradient for its weight map '
+                         '(pass weight.detach())')
+    B, _, H, W = x.shape
+    if tuple(weight.shape) == (B, 1, H, W):
+        weight = weight[:, 0]
+    elif tuple(weight.shape) != (B, H, W):
+        raise ValueError(f'weight must have shape {(B, 1, H, W)} or {(B, H, W)} for an input of shape '
+                         f'{tuple(x.shape)}, got {tuple(weight.shape)}')
+    if weight.is_cuda:
+        raise RuntimeError('hist_cpu: GPU weight on the CPU path')
+    return weight if weight.dtype == torch.float32 else weight.float()
+
+
+def hist_cpu(x, cfg, pre_relu=False, weight=None):
+    """x: CPU float (B, C>=3, H, W) -> CPU float32 (B, 3|1, h, h), L1-normalised per image (:224-228).
+    weight: optional per-pixel weight map (B, 1, H, W) or (B, H, W), clamp(weight, 0, 1), resized with the image; pixel n
+    counts with weight_n * I_y,n (the definition of the HIP kernels, include/hg_hist.h).  A constant: no gradient for it."""
     if x.is_cuda:
         raise RuntimeError('hist_cpu: GPU tensor on the CPU path')
     if x.dim() != 4 or x.shape[1] < 3:
         raise ValueError(f'expected (B, C>=3, H, W) input, got {tuple(x.shape)}')
     if x.dtype != torch.float32:
         x = x.float()
+    if weight is not None:
+        weight = _check_weight(x, weight)
     if pre_relu:
         x = F.relu(x)
-    xs = _resize(x, cfg)
+    xs = _resize(x, cfg, weight)
     B, N = xs.shape[0], xs.shape[2] * xs.shape[3]
-    I = xs.reshape(B, 3, N)
+    I = xs[:, :3].reshape(B, 3, N)
+    wmap = None if weight is None else xs[:, 3].reshape(B, N)
     bins = torch.from_numpy(np.linspace(cfg.lo, cfg.hi, num=cfg.h))
     chunk = max(1, _CHUNK_BYTES // max(1, 16 * N * cfg.h))
     parts = []
     for s in range(0, B, chunk):
         w, planes = _planes(I[s:s + chunk], cfg)
+        if wmap is not None:                       # pixel weight: map x I_y (the map alone without intensity_scale)
+            w = wmap[s:s + chunk] if w is None else wmap[s:s + chunk] * w
         hs = []
         for u, v in planes:
             ku, kv = _kernel(u, bins, cfg), _kernel(v, bins, cfg)

@@ -306,6 +306,16 @@ class SyntheticData:
         return b
 
 
+def _alpha_weight(images):
+    """The generated alpha channel as the histogram's weight map, detached.  An image whose alpha is nowhere positive
+    (a fresh generator's output is centred on 0: whole images come out fully transparent) has an all-zero histogram, at
+    which the Hellinger loss has no finite gradient (d sqrt(g) / dg at g = 0): such an image is weighed uniformly, as
+    without the option, so the loss keeps pulling its colours.  Device-side selects only: no host synchronisation."""
+    w = images[:, 3].detach().clamp(0, 1)
+    empty = w.amax(dim=(1, 2), keepdim=True) <= 0
+    return torch.where(empty, torch.ones_like(w), w)
+
+
 class Trainer():
     d_loss, g_loss, h_loss = _lazy_field('d_loss'), _lazy_field('g_loss'), _lazy_field('h_loss')
     last_gp_loss, q_loss, pl_mean = _lazy_field('last_gp_loss'), _lazy_field('q_loss'), _lazy_field('pl_mean')
@@ -315,8 +325,14 @@ class Trainer():
                  save_every=1000, trunc_psi=0.6, fp16=False, fq_layers=[], fq_dict_size=256, attn_layers=[],
                  hist_method='inverse-quadratic', hist_resizing='sampling', hist_sigma=0.02, hist_bin=64,
                  hist_insz=150, aug_prob=0.0, dataset_aug_prob=0.0, aug_types=None, rng='device',
-                 *args, **kwargs):
+                 hist_alpha_weight=False, *args, **kwargs):
         from histogram_classes.RGBuvHistBlock import RGBuvHistBlock
+        # opt-in (transparent=True only): histograms weigh every pixel by its alpha -- the targets by the image's alpha
+        # channel (FolderData), the generator-side histogram of the G loss by the generated alpha, detached -- so the
+        # colour under transparent pixels stops counting.  Default: the reference's behaviour (alpha ignored).
+        if hist_alpha_weight and not transparent:
+            raise ValueError('hist_alpha_weight=True needs transparent=True (there is no alpha channel to weigh by)')
+        self.hist_alpha_weight = bool(hist_alpha_weight)
         if aug_types is None:
             aug_types = ['translation', 'cutout']
         self.GAN_params = [args, kwargs]
@@ -416,9 +432,11 @@ class Trainer():
     def set_data_src(self, folder):
         from .data import FolderData
         self.loader = FolderData(folder, self.histBlock, self.batch_size, self.image_size, self.device,
-                                 transparent=self.transparent, seed=ddp.rank(), aug_prob=self.dataset_aug_prob)
+                                 transparent=self.transparent, seed=ddp.rank(), aug_prob=self.dataset_aug_prob,
+                                 hist_alpha_weight=self.hist_alpha_weight)
         self.loader_evaluate = FolderData(folder, self.histBlock, 4, self.image_size, self.device,
-                                          transparent=self.transparent, seed=977 + ddp.rank(), test=True)
+                                          transparent=self.transparent, seed=977 + ddp.rank(), test=True,
+                                          hist_alpha_weight=self.hist_alpha_weight)
 
     # ------------------------------------------------------------------------------------------
     def _g_stream(self):
@@ -766,7 +784,11 @@ class Trainer():
             self._mark('g_forward_joined_d_updated')
             fake_output, _ = Disc(aug(generated_images))
             self._mark('g_phase_d_forward')
-            generated_histograms = self.histBlock(generated_images, pre_relu=True)   # == histBlock(F.relu(.)), reference :955
+            if self.hist_alpha_weight:   # weigh by the generated alpha (a constant of this histogram: no gradient through it)
+                generated_histograms = self.histBlock(generated_images, pre_relu=True,
+                                                      weight=_alpha_weight(generated_images))
+            else:
+                generated_histograms = self.histBlock(generated_images, pre_relu=True)   # == histBlock(F.relu(.)), reference :955
             histogram_loss = hellinger_loss(hist_batch, generated_histograms, alpha)
             loss = fake_output.mean()
             gen_loss = loss + histogram_loss

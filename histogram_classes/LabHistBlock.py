@@ -33,9 +33,12 @@ class LabHistBlock(nn.Module):
     else:
       self.sigma = sigma
 
-  def forward(self, x):
-    """x: float (B, C>=3, H, W) -> float32 (B, 1, h, h), L1-normalised per image, on `device`."""
+  def forward(self, x, weight=None):
+    """x: float (B, C>=3, H, W) -> float32 (B, 1, h, h), L1-normalised per image, on `device`.
+    weight (an extension; the reference signature is forward(x)): optional per-pixel weight map (B, 1, H, W) or
+    (B, H, W), taken as clamp(weight, 0, 1) and resized with the image; pixel n counts with
+    weight_n * L_n (weight_n alone without intensity_scale).  A constant: no gradient is produced for it."""
     cfg = HistConfig(h=self.h, insz=self.insz, resizing=self.resizing, method=self.method,
                      sigma=getattr(self, 'sigma', 0.02), intensity_scale=self.intensity_scale,
                      hist_boundary=list(self.hist_boundary), projection='direct')
-    return run_block(x, cfg, self.device, 'LabHistBlock')
+    return run_block(x, cfg, self.device, 'LabHistBlock', weight=weight)

@@ -48,8 +48,12 @@ class RGBuvHistBlock(nn.Module):
                       sigma=getattr(self, 'sigma', 0.02), intensity_scale=self.intensity_scale,
                       hist_boundary=list(self.hist_boundary), green_only=self.green_only)
 
-  def forward(self, x, pre_relu=False):
+  def forward(self, x, pre_relu=False, weight=None):
     """x: float (B, C>=3, H, W) -> float32 (B, 3 or 1, h, h), L1-normalised per image, on `device`.
     pre_relu=True: the value and gradient of forward(F.relu(x)) -- the train step's call (histoGAN/histoGAN.py:955) --
-    with the relu folded into the kernel's clamp mask (an extension; the reference signature is forward(x))."""
-    return run_block(x, self._config(), self.device, 'RGBuvHistBlock', pre_relu)
+    with the relu folded into the kernel's clamp mask (an extension; the reference signature is forward(x)).
+    weight (an extension too): optional per-pixel weight map (B, 1, H, W) or (B, H, W) -- a mask, an alpha channel --
+    taken as clamp(weight, 0, 1) and resized with the image; pixel n counts with weight_n * I_y,n (weight_n alone
+    without intensity_scale).  A constant: the gradient goes to x only (exactly 0 where the weight is 0), and a weight
+    that requires grad raises ValueError.  None: every pixel counts, bit-identical to a map of ones."""
+    return run_block(x, self._config(), self.device, 'RGBuvHistBlock', pre_relu, weight)

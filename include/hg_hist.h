@@ -73,10 +73,20 @@ typedef struct hg_hist_params {
    * forward (clamp(relu(x)) == clamp(x)); the backward masks x <= 0 instead of x < 0.  Saves that aten launch and node. */
   int32_t pre_relu;
   /* Optional device buffer of B * Hs * Ws * 32 bytes (16-byte aligned), or NULL.  The forward stores every pixel's
-   * projection (log-chroma differences, weight, clamped / resized colour) there; a backward call given the SAME
+   * projection (log-chroma differences, Iy, clamped / resized colour, the resized `weight` value) there; a backward call given the SAME
    * buffer reads it instead of re-sampling and re-projecting (bilinear taps + three fp64 logarithms per pixel).
    * Smooth kernels (inverse-quadratic, dense RBF) only; the scatter paths ignore it. */
   void *proj_cache;
+  /* Optional per-pixel weight map (since version 103), or NULL = every pixel counts fully (the strides are then not
+   * read).  Device, fp32, one value per INPUT pixel: element (b, y, x) at weight[b*weight_stride_b + y*weight_stride_h
+   * + x*weight_stride_w], element strides, any layout; a stride of 0 broadcasts the map over that axis (one map for the
+   * whole batch: weight_stride_b = 0).  Values are taken as clamp(w, 0, 1).  Stage 0 resizes the map exactly like a
+   * colour channel (same bilinear taps / same row_idx, col_idx gather); histogram pixel n then enters with the weight
+   * w_n * Iy_n (w_n * 1 without intensity_scale, w_n * channel 0 for HG_PROJ_DIRECT).  The map is a constant of the
+   * backward: grad_x is the gradient with w fixed (exactly 0 where w_n == 0), no gradient is produced for it, and the
+   * backward call must be given the same map as the forward.  Every kernel path honours it. */
+  const float *weight;
+  int64_t weight_stride_b, weight_stride_h, weight_stride_w;
 } hg_hist_params;
 
 /* library / build identification */
