@@ -225,7 +225,7 @@ def cached(w, tag, compute):
         if tag == 'wsq':
             _await_pack(owner, w.device, key)
         return hit[1]
-    if tag == 'wsq' and PACK_MULTI and w.is_cuda and _pack_owner(owner, w.device):
+    if tag == 'wsq' and w.is_cuda and _pack_owner(owner, w.device):
         # the batched packing launch of this weight's flat buffer also leaves sum_taps W^2 of every weight (hg_pack_item.wsq)
         hit = _cache.get((key, tag))
         if hit is not None and hit[0] == st:
@@ -248,7 +248,7 @@ def pack_weights(w, mode):
         # A registered (training) weight needs both operands once per optimizer step, and so do all its siblings in the
         # same flat buffer: ONE launch packs every convolution weight of that buffer (hg_conv_pack_weights_multi) the
         # first time one of them is asked for after the buffer changed.
-        if PACK_MULTI and _pack_owner(owner, w.device):
+        if _pack_owner(owner, w.device):
             hit = _cache.get((key, mode))
             if hit is not None and hit[0] == st:
                 return hit[1]
@@ -259,8 +259,7 @@ def pack_weights(w, mode):
     return _pack_weights(w, mode)
 
 
-PACK_MULTI = os.environ.get('HG_PACK_MULTI', '1') != '0'
-_multi = {}          # owner -> dict(sig, keys, bufs, table, n, blocks): the batched-pack plan of one flat buffer
+_multi = {}          # owner -> dict(sig, keys, bufs, lazy, table, n, blocks, wtable, wn, wblocks): the batched-pack plan of one flat buffer
 
 
 class _PackItem(ctypes.Structure):       # include/hg_conv.h: hg_pack_item
@@ -281,7 +280,6 @@ def build_pack_plans(device):
         _pack_owner(owner, device, launch=False)
 
 
-LAZY_DIRECT = os.environ.get('HG_LAZY_DIRECT', '1') != '0'   # no direct pack for weights only ever used through Winograd
 _direct_needed = set()    # keys of registered 3x3 weights whose DIRECT operands some launch asked for
 
 
@@ -299,23 +297,19 @@ def _direct_operand(wt):
         _direct_needed.add(key)
         if p.is_cuda and not torch.cuda.is_current_stream_capturing():
             # another stream that takes this operand afterwards sees direct_stale == False: it has to wait for THIS pack
-            # (registered like a group of the batched pack: consumers wait once per stream, _await_pack)
+            # (registered like the batched pack: consumers wait once per stream, _await_pack)
             cur = torch.cuda.current_stream(p.device)
             _pack_events.setdefault(_owner_of(p), []).append([cur.record_event(), {cur.cuda_stream}, {key}])
     return wt
 
 
-PACK_SPLIT = float(os.environ.get('HG_PACK_SPLIT', '0'))   # share of a buffer's weights in the first pack group (0: one group)
-
-
 def _pack_owner(owner, device, launch=True, record_on=None):
     """Pack every live registered weight of flat buffer `owner` into persistent operand buffers (direct operands + squared
     sums: hg_conv_pack_weights_multi; Winograd operands of the 3x3 weights: hg_wino_pack_weights_multi) and stamp their cache
-    entries.  With HG_PACK_SPLIT > 0 the weights go in TWO groups of launches, in registration (= forward) order: the
-    leading weights that together hold <= PACK_SPLIT of the bytes first (the discriminator's first five blocks are 5 % of
-    its weights: its forward pass could start behind a ~20 us pack while the bulk is packed beside it).  Measured at C3:
-    793.7 images/s with one group, 789.9 with the split (profiles/r05_ab_pack_split.json) -- no gain, the default is one group.  `record_on`: the stream the launches run on -- an event per group is recorded
-    there for the consumers (_await_pack).  The plan (buffers + device tables) is rebuilt when the set of weights changes."""
+    entries.  One pair of launches per buffer (packing a leading share of the weights first was measured without gain: 789.9
+    against 793.7 images/s, profiles/r05_ab_pack_split.json).  `record_on`: the stream the launches run on -- an event is
+    recorded there for the consumers (_await_pack).  The plan (buffers + device tables) is rebuilt when the set of weights
+    changes."""
     live = []
     for key, (own, ref) in list(_cacheable.items()):
         p = ref()
@@ -334,72 +328,59 @@ def _pack_owner(owner, device, launch=True, record_on=None):
         if plan is None or plan['sig'] != sig:
             if torch.cuda.is_current_stream_capturing():
                 return False          # (the table upload is not capturable: per-weight launches for this capture)
-            total = sum(p.numel() for _, p in live)
-            ncut, run = 0, 0
-            for _, p in live:
-                if run + p.numel() > PACK_SPLIT * total:
-                    break
-                run += p.numel()
-                ncut += 1
-            cuts = [(0, ncut), (ncut, len(live))] if 0 < ncut < len(live) else [(0, len(live))]
-            bufs, groups, lazy = {}, [], set()
-            for lo, hi in cuts:
-                items, witems, blocks, wblocks = [], [], 0, 0
-                for key, p in live[lo:hi]:
-                    Co, Ci, k, _ = p.shape
-                    wf = torch.empty(lib.hg_conv_packed_elems(Co, Ci, k, PACK_FWD), dtype=torch.float32, device=device)
-                    wd = torch.empty(lib.hg_conv_packed_elems(Co, Ci, k, PACK_DGRAD), dtype=torch.float32, device=device)
-                    # sum over the taps of W^2 (the demodulation coefficient's weight factor), from the same tile
-                    wq = torch.empty((Co, Ci), dtype=torch.float32, device=device)
-                    bufs[key] = (wf, wd, wq)
-                    wf.wino = wd.wino = False
-                    nf = nd = 0
-                    if WINO and k == 3 and key not in no_wino:   # the Winograd operands of the 3x3 weights (include/hg_wino.h), one more launch
-                        nf, nd = lib.hg_wino_packed_elems(Co, Ci, PACK_FWD), lib.hg_wino_packed_elems(Co, Ci, PACK_DGRAD)
-                        if nf:
-                            wf.wino = torch.empty(nf, dtype=torch.float32, device=device)
-                        if nd:
-                            wd.wino = torch.empty(nd, dtype=torch.float32, device=device)
-                    # A weight whose launches all take the Winograd operands needs no direct pack: its direct operands are
-                    # left stale (`direct_stale`) until a launch asks for them -- _direct_operand packs that one weight then
-                    # and puts it on the `_direct_needed` list, i.e. into the batched launch from the next plan on.
-                    skip = LAZY_DIRECT and nf and nd and key not in _direct_needed
-                    if skip:
-                        lazy.add(key)
-                    else:
-                        items.append(_PackItem(p.data_ptr(), wf.data_ptr(), wd.data_ptr(), Co, Ci, k, blocks, wq.data_ptr()))
-                        blocks += lib.hg_conv_pack_blocks(Co, Ci)
-                    if nf or nd:
-                        witems.append(_WinoItem(p.data_ptr(), wf.wino.data_ptr() if nf else None,
-                                                wd.wino.data_ptr() if nd else None, wq.data_ptr() if skip else None,
-                                                Co, Ci, wblocks, 0))
-                        wblocks += lib.hg_wino_pack_blocks(Co, Ci, int(bool(nf)), int(bool(nd)))
-                    for m_, t_ in ((PACK_FWD, wf), (PACK_DGRAD, wd)):
-                        t_.pack_src = (weakref.ref(p), m_, key)
-                up = lambda arr: torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone().to(device)
-                groups.append(dict(keys={key for key, _ in live[lo:hi]}, table=up((_PackItem * len(items))(*items)) if items else None,
-                                   n=len(items), blocks=blocks, wn=len(witems), wblocks=wblocks,
-                                   wtable=up((_WinoItem * len(witems))(*witems)) if witems else None))
-            plan = _multi[owner] = dict(sig=sig, bufs=bufs, groups=groups, lazy=lazy)
+            bufs, lazy = {}, set()
+            items, witems, blocks, wblocks = [], [], 0, 0
+            for key, p in live:
+                Co, Ci, k, _ = p.shape
+                wf = torch.empty(lib.hg_conv_packed_elems(Co, Ci, k, PACK_FWD), dtype=torch.float32, device=device)
+                wd = torch.empty(lib.hg_conv_packed_elems(Co, Ci, k, PACK_DGRAD), dtype=torch.float32, device=device)
+                # sum over the taps of W^2 (the demodulation coefficient's weight factor), from the same tile
+                wq = torch.empty((Co, Ci), dtype=torch.float32, device=device)
+                bufs[key] = (wf, wd, wq)
+                wf.wino = wd.wino = False
+                nf = nd = 0
+                if WINO and k == 3 and key not in no_wino:   # the Winograd operands of the 3x3 weights (include/hg_wino.h), one more launch
+                    nf, nd = lib.hg_wino_packed_elems(Co, Ci, PACK_FWD), lib.hg_wino_packed_elems(Co, Ci, PACK_DGRAD)
+                    if nf:
+                        wf.wino = torch.empty(nf, dtype=torch.float32, device=device)
+                    if nd:
+                        wd.wino = torch.empty(nd, dtype=torch.float32, device=device)
+                # A weight whose launches all take the Winograd operands needs no direct pack: its direct operands are
+                # left stale (`direct_stale`) until a launch asks for them -- _direct_operand packs that one weight then
+                # and puts it on the `_direct_needed` list, i.e. into the batched launch from the next plan on.
+                skip = nf and nd and key not in _direct_needed
+                if skip:
+                    lazy.add(key)
+                else:
+                    items.append(_PackItem(p.data_ptr(), wf.data_ptr(), wd.data_ptr(), Co, Ci, k, blocks, wq.data_ptr()))
+                    blocks += lib.hg_conv_pack_blocks(Co, Ci)
+                if nf or nd:
+                    witems.append(_WinoItem(p.data_ptr(), wf.wino.data_ptr() if nf else None,
+                                            wd.wino.data_ptr() if nd else None, wq.data_ptr() if skip else None,
+                                            Co, Ci, wblocks, 0))
+                    wblocks += lib.hg_wino_pack_blocks(Co, Ci, int(bool(nf)), int(bool(nd)))
+                for m_, t_ in ((PACK_FWD, wf), (PACK_DGRAD, wd)):
+                    t_.pack_src = (weakref.ref(p), m_, key)
+            up = lambda arr: torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone().to(device)
+            plan = _multi[owner] = dict(sig=sig, keys={key for key, _ in live}, bufs=bufs, lazy=lazy,
+                                        table=up((_PackItem * len(items))(*items)) if items else None,
+                                        n=len(items), blocks=blocks, wn=len(witems), wblocks=wblocks,
+                                        wtable=up((_WinoItem * len(witems))(*witems)) if witems else None)
         if not launch:
             return True
         _await_pack(owner, device)         # an asynchronous pack of the same buffers still in flight goes first
         _pack_events.pop(owner, None)
-        events = []
         for key in plan['lazy']:           # (weights changed: a direct operand packed on demand last step is stale again)
             wf, wd, _ = plan['bufs'][key]
             wf.direct_stale = wd.direct_stale = True
-        for g in plan['groups']:
-            if g['table'] is not None:
-                check(lib.hg_conv_pack_weights_multi(g['table'].data_ptr(), g['n'], g['blocks'], raw_stream(device)),
-                      'hg_conv_pack_weights_multi')
-            if g['wtable'] is not None:
-                check(lib.hg_wino_pack_weights_multi(g['wtable'].data_ptr(), g['wn'], g['wblocks'], raw_stream(device)),
-                      'hg_wino_pack_weights_multi')
-            if record_on is not None:
-                events.append([record_on.record_event(), {record_on.cuda_stream}, g['keys']])
-        if events:
-            _pack_events[owner] = events
+        if plan['table'] is not None:
+            check(lib.hg_conv_pack_weights_multi(plan['table'].data_ptr(), plan['n'], plan['blocks'], raw_stream(device)),
+                  'hg_conv_pack_weights_multi')
+        if plan['wtable'] is not None:
+            check(lib.hg_wino_pack_weights_multi(plan['wtable'].data_ptr(), plan['wn'], plan['wblocks'], raw_stream(device)),
+                  'hg_wino_pack_weights_multi')
+        if record_on is not None:
+            _pack_events[owner] = [[record_on.record_event(), {record_on.cuda_stream}, plan['keys']]]
     for key, p in live:
         st = _stamp(p, owner)
         wf, wd, wq = plan['bufs'][key]
@@ -409,9 +390,8 @@ def _pack_owner(owner, device, launch=True, record_on=None):
     return True
 
 
-PREPACK = os.environ.get('HG_PREPACK', '1') != '0'
 _pack_streams = {}
-_pack_events = {}    # owner -> [[event behind a group of the asynchronous batched pack, ids of the streams that already wait for it, keys of the group]]
+_pack_events = {}    # owner -> [[event behind the asynchronous batched pack (or one on-demand direct pack), ids of the streams that already wait for it, keys of the weights it covers]]
 
 
 def prepack_async(flat):
@@ -420,7 +400,7 @@ def prepack_async(flat):
     mapping network's serial ~15 us launches -- the 0.2 ms packing launch runs under those.  Consumers wait for the pack's
     event (_await_pack, once per stream); the launch itself is ordered behind everything enqueued on the current stream
     (the readers of the operand buffers it overwrites)."""
-    if not (PREPACK and PACK_MULTI) or not flat.is_cuda or torch.cuda.is_current_stream_capturing():
+    if not flat.is_cuda or torch.cuda.is_current_stream_capturing():
         return False
     device, owner = flat.device, _owner_of(flat)
     st = _pack_streams.get(device.index)
@@ -443,8 +423,8 @@ def drain_pack_streams():
 
 
 def _await_pack(owner, device, key=None):
-    """The current stream waits for the asynchronous pack of flat buffer `owner` -- for the group that holds weight `key`
-    (None: every group) -- once per stream and event."""
+    """The current stream waits for the asynchronous packs of flat buffer `owner` -- for those that cover weight `key`
+    (None: all of them) -- once per stream and event."""
     if torch.cuda.is_current_stream_capturing():    # (drain_pack_streams() ran before the capture began)
         return
     ents = _pack_events.get(owner)
@@ -577,9 +557,6 @@ def conv_wgrad(x, gout, ksize, stride=1, iscale=None, gscale=None, out=None):
 # All direct writes go through the one side stream, in order, so a second contribution to the same weight in the same
 # step (gradient accumulation, the gradient penalty's second-order term, the path-length pass) is simply added there;
 # FlatParams.gather() makes the main stream wait for the side stream before anything reads the buffer.
-SIDE_WGRAD = os.environ.get('HG_WGRAD_STREAM', '1') != '0'
-GRAPH_WGRAD_INLINE = os.environ.get('HG_GRAPH_WGRAD_INLINE', '1') != '0'
-DIRECT_DEMOD = os.environ.get('HG_DIRECT_DEMOD', '1') != '0'   # demodulation's weight-gradient term into the flat slot (direct_weight_term)
 _slots = {}          # (data_ptr, shape) of a registered weight -> (offset, numel, weakref to the owner FlatParams)
 _side_streams = {}   # device index -> torch.cuda.Stream
 
@@ -600,7 +577,7 @@ def register_grad_slots(flat):
 def grad_slot(w):
     """(slot view, owner FlatParams) of a registered convolution weight whose gradient may be written directly right now
     (between zero_grad() and gather(), plain backward), or None."""
-    if not SIDE_WGRAD or torch.is_grad_enabled():
+    if torch.is_grad_enabled():
         return None
     ent = _slots.get((w.data_ptr(), tuple(w.shape)))
     if ent is None:
@@ -615,16 +592,14 @@ def grad_slot(w):
 def side_stream(device):
     st = _side_streams.get(device.index)
     if st is None:
-        # HG_W_STREAM_PRIO: HIP priority of the weight-gradient stream (0 normal, -1 high), an experiment knob
-        st = _side_streams[device.index] = torch.cuda.Stream(
-            device=device, priority=int(os.environ.get('HG_W_STREAM_PRIO', '0')))
+        st = _side_streams[device.index] = torch.cuda.Stream(device=device)
     return st
 
 
 def _assert_single_writer(device):
     """Overwrite-vs-accumulate of a flat gradient slot is decided from the host-side set `direct_written` at ENQUEUE time:
     correct only while every direct write is enqueued on ONE stream in order (the weight-gradient stream, or the capturing
-    stream with HG_GRAPH_WGRAD_INLINE).  A second writer stream would silently corrupt gradients: fail loudly instead."""
+    stream during a hipGraph capture).  A second writer stream would silently corrupt gradients: fail loudly instead."""
     cur = torch.cuda.current_stream(device)
     assert torch.cuda.is_current_stream_capturing() or cur.cuda_stream == side_stream(device).cuda_stream, \
         'direct gradient write outside the weight-gradient stream'
@@ -633,7 +608,7 @@ def _assert_single_writer(device):
 def _direct_wgrad(w, x, g, stride):
     """Weight gradient of conv(x, w) for upstream gradient g into w's flat-buffer slot; False if w has no slot (or
     a graph is being recorded): the caller then returns the gradient to autograd as usual."""
-    if not SIDE_WGRAD or torch.is_grad_enabled():
+    if torch.is_grad_enabled():
         return False
     key = (w.data_ptr(), tuple(w.shape))
     ent = _slots.get(key)
@@ -651,7 +626,7 @@ def _direct_wgrad(w, x, g, stride):
     if _batch_pieces(xc, w, stride) != 1:
         return False
     skey = slot.data_ptr()
-    if GRAPH_WGRAD_INLINE and torch.cuda.is_current_stream_capturing():
+    if torch.cuda.is_current_stream_capturing():
         # inside a hipGraph capture every fork to the side stream becomes a cross-branch dependency edge (~100 per step):
         # measured slower than the eager side stream; the direct write (no per-parameter copy) stays, on the main branch
         if skey in flat.direct_written:
@@ -681,7 +656,7 @@ def direct_demod_weight_term(w, gd, d, s1):
     (N x B) @ (B x K) rocBLAS GEMM (314 us at 2048 x 2048: no library kernel for a 32-deep reduction), two element-wise
     launches over the weight, a gradient tensor for autograd and the `both` add of FlatParams.gather.  False: no slot
     (or a higher-order pass / a recording graph) -- the caller returns the term to autograd."""
-    if not (SIDE_WGRAD and DIRECT_DEMOD) or torch.is_grad_enabled():
+    if torch.is_grad_enabled():
         return False
     key = (w.data_ptr(), tuple(w.shape))
     ent = _slots.get(key)
@@ -705,7 +680,7 @@ def direct_demod_weight_term(w, gd, d, s1):
                   'hg_demod_weight_term')
         flat.direct_written.add(skey)
 
-    if GRAPH_WGRAD_INLINE and torch.cuda.is_current_stream_capturing():
+    if torch.cuda.is_current_stream_capturing():
         run()
         return True
     main = torch.cuda.current_stream(w.device)

@@ -23,7 +23,6 @@ from ._lib import check, lib, on_device, raw_stream
 
 GFUSED = os.environ.get('HG_GFUSED', '1') != '0'
 PER_BLOCK = 10        # tensors per block in the Function's argument list (see generator_train)
-DEMOD_AUX = os.environ.get('HG_DEMOD_AUX', '0') != '0'
 AFTER_BLOCKS = None    # trainer: called when the node's backward has enqueued the last convolution weight gradient
 STAGE_OBSERVER = None  # tests: called with every stage output (two per block, forward order) -- the LeakyReLU branches taken
 
@@ -195,25 +194,14 @@ class _GeneratorTrain(torch.autograd.Function):
         ga = None          # d loss / d (modulated, up-sampled input of the NEXT block's first convolution)
         sa = None
         # The demodulation coefficients' adjoints (a small GEMM-like kernel pair + the weight term per convolution) only feed
-        # the style gradients returned at the end.  HG_DEMOD_AUX=1 runs them on the auxiliary stream, off the dgrad -> stage ->
-        # dgrad chain: measured 854.6 vs 867.7 images/s inline (they already hide under the weight-gradient kernels) -- off.
-        dev = g_rgb.device
-        main, aux = torch.cuda.current_stream(dev), _N.aux_stream(dev)
+        # the style gradients returned at the end.  They run inline: on the auxiliary stream, off the dgrad -> stage -> dgrad
+        # chain, they measured 854.6 against 867.7 images/s -- they already hide under the
+        # weight-gradient kernels.
         pend = []          # (index into grads, modulation part, demodulation part)
         wterm = {}
 
-        def demod_async(idx, gd, d, s1p, wsq, wp):
-            if not DEMOD_AUX or torch.cuda.is_current_stream_capturing():
-                gy, wterm[idx] = _demod_bwd(gd, d, s1p, wsq, wp)
-                return gy
-            aux.wait_event(main.record_event())
-            with torch.cuda.stream(aux):
-                gy, gwd = _demod_bwd(gd, d, s1p, wsq, wp)
-            gd.record_stream(aux)
-            gy.record_stream(main)
-            if gwd is not None:
-                gwd.record_stream(main)
-            wterm[idx] = gwd
+        def demod(idx, gd, d, s1p, wsq, wp):
+            gy, wterm[idx] = _demod_bwd(gd, d, s1p, wsq, wp)
             return gy
         for i in range(L - 1, -1, -1):
             xm1, out1, xm2, out2, s1, s2, srgb, d1, d2, wn1, bn1, wn2, bn2, s1p, s2p, wsq1, wsq2 = blk(i)
@@ -239,7 +227,7 @@ class _GeneratorTrain(torch.autograd.Function):
             grads[base + 8], grads[base + 9] = gwn2.reshape(-1, 1), gbn2
             g_xm2 = C.conv_dgrad_packed(gconv2, C.pack_weights(w2, C.PACK_DGRAD), w2.shape[1], xm2.shape[2], xm2.shape[3], 3)
             grads[base + 4] = _wgrad(w2p, xm2, gconv2)
-            gy2 = demod_async(base + 4, gd2, d2, s2p, wsq2, w2p)
+            gy2 = demod(base + 4, gd2, d2, s2p, wsq2, w2p)
             if i > 0:                                            # rgb_i = to_rgb(out2) + up2(rgb_{i-1})
                 g_rgb_prev, _ = _modulate_bwd(g_rgb, torch.empty((g_rgb.shape[0], Cr, g_rgb.shape[2] // 2, g_rgb.shape[3] // 2),
                                                                  dtype=torch.float32, device=g_rgb.device), None, True)
@@ -249,7 +237,7 @@ class _GeneratorTrain(torch.autograd.Function):
             grads[base + 6], grads[base + 7] = gwn1.reshape(-1, 1), gbn1
             ga = C.conv_dgrad_packed(gconv1, C.pack_weights(w1, C.PACK_DGRAD), w1.shape[1], xm1.shape[2], xm1.shape[3], 3)
             grads[base + 3] = _wgrad(w1p, xm1, gconv1)
-            gy_next = demod_async(base + 3, gd1, d1, s1p, wsq1, w1p)
+            gy_next = demod(base + 3, gd1, d1, s1p, wsq1, w1p)
             sa = s1
             if i > 0:
                 g_rgb = g_rgb_prev
@@ -257,8 +245,6 @@ class _GeneratorTrain(torch.autograd.Function):
         gx0e, gs1_0 = _modulate_bwd(ga, x0e, sa, False)
         pend.append((0, gs1_0, gy_next))
         g_x0 = gx0e.sum(0)
-        if DEMOD_AUX and not torch.cuda.is_current_stream_capturing():
-            main.wait_stream(aux)
         torch._foreach_add_([a for _, a, _ in pend], [b for _, _, b in pend])
         for idx, a, _ in pend:
             grads[idx] = a

@@ -14,7 +14,6 @@ from . import _lib
 from ._lib import HgHistParams, check, lib, on_device, raw_stream
 
 _IDX_CACHE = {}
-PROJ_CACHE = os.environ.get('HG_PROJ_CACHE', '1') != '0'   # A/B switch of the forward->backward projection cache
 
 
 def _sampling_idx(size, h, device):
@@ -134,7 +133,7 @@ class RGBuvHistFunction(torch.autograd.Function):
             # for and only when the dense MFMA kernels will run (the scatter paths -- thresholding, narrow RBF --
             # re-classify pixels cheaply and ignore it)
             cache = None
-            if ctx.needs_input_grad[0] and PROJ_CACHE and lib.hg_rgbuv_hist_uses_proj_cache(ctypes.byref(p)) == 1:
+            if ctx.needs_input_grad[0] and lib.hg_rgbuv_hist_uses_proj_cache(ctypes.byref(p)) == 1:
                 cache = torch.empty((p.B, p.Hs * p.Ws, 8), dtype=torch.float32, device=x.device)
                 p.proj_cache = cache.data_ptr()
             ctx.cache = cache

@@ -47,7 +47,6 @@ def _noise_t(inoise):
     return nzt
 
 
-STYLES_AHEAD = os.environ.get('HG_STYLES_AHEAD', '1') != '0'
 PHASE_HOOK = None     # tools/phase_probe.py: called with a phase name at points inside the networks (None: no-op)
 _aux_streams = {}
 
@@ -156,7 +155,7 @@ class GeneratorBlock(nn.Module):
         # (d before the convolution: the backward then reaches the convolution's weight gradient first, which writes the flat
         # gradient slot outright, and the demodulation's weight term accumulates into it -- conv.direct_weight_term)
         d = conv.demod_coeff(style) if conv.demod else None
-        if (ops.FUSED_DNL and conv.stride == 1 and conv.dilation == 1 and conv.kernel in (1, 3) and x.is_cuda
+        if (conv.stride == 1 and conv.dilation == 1 and conv.kernel in (1, 3) and x.is_cuda
                 and nzt.shape[-1] % 2 == 0 and conv.weight.dtype == torch.float32):
             # modulation prologue (materialised: the weight gradient's operand), then convolution + demodulation + noise +
             # LeakyReLU as one launch (ops._ConvDnl)
@@ -218,7 +217,7 @@ class Generator(nn.Module):
             # chain on the second stream.
             groups = [i for i in range(len(self.blocks)) for _ in range(3)]
             xs = [styles[i] for i in range(len(self.blocks))]
-            ahead = (STYLES_AHEAD and not torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing())
+            ahead = not torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing()
             if ahead:
                 main, aux = torch.cuda.current_stream(styles.device), aux_stream(styles.device)
                 aux.wait_event(main.record_event())
@@ -243,8 +242,7 @@ class Generator(nn.Module):
             for i, block in enumerate(self.blocks):
                 x, rgb = block.forward_(x, rgb, t[3 * i], t[3 * i + 1], t[3 * i + 2], inoise=input_noise)
             return rgb
-        if (STYLES_AHEAD and styles.is_cuda and not torch.is_grad_enabled()
-                and not torch.cuda.is_current_stream_capturing()):
+        if styles.is_cuda and not torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
             # Without autograd (the D phase's generator forward, evaluate()): the 21 `to_style` projections depend on the
             # styles only, yet as launches between the convolutions each one holds the convolution chain up for a
             # ~15 us GEMM.  They run ahead on a second stream, block by block; the chain waits for its block's event.

@@ -12,9 +12,7 @@ import torch
 from ._lib import check, lib, on_device, raw_stream
 
 
-KEEP_CONV = os.environ.get('HG_DNL_KEEP_CONV', '1') != '0'
 SKINNY_SPLIT = os.environ.get('HG_SKINNY_SPLIT', '1') != '0'   # _skinny_mm: chunked bmm + sum (0: plain mm)
-FUSED_DEMOD_BWD = os.environ.get('HG_FUSED_DEMOD_BWD', '1') != '0'   # hg_demod_style_grad (0: aten ops)
 
 
 def _st(t):
@@ -104,19 +102,14 @@ class _DemodNoiseLrelu(torch.autograd.Function):
             check(lib.hg_demod_noise_lrelu_fwd(conv.data_ptr(), None if d is None else d.data_ptr(), nzt.data_ptr(),
                                                wn.data_ptr(), bn.data_ptr(), out.data_ptr(), B, O, H, S, _st(conv)),
                   'hg_demod_noise_lrelu_fwd')
-        # HG_DNL_KEEP_CONV=0: the convolution output is not kept for the backward; conv*d is recovered from `out` there
-        # (pre = out > 0 ? out : 5 out, minus the noise term) -- one tensor less per stage and one read less in k_dnl_bwd.
-        # Measured at C3: 54.7 vs 54.5 ms per plain step (the kernel hides behind the side-stream weight gradients), so
-        # the stored operand (no recovery rounding) stays the default.
-        if KEEP_CONV:
-            ctx.save_for_backward(conv, d, nzt, out, wn, bn)
-        else:
-            ctx.save_for_backward(None, d, nzt, out, wn, bn)
+        # The convolution output is kept for the backward (no recovery rounding); recovering conv*d from `out` there instead
+        # was measured at C3 within noise: 45.86 against 45.99 ms per plain step.
+        ctx.save_for_backward(conv, d, nzt, out)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        conv, d, nzt, out, wn, bn = ctx.saved_tensors
+        conv, d, nzt, out = ctx.saved_tensors
         g = _f32c(g.detach())
         B, O, H, _ = out.shape
         S = nzt.shape[-1]
@@ -126,10 +119,8 @@ class _DemodNoiseLrelu(torch.autograd.Function):
             gw = torch.empty((B, O), dtype=torch.float32, device=out.device)
             gb = torch.empty((B, O), dtype=torch.float32, device=out.device)
             ws, n = _ws(out, B, O, H, H)
-            check(lib.hg_demod_noise_lrelu_bwd(g.data_ptr(), out.data_ptr(), None if conv is None else conv.data_ptr(),
-                                               None if d is None else d.data_ptr(), nzt.data_ptr(),
-                                               None if conv is not None else wn.data_ptr(),
-                                               None if conv is not None else bn.data_ptr(), gconv.data_ptr(),
+            check(lib.hg_demod_noise_lrelu_bwd(g.data_ptr(), out.data_ptr(), conv.data_ptr(),
+                                               None if d is None else d.data_ptr(), nzt.data_ptr(), None, None, gconv.data_ptr(),
                                                None if gd is None else gd.data_ptr(), gw.data_ptr(), gb.data_ptr(),
                                                B, O, H, S, ws.data_ptr(), n, _st(out)), 'hg_demod_noise_lrelu_bwd')
         return gconv, gd, None, gw.sum(0).reshape(-1, 1), gb.sum(0)
@@ -189,9 +180,6 @@ class _ToRGB(torch.autograd.Function):
 def torgb(x, style, weight, prev=None):
     """conv1x1(x * (style + 1), weight) + prev in one launch per direction -- see _ToRGB."""
     return _ToRGB.apply(x, style, weight, prev)
-
-
-FUSED_DNL = os.environ.get('HG_FUSED_DNL', '1') != '0'   # conv + demodulation + noise + LeakyReLU as one forward launch in training
 
 
 class _ConvDnl(torch.autograd.Function):
@@ -378,7 +366,7 @@ class _DemodCoeff(torch.autograd.Function):
     def backward(ctx, gd):
         s1, wsq, d, w = ctx.saved_tensors
         gy = gw = gq = None
-        fused = FUSED_DEMOD_BWD and gd.is_cuda and not torch.is_grad_enabled() and wsq.is_contiguous()
+        fused = gd.is_cuda and not torch.is_grad_enabled() and wsq.is_contiguous()
         if ctx.needs_input_grad[0]:
             if fused:       # one kernel pair (hg_demod_style_grad) instead of a skinny rocBLAS GEMM + five element-wise launches
                 gdc, B, N, K = _f32c(gd), d.shape[0], d.shape[1], s1.shape[1]

@@ -21,7 +21,7 @@ def _st(t):
 def conv_first(params):
     """`params` with the convolution weights (4-d tensors) first, order otherwise kept: the flat buffer then starts with one
     contiguous region that holds every convolution weight (FlatParams.n_conv elements) -- the region whose gradients are final
-    when the last convolution's backward has been enqueued, long before the mapping networks' (DiffGrad.step_early)."""
+    when the last convolution's backward has been enqueued, long before the mapping networks' (ddp.GradAllReduce.start_early)."""
     params = list(params)
     return [p for p in params if p.dim() == 4] + [p for p in params if p.dim() != 4]
 
@@ -104,8 +104,8 @@ class FlatParams:
             return
         self.direct_ok = False
         if self.direct_written and self.grad.is_cuda:   # weight gradients written on the side stream: order them before any reader
-            from .conv import GRAPH_WGRAD_INLINE, side_stream
-            if not (GRAPH_WGRAD_INLINE and torch.cuda.is_current_stream_capturing()):   # (captured: written on this branch)
+            from .conv import side_stream
+            if not torch.cuda.is_current_stream_capturing():   # (captured: written on this branch)
                 torch.cuda.current_stream(self.grad.device).wait_stream(side_stream(self.grad.device))
         dst, src, missing, both = [], [], [], []
         off = 0
@@ -171,62 +171,29 @@ class DiffGrad:
         if self.graph_mode:
             raise RuntimeError('DiffGrad.step_buckets: not available inside a captured graph')
         self.step_count += 1
-        lr = self.param_groups[0]['lr']
         with on_device(f.data.device):
             for i, (lo, hi) in enumerate(reducer.ranges):
                 reducer.wait(i)
-                o = 4 * lo
-                check(lib.hg_diffgrad_step(f.data.data_ptr() + o, f.grad.data_ptr() + o, self.exp_avg.data_ptr() + o,
-                                           self.exp_avg_sq.data_ptr() + o, self.previous_grad.data_ptr() + o, hi - lo,
-                                           float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                           self.step_count, _st(f.data)), 'hg_diffgrad_step')
+                self._launch(lo, hi, self.step_count)
         reducer.finish()
         weights_changed(f.data)
 
-    def step_early(self, stream):
-        """The update of the flat buffer's leading convolution-weight region NOW, on `stream` -- legal as soon as every one of
-        those weights has its final gradient in its flat slot (all written directly: conv._direct_wgrad, the demodulation
-        term, gfused's to-RGB slot write), i.e. when the generator's fused backward node returns, while the mapping
-        networks' backward (a latency-bound chain of ~70 small launches) is still to run.  `step()` then updates the rest.
-        Returns False (nothing done) when a slot of the region was not written directly."""
+    def _launch(self, lo, hi, step_count):
+        """hg_diffgrad_step over elements [lo, hi) of the flat buffers, as step number `step_count`."""
         f = self.flat
-        hi = f.n_conv
-        if hi <= 0 or self.graph_mode or not f.data.is_cuda or getattr(self, '_early', None) is not None \
-                or not f.conv_region_final():
-            return False
-        from .conv import side_stream
-        dev = f.data.device
-        stream.wait_stream(side_stream(dev))                       # the weight gradients and demodulation terms
-        stream.wait_event(torch.cuda.current_stream(dev).record_event())   # slots written on the calling stream (to-RGB)
         lr = self.param_groups[0]['lr']
-        with torch.cuda.stream(stream), on_device(dev):
-            check(lib.hg_diffgrad_step(f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                       self.exp_avg_sq.data_ptr(), self.previous_grad.data_ptr(), hi, float(lr),
-                                       float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_count + 1,
-                                       _st(f.data)), 'hg_diffgrad_step')
-        self._early = (hi, stream)
-        weights_changed(f.data)
-        return True
+        o = 4 * lo
+        with on_device(f.data.device):
+            check(lib.hg_diffgrad_step(f.data.data_ptr() + o, f.grad.data_ptr() + o, self.exp_avg.data_ptr() + o,
+                                       self.exp_avg_sq.data_ptr() + o, self.previous_grad.data_ptr() + o, hi - lo,
+                                       float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                                       step_count, _st(f.data)), 'hg_diffgrad_step')
 
     def step(self):
         f = self.flat
         f.gather()
         if not f.data.is_cuda:
             raise RuntimeError('DiffGrad: parameters are not on a GPU; no CPU implementation')
-        early = self.__dict__.pop('_early', None)
-        if early is not None:         # the convolution-weight region was updated by step_early(): the rest now, same step number
-            lo, stream = early
-            self.step_count += 1
-            lr = self.param_groups[0]['lr']
-            with on_device(f.data.device):
-                if f.numel > lo:
-                    o = 4 * lo
-                    check(lib.hg_diffgrad_step(f.data.data_ptr() + o, f.grad.data_ptr() + o, self.exp_avg.data_ptr() + o,
-                                               self.exp_avg_sq.data_ptr() + o, self.previous_grad.data_ptr() + o, f.numel - lo,
-                                               float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                               self.step_count, _st(f.data)), 'hg_diffgrad_step')
-            torch.cuda.current_stream(f.data.device).wait_stream(stream)
-            return                    # (weights_changed() ran with the early part: the packed operands may already be rebuilt)
         if self.graph_mode:           # being captured: step size from device memory, counter advanced by prepare_replay()
             with on_device(f.data.device):
                 check(lib.hg_diffgrad_step_dev(f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
@@ -237,12 +204,7 @@ class DiffGrad:
             weights_changed(f.data)
             return
         self.step_count += 1
-        lr = self.param_groups[0]['lr']
-        with on_device(f.data.device):
-            check(lib.hg_diffgrad_step(f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                       self.exp_avg_sq.data_ptr(), self.previous_grad.data_ptr(), f.numel,
-                                       float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                       self.step_count, _st(f.data)), 'hg_diffgrad_step')
+        self._launch(0, f.numel, self.step_count)
         weights_changed(f.data)
 
 

@@ -32,7 +32,7 @@ from .hist import hellinger_loss
 from .nets import Discriminator, HistVectorizer
 from .optim import DiffGrad, FlatParams
 from .renets import RecoloringEncoderDecoder, RecoloringGAN
-from .trainer import (G_OVERLAP, NanException, SyntheticData, _freeze_gc_once, _Rng, cast_list, gradient_penalty,
+from .trainer import (NanException, SyntheticData, _freeze_gc_once, _Rng, cast_list, gradient_penalty,
                       set_requires_grad)
 
 SOBEL_X = ((1, 0, -1), (2, 0, -2), (1, 0, -1))
@@ -315,7 +315,7 @@ class recoloringTrainer():
 
         # the G phase's forward on a second stream beside the discriminator's forward / backward (single-GPU runs; see
         # histogan_amd/trainer.py)
-        overlap_g = G_OVERLAP and acc == 1 and not ddp.is_dist()
+        overlap_g = acc == 1 and not ddp.is_dist()
         if overlap_g and not getattr(self, '_warn_off', False):
             fn = getattr(torch.autograd.graph, 'set_warn_on_accumulate_grad_stream_mismatch', None)
             if fn is not None:

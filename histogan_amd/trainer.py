@@ -50,13 +50,8 @@ from .optim import DiffGrad, FlatParams, conv_first, ema_update
 
 EPS = 1e-8
 EXTS = ['jpg', 'png']
-G_OVERLAP_DDP = os.environ.get('HG_G_OVERLAP_DDP', 'auto')   # the same under data parallelism: auto | 1 | 0 (see _device_step)
-G_OVERLAP = os.environ.get('HG_G_OVERLAP', '1') != '0'   # G-phase generator forward on a second stream beside the D phase
-G_STREAM_PRIO = int(os.environ.get('HG_G_STREAM_PRIO', '0'))   # HIP priority of that stream (0 normal, -1 high)
-H_SIDE = os.environ.get('HG_H_SIDE', '1') != '0'               # histogram vectorizer on a second stream beside S
-H_SIDE_GRAD = os.environ.get('HG_H_SIDE_GRAD', '1') != '0'     # ... in the grad-enabled G-phase forward too (its backward then runs there as well)
-BATCH_S = os.environ.get('HG_BATCH_S', '1') != '0'             # both latent batches of a mixed draw through S at once
-D_STEP_EARLY = os.environ.get('HG_D_STEP_EARLY', '1') != '0'   # D's optimizer step before main waits for that stream
+# G-phase generator forward on a second stream beside the D phase, under data parallelism: auto | 1 | 0 (see _device_step)
+G_OVERLAP_DDP = os.environ.get('HG_G_OVERLAP_DDP', 'auto')
 # Plain steps replayed from a captured hipGraph (single process): HG_GRAPH = auto (default) | 1 | 0 | 2.
 #   auto: decided from the first eager plain steps -- the graph is used when the host's enqueue work IS the step (small
 #         batches, slow hosts: batch 4 at 256^2 runs 30 -> 20 ms; the enqueue time then equals the GPU-side step time,
@@ -68,10 +63,6 @@ D_STEP_EARLY = os.environ.get('HG_D_STEP_EARLY', '1') != '0'   # D's optimizer s
 GRAPH_MODE = os.environ.get('HG_GRAPH', 'auto')
 GRAPH_AUTO_RATIO = float(os.environ.get('HG_GRAPH_AUTO_RATIO', '0.9'))
 GRAPH_GP = os.environ.get('HG_GRAPH_GP', '1') != '0'      # gradient-penalty steps replay from their own graph too
-# G's convolution weights updated + re-packed under the tail of its backward (DiffGrad.step_early).  Measured at C3
-# (profiles/r06_ab_early_gopt.json): 865.7 images/s with it, 867.7 without -- the HBM-bound update beside the latency-bound
-# mapping-network backward slows that chain by what it saves at the step boundary; off by default.
-EARLY_GOPT = os.environ.get('HG_EARLY_GOPT', '0') != '0'
 # Data parallelism: the all-reduce of G's convolution-weight gradients (83 of 99.8 M parameters at C3) starts when the
 # generator's fused backward node returns, under the rest of the backward (ddp.GradAllReduce.start_early)
 EARLY_GREDUCE = os.environ.get('HG_EARLY_GREDUCE', '1') != '0'
@@ -194,7 +185,7 @@ class _Rng:
 
 def latent_to_w(style_vectorizer, latent_descr):
     zs = [z for z, _ in latent_descr]
-    if BATCH_S and len(zs) > 1 and zs[0].is_cuda and all(z.shape == zs[0].shape for z in zs):
+    if len(zs) > 1 and zs[0].is_cuda and all(z.shape == zs[0].shape for z in zs):
         # mixed latents (90 % of the steps): the two z batches through the 8-layer mapping network as ONE batch -- rows are
         # independent, and the 16 launches it saves are serial ~15 us ones at the head of every generator forward
         ws = style_vectorizer(torch.cat(zs, dim=0)).split(zs[0].shape[0], dim=0)
@@ -245,7 +236,8 @@ class HistoGAN(nn.Module):
             device = torch.device('cuda', torch.cuda.current_device())
         self.to(device)
         # flat storage (after the move): generator side in the reference's optimizer order G, S, H (:668-670)
-        # (convolution weights first: DiffGrad.step_early updates that region while the mapping networks' backward still runs)
+        # (convolution weights first: under data parallelism that region's all-reduce starts while the mapping networks'
+        # backward still runs, _early_g_reduce)
         self._flat_g = FlatParams(conv_first(list(self.G.parameters()) + list(self.S.parameters()) + list(self.H.parameters())))
         self._flat_d = FlatParams(self.D.parameters())
         self._flat_ema = FlatParams(conv_first(list(self.GE.parameters()) + list(self.SE.parameters()) +
@@ -441,13 +433,12 @@ class Trainer():
     # ------------------------------------------------------------------------------------------
     def _g_stream(self):
         if getattr(self, '_gstream', None) is None:
-            self._gstream = torch.cuda.Stream(device=self.device, priority=G_STREAM_PRIO)
+            self._gstream = torch.cuda.Stream(device=self.device)
         return self._gstream
 
     def _w_and_hw(self, style, hist_batch):
         GAN = self.GAN
-        if (H_SIDE and hist_batch.is_cuda
-                and ((H_SIDE_GRAD and self.__dict__.get('_extra_streams_ok', True)) or not torch.is_grad_enabled())
+        if (hist_batch.is_cuda and (self.__dict__.get('_extra_streams_ok', True) or not torch.is_grad_enabled())
                 and not torch.cuda.is_current_stream_capturing()):
             # the histogram vectorizer beside the mapping network instead of behind it -- two independent chains of 8 small
             # serial GEMMs at the head of the generator forward; with autograd recording, the engine runs each chain's
@@ -529,10 +520,7 @@ class Trainer():
         (`styles_def_to_tensor(latent_to_w(S, mixed_list(...)))` of the reference, :166-189, with the launch sequence
         independent of the draw)."""
         z1, z2 = self.rng.noise(batch_size, latent_dim), self.rng.noise(batch_size, latent_dim)
-        if BATCH_S:
-            w1, w2 = self.GAN.S(torch.cat((z1, z2), dim=0)).split(batch_size, dim=0)
-        else:
-            w1, w2 = self.GAN.S(z1), self.GAN.S(z2)
+        w1, w2 = self.GAN.S(torch.cat((z1, z2), dim=0)).split(batch_size, dim=0)
         first = (torch.arange(layers, device=self.device) < tt_dev).view(1, layers, 1)
         return torch.where(first, w1[:, None, :], w2[:, None, :])
 
@@ -657,7 +645,7 @@ class Trainer():
             ddp_ok = G_OVERLAP_DDP == '1'
         else:
             ddp_ok = not ddp.ranks_share_a_device(dev)        # (collective on first use: every rank is in its first step here)
-        overlap_g = G_OVERLAP and acc == 1 and ddp_ok
+        overlap_g = acc == 1 and ddp_ok
         self._extra_streams_ok = ddp_ok       # (ranks sharing a GPU: no further streams either -- H beside S under autograd, early all-reduce)
         if overlap_g and not getattr(self, '_warn_off', False):
             # parameters live on the default stream, part of the graph now runs on another one: the engine's stream
@@ -745,8 +733,7 @@ class Trainer():
         else:
             GAN._reduce_g()
             GAN.G_opt.step()
-        if not self.__dict__.pop('_early_packed', False):
-            prepack_async(GAN._flat_g.data)    # next step's generator operands, under the head of its forward
+        prepack_async(GAN._flat_g.data)    # next step's generator operands, under the head of its forward
         mark('g_optimizer')
 
         return torch.stack([total_disc_loss, total_gen_loss, total_hist_loss, gp_val.reshape(()),
@@ -764,7 +751,7 @@ class Trainer():
                 GAN._reduce_d.finish()
                 GAN.D_opt.step()
 
-        if early is not None and D_STEP_EARLY:
+        if early is not None:
             # the update only needs D's gradients: enqueued before this stream waits for the second one, it runs under
             # the tail of the G-phase generator forward when that is still in flight
             update_d()
@@ -807,18 +794,19 @@ class Trainer():
                         gen_loss = gen_loss + pl_loss
             gen_loss = gen_loss / acc
             self._mark('g_phase_d_forward_hist_loss')
-            # at the end of the generator's fused backward node: start the all-reduce of G's convolution-weight gradients
-            # (data parallelism) or -- single process, opt-in -- update them
-            early_opt = ((EARLY_GREDUCE and self.__dict__.get('_extra_streams_ok', True) if ddp.is_dist() else EARLY_GOPT)
-                         and acc == 1 and not apply_path_penalty
-                         and not torch.cuda.is_current_stream_capturing())
-            if early_opt:
+            # data parallelism: at the end of the generator's fused backward node, start the all-reduce of G's
+            # convolution-weight gradients.  (Updating them there in a single process was measured and dropped: 865.7
+            # against 867.7 images/s without, profiles/r06_ab_early_gopt.json.)
+            early_reduce = (EARLY_GREDUCE and self.__dict__.get('_extra_streams_ok', True) and ddp.is_dist()
+                            and acc == 1 and not apply_path_penalty
+                            and not torch.cuda.is_current_stream_capturing())
+            if early_reduce:
                 from . import gfused
-                gfused.AFTER_BLOCKS = self._early_g_update
+                gfused.AFTER_BLOCKS = self._early_g_reduce
             try:
                 gen_loss.backward()
             finally:
-                if early_opt:
+                if early_reduce:
                     gfused.AFTER_BLOCKS = None
             self._mark('g_backward')
             total_gen_loss = total_gen_loss + loss.detach() / acc
@@ -900,19 +888,14 @@ class Trainer():
         self.steps += 1
         self.av = None
 
-    def _early_g_update(self):
-        """Called by the generator's fused backward node when its last convolution weight gradient is enqueued: DiffGrad on the
-        convolution-weight region of G's flat buffer and the re-pack of its operands run on a stream of their own beside the
-        rest of the backward (mapping networks, style projections); `G_opt.step()` finishes the other parameters."""
-        GAN = self.GAN
-        st = self.__dict__.get('_opt_stream')
+    def _early_g_reduce(self):
+        """Called by the generator's fused backward node when its last convolution weight gradient is enqueued (data
+        parallelism): the all-reduce of the convolution-weight region of G's flat gradient buffer starts on a stream of its
+        own beside the rest of the backward (mapping networks, style projections)."""
+        st = self.__dict__.get('_reduce_stream')
         if st is None:
-            st = self._opt_stream = torch.cuda.Stream(device=self.device)
-        if ddp.is_dist():
-            GAN._reduce_g.start_early(st)
-        elif GAN.G_opt.step_early(st):
-            with torch.cuda.stream(st):
-                self._early_packed = bool(prepack_async(GAN._flat_g.data))
+            st = self._reduce_stream = torch.cuda.Stream(device=self.device)
+        self.GAN._reduce_g.start_early(st)
 
     def _mark(self, name):
         """Phase marker of the step on the CURRENT stream (tools/phase_probe.py sets `phase_events = []`; None: no-op)."""

@@ -546,7 +546,7 @@ def _ulp(x):
 @pytest.mark.parametrize('which', ['G', 'D'])
 def test_diffgrad_and_ema_on_flat_buffers_match_fp64(which, gpu_device, record_testsuite_property):
     """FlatParams of Generator(256, 512, 16) / Discriminator(256, 16) (83 M / 91 M elements: the grid-stride loops wrap
-    ~80x), 3 DiffGrad steps: (a) one hg_diffgrad_step, (b) split at n_conv (two offset launches, as step_early + step),
+    ~80x), 3 DiffGrad steps: (a) one hg_diffgrad_step, (b) split at n_conv (two offset launches, as step_buckets does per bucket),
     (c) DiffGrad.step_buckets behind a stub reducer, (d) hg_diffgrad_step_dev fed by hg_diffgrad_step_size -- all
     bit-identical in parameters and state; (a) against oracle.histogan_nets.diffgrad_step in fp64 step by step (update
     bar in the module docstring) and over the whole run (relmax 1e-6); then ema_update against fp64."""

@@ -80,3 +80,24 @@ def test_demod_backward_formulas_equal_autograd_of_the_reference_expression():
         gy = 2.0 * s1 * (gq @ wsq)                                   # hg_demod_style_grad
         gw = 2.0 * w * (gq.t() @ (s1 * s1))[:, :, None, None]        # hg_demod_weight_term
     assert torch.allclose(gy, gy_ref, rtol=1e-10, atol=1e-12) and torch.allclose(gw, gw_ref, rtol=1e-10, atol=1e-12)
+
+
+def test_environment_switches_of_the_python_layer_are_the_documented_ones():
+    """Every HG_* variable histogan_amd/*.py reads from the environment is a row of the first table under 'Environment
+    switches' in DESIGN.md, and the other way round.  The sources are read as text (nothing is imported), so an A/B switch
+    added for an experiment shows up here until it is documented or retired."""
+    import pathlib
+    import re
+    root = pathlib.Path(__file__).resolve().parents[1]
+    read = set()
+    for src in sorted((root / 'histogan_amd').glob('*.py')):
+        read |= set(re.findall(r"""os\.environ\.get\(\s*['"](HG_[A-Z0-9_]+)['"]""", src.read_text()))
+    lines = (root / 'DESIGN.md').read_text().split('\n')
+    at = lines.index('### Environment switches')
+    first = next(i for i in range(at, len(lines)) if lines[i].startswith('|'))
+    documented = set()
+    for line in lines[first + 2:]:                   # rows of the first table (behind its header and separator)
+        if not line.startswith('|'):
+            break
+        documented |= set(re.findall(r'`(HG_[A-Z0-9_]+)`', line.split('|')[1]))
+    assert read and read == documented, (sorted(read - documented), sorted(documented - read))
