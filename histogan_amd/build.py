@@ -13,7 +13,7 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 ROOT = os.path.dirname(PKG)
-# experiment builds: HG_LIB_TAG=foo HG_CFLAGS='-DHG_BWD_WAVES=2' -> libhistogan_hip_foo.so (loaded when HG_LIB_TAG=foo)
+# experiment builds: HG_LIB_TAG=foo HG_CFLAGS='-DHG_HIST_PROBE=1' -> libhistogan_hip_foo.so (loaded when HG_LIB_TAG=foo)
 TAG = os.environ.get('HG_LIB_TAG', '')
 EXTRA = os.environ.get('HG_CFLAGS', '').split()
 LIB = os.path.join(PKG, 'libhistogan_hip' + ('_' + TAG if TAG else '') + '.so')

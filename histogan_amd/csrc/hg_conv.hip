@@ -28,36 +28,14 @@
 #include "../../include/hg_hist.h"
 #include "../../include/hg_conv.h"
 
-// tuning knobs (experiment builds: HG_CFLAGS='-DHG_CONV_MINW=3' python -m histogan_amd.build, see build.py)
-#ifndef HG_CONV_MINW
-#define HG_CONV_MINW 2   // __launch_bounds__ minimum waves per SIMD of k_conv (register budget 512 / MINW)
-#endif
-#ifndef HG_CONV_SETPRIO
-#define HG_CONV_SETPRIO 0
-#endif
-#ifndef HG_CONV_OPIPE
-#define HG_CONV_OPIPE 1  // explicit one-step-ahead operand pipeline in the MFMA loop of k_conv (+2.5 % on the generator layers)
-#endif
-#ifndef HG_CONV_KC
-#define HG_CONV_KC 4     // input channels per K chunk of the stride-1 tiles (64x64 tile: twice that); 2/4/8 measure within 3 %
-#endif
-#ifndef HG_WGRAD_TS_DBUF
-#define HG_WGRAD_TS_DBUF 0   // double-buffering the tap-split pixel-split tiles: measured no gain
-#endif
-#ifndef HG_WGRAD_TAPSPLIT
-#define HG_WGRAD_TAPSPLIT 2   // k_wgrad: the three kernel rows of a tile on three waves (1: 2x2-tile blocks only, 2: all 3x3 tiles)
-#endif
-#ifndef HG_WGRAD_PC128
-#define HG_WGRAD_PC128 1   // 128-pixel chunks for the pixel-split 3x3 weight-gradient tiles (<= 32 channels on one side)
-#endif
+// Settled tuning constants (DESIGN.md sections 8 and 11 hold the measurements).
+constexpr int kConvMinWaves = 2;   // __launch_bounds__ minimum waves per SIMD of k_conv (register budget 512 / 2; a 3-wave cap spills, -50 %)
+constexpr int kConvKC = 4;         // input channels per K chunk of the stride-1 tiles (64x64 tile: twice that); 2/4/8 measure within 3 %
 // (Rounds 3-4 built the K-split combination INSIDE k_conv three times and removed it each time: with device-scope fences
 // 53 instead of 38 ms of convolutions per step (a release / acquire pair writes back / invalidates a whole L2 on this
 // multi-XCD part); fence-free with a tile's splits on one XCD 48.5 ms per plain step against 46.1 (the finishers run
 // alone at the tail of the launch); with the splits adjacent in dispatch order 50.9 (profiles/r04_xcd_splitk.json).  The
 // two-launch form -- slabs + k_splitk_reduce -- stays.  The code is in the history: commits 547ecd1, 19f73b6.)
-#ifndef HG_CONV_BIGTILE_SPLITK
-#define HG_CONV_BIGTILE_SPLITK 2   // 128x128 tile + K split for 8x8 maps (1) and 4x4 maps (2)
-#endif
 
 namespace {
 
@@ -297,7 +275,6 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, con
     if (c + 1 < nchunks) prefetch(c + 1);
     if (c < c_begin) continue;
 
-#if HG_CONV_OPIPE
     // operand reads one MFMA step ahead (explicit two-slot pipeline): the ds_reads of step s+1 are issued before the
     // MFMAs of step s, so a wave never waits a full LDS latency between two MFMA groups
     constexpr int NS = TAPS * (KC / KS);
@@ -324,11 +301,6 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, con
     // reads of several steps and issues the weight reads just in time, behind an s_waitcnt lgkmcnt(0) per step)
     constexpr int DSN = (MT == 32 ? (TC + 1) / 2 : TC) + TP;
     __builtin_amdgcn_sched_group_barrier(0x100, DSN, 0);
-#if HG_CONV_SETPRIO > 0
-    __builtin_amdgcn_s_setprio(HG_CONV_SETPRIO);   // waves in their MFMA phase go first: the staging of other waves fills in
-#elif HG_CONV_SETPRIO < 0
-    __builtin_amdgcn_s_setprio(0);
-#endif
 #pragma unroll
     for (int s_ = 0; s_ < NS; ++s_) {
       if (s_ + 1 < NS) ldop(s_ + 1, (s_ + 1) & 1);
@@ -342,29 +314,6 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, con
       }
       __builtin_amdgcn_sched_group_barrier(0x008, TC * TP, 0);
     }
-#if HG_CONV_SETPRIO > 0
-    __builtin_amdgcn_s_setprio(0);
-#elif HG_CONV_SETPRIO < 0
-    __builtin_amdgcn_s_setprio(-(HG_CONV_SETPRIO));   // staging / barrier phases go first, so waves return to their MFMAs sooner
-#endif
-#else
-#pragma unroll
-    for (int t = 0; t < TAPS; ++t) {
-      const int toff = a.toff[t];
-#pragma unroll
-      for (int kk = 0; kk < KC / KS; ++kk) {
-        float av[TC], bv[TP];
-#pragma unroll
-        for (int i = 0; i < TC; ++i) av[i] = Ws[(t * KC + kk * KS) * NB + aoff + i * MT];
-#pragma unroll
-        for (int j = 0; j < TP; ++j) bv[j] = Xs[pixoff[j] + toff + kk * KS * g.CHS];
-#pragma unroll
-        for (int i = 0; i < TC; ++i)
-#pragma unroll
-          for (int j = 0; j < TP; ++j) acc[i][j] = M::mma(av[i], bv[j], acc[i][j]);
-      }
-    }
-#endif
   }
 
   // ---- epilogue: D[i = channel][j = pixel]; 32x32: row(i) = (r&3) + 8*(r>>2) + 4*(lane>>5), col(j) = lane&31;
@@ -448,7 +397,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, con
 }
 
 template <int WC, int WP, int TC, int TP, int TAPS, int KC, int IS, bool SM, int MT, bool FE>
-__global__ __launch_bounds__(WC *WP * 64, HG_CONV_MINW) void k_conv(const ConvArgs a) {
+__global__ __launch_bounds__(WC *WP * 64, kConvMinWaves) void k_conv(const ConvArgs a) {
   conv_body<WC, WP, TC, TP, TAPS, KC, IS, SM, MT, FE>(a, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
@@ -466,7 +415,7 @@ struct ConvArgs4 {
 // leave it as whole lines (the classes on different XCDs -- or in separate launches -- send masked partial lines to
 // memory: 1.6 TB/s on the 256^2 maps of the first discriminator block, 2.26 TB/s paired; tools/s2_dgrad_probe.py).
 template <int WC, int WP, int TC, int TP, int KC, bool SM, int MT, bool FE>
-__global__ __launch_bounds__(WC *WP * 64, HG_CONV_MINW) void k_conv_parity4(const ConvArgs4 a) {
+__global__ __launch_bounds__(WC *WP * 64, kConvMinWaves) void k_conv_parity4(const ConvArgs4 a) {
   const int cls = a.xcd_map ? (blockIdx.x >> 3) & 3 : blockIdx.x & 3;
   const int t = a.xcd_map ? (blockIdx.x >> 5) * 8 + (blockIdx.x & 7) : blockIdx.x >> 2;
   if (t >= a.tiles[cls]) return;
@@ -658,7 +607,7 @@ __global__ __launch_bounds__(WN *WK *WS *TS * 64) void k_wgrad(const WgradArgs a
   // buffer (it&1), the registers holding chunk c+1 are stored into the other buffer and re-filled with chunk c+2.
   constexpr int BUFSZ = NBW * GP + KBW * G::CHS;   // floats of one (gout + halo) buffer
   // (measured: +3..5 % for the 4-wave tiles; the pixel-split tiles (WS > 1) are faster single-buffered)
-  constexpr int NBUF = ((WS == 1 || (TS > 1 && HG_WGRAD_TS_DBUF)) && 2 * BUFSZ * 4 <= 160 * 1024) ? 2 : 1;
+  constexpr int NBUF = (WS == 1 && 2 * BUFSZ * 4 <= 160 * 1024) ? 2 : 1;
   auto store = [&](int buf) __attribute__((always_inline)) {
     float *G2 = smem + buf * BUFSZ, *X2 = G2 + NBW * GP;
     if constexpr (!SC) {
@@ -1036,7 +985,7 @@ struct ConvPlan {
 };
 
 // How many blocks per CU should a launch of `nwg` equal blocks run with?  The MFMA kernels here are resident-block
-// bound: a CU with c blocks in flight sustains e[c] of the matrix peak (measured, tools/occ_probe.py: 0.71 / 0.85 / 0.90
+// bound: a CU with c blocks in flight sustains e[c] of the matrix peak (measured, profiles/r02_occ_probe.txt: 0.71 / 0.85 / 0.90
 // for 1 / 2 / 3 blocks of the 128x128 tile), and a launch whose block count is not a multiple of (CUs x c) ends in a
 // round at low occupancy that the dispatcher also balances badly (1024 blocks at c = 3: 104 TFLOP/s, at c = 2: 134).
 constexpr size_t kLdsPerCu = 160 * 1024;
@@ -1060,14 +1009,12 @@ inline int num_cus() {
 }
 // *t_out: modelled duration of the launch in units of (one block alone on a CU at the full matrix rate)
 inline int pick_blocks_per_cu(long long nwg, int cmax, double *t_out = nullptr) {
-  static const int forced = getenv("HG_CONV_OCC") ? atoi(getenv("HG_CONV_OCC")) : 0;   // experiments: fixed cap
   static const double e[9] = {0, 0.71, 0.85, 0.90, 0.92, 0.93, 0.93, 0.93, 0.93};
   if (cmax > 8) cmax = 8;
   const double cus = (double)num_cus();
   int best = cmax;
   double best_t = 1e300;
   for (int c = cmax; c >= 1; --c) {
-    if (forced > 0 && c != (forced < cmax ? forced : cmax)) continue;
     const long long per_round = (long long)cus * c;
     const long long full = nwg / per_round, rem = nwg - full * per_round;
     double t = (double)full * c / e[c];
@@ -1113,8 +1060,8 @@ ConvPlan plan_conv(int B, int K, int N, int Hc, int Wc, int IS, int os, bool hav
   if (N <= 64 && wide256 && blocks(64, 256) >= 384) { p.tile = TILE_64x256; return p; }
   if (N > 64 && wide128) {
     const long long nb = blocks(128, 128);
-    const int nch = (K + HG_CONV_KC - 1) / HG_CONV_KC;
-    const bool may_split = HG_CONV_BIGTILE_SPLITK && big_split && have_ws && os == 1 && IS == 1;
+    const int nch = (K + kConvKC - 1) / kConvKC;
+    const bool may_split = big_split && have_ws && os == 1 && IS == 1;
     if (nb >= 256 || (may_split && nb >= 32 && nch >= 32)) {
       p.tile = TILE_128x128;
       if (may_split)
@@ -1122,11 +1069,10 @@ ConvPlan plan_conv(int B, int K, int N, int Hc, int Wc, int IS, int os, bool hav
       return p;
     }
   }
-#if HG_CONV_BIGTILE_SPLITK > 1
   // 4x4 maps (8 images per 128-pixel tile): the small-map instantiation of the 128x128 tile (larger halo bound)
   if (N > 64 && Wc == 4 && Hc == 4 && big_split && have_ws && os == 1 && IS == 1) {
     const long long nb = blocks(128, 128);
-    const int nch = (K + HG_CONV_KC - 1) / HG_CONV_KC;
+    const int nch = (K + kConvKC - 1) / kConvKC;
     if (nb >= 32 && nch >= 32) {
       int ks = (int)((512 + nb - 1) / nb);
       if (ks > nch / 8) ks = nch / 8;
@@ -1135,7 +1081,6 @@ ConvPlan plan_conv(int B, int K, int N, int Hc, int Wc, int IS, int os, bool hav
       p.tile = TILE_128x128_SM; p.ksplit = ks; return p;
     }
   }
-#endif
   p.tile = TILE_64x64;
   // pixel tiles of the 64x64 shape: images are grouped when the map is smaller than the tile
   const int tw = Wc <= 2 ? 2 : (Wc <= 4 ? 4 : (Wc <= 8 ? 8 : (Wc <= 16 ? 16 : 32)));
@@ -1143,7 +1088,7 @@ ConvPlan plan_conv(int B, int K, int N, int Hc, int Wc, int IS, int os, bool hav
   if (th > 64 / tw) th = 64 / tw;
   const int ni = 64 / (tw * th);
   const long long nblk = (long long)((Wc + tw - 1) / tw) * ((Hc + th - 1) / th) * ((B + ni - 1) / ni) * ((N + 63) / 64);
-  const int kc = IS == 2 ? 8 : 2 * HG_CONV_KC, nchunks = (K + kc - 1) / kc;
+  const int kc = IS == 2 ? 8 : 2 * kConvKC, nchunks = (K + kc - 1) / kc;
   // blocks to aim for: 1024 for the stride-1 launches (2x2 maps, 2048 channels: 103 -> 113 TFLOP/s; the kernel is small enough
   // for 4+ blocks per CU), 512 for the stride-2 forward and the four parity-class launches of the stride-2 data gradient
   // (measured slower with more, shorter blocks)
@@ -1292,8 +1237,7 @@ int launch_conv_parity4(const ConvArgs (&base)[4], const Taps (&tp)[4], int kspl
   const int ny = (a.N + NB - 1) / NB;
   if (int rc = fit_blocks_per_cu((const void *)kern, NT, tiles_sum * ny * ksplit, lds, state[fe], "k_conv_parity4")) return rc;
   // (only where the tiles alone cover the XCDs: 4 tiles x 16 channel blocks of a 4x4 map would use 4 of the 8 -- 94 -> 163 us)
-  static const bool xcd_env = !(getenv("HG_PARITY_XCD") && atoi(getenv("HG_PARITY_XCD")) == 0);
-  const bool xcd_map = xcd_env && tiles_max >= 64;
+  const bool xcd_map = tiles_max >= 64;
   a4.xcd_map = xcd_map;
   const unsigned gx = xcd_map ? (unsigned)((tiles_max + 7) / 8 * 32) : (unsigned)(4 * tiles_max);
   hipLaunchKernelGGL(kern, dim3(gx, (unsigned)ny, (unsigned)ksplit), dim3(NT), lds, st, a4);
@@ -1322,7 +1266,7 @@ inline int launch_splitk_reduce(const ConvArgs &a, int ksplit, hipStream_t st) {
 // force_ksplit > 0: the caller fixed the K split (and reduces the slabs itself); the 64x64 tile is used
 template <int TAPS, int IS>
 int dispatch_conv(ConvArgs a, const Taps &tp, void *ws, size_t ws_bytes, hipStream_t st, int force_ksplit = 0) {
-  constexpr int KC = IS == 2 ? 4 : HG_CONV_KC;
+  constexpr int KC = IS == 2 ? 4 : kConvKC;
   a.slab = (float *)ws;
   if (force_ksplit > 0) return launch_conv<2, 2, 1, 1, TAPS, 2 * KC, IS, true>(a, tp, force_ksplit, false, st);
   ConvPlan p = plan_conv(a.B, a.K, a.N, a.Hc, a.Wc, IS, a.os, ws != nullptr, true, TAPS);
@@ -1367,7 +1311,7 @@ inline int out_size(int in, int stride) { return (in - 1) / stride + 1; }  // k 
 // behind: the 16x16 tile (4x less work per pixel) and the pixel-split 32-channel tiles of the 3x3 kernel (each of the WS
 // waves of a tile only multiplies 1/WS of a chunk) -- on rows at least 8 / 16 wide, where the halo still fits one pass.
 constexpr int wgrad_chunk_pixels(int stride, int MT, int lTW, int WS, int taps) {
-  return stride == 2 ? 32 : ((MT == 16 && lTW >= 3) || (HG_WGRAD_PC128 && MT == 32 && WS > 1 && taps == 9 && lTW >= 4)) ? 128 : 64;
+  return stride == 2 ? 32 : ((MT == 16 && lTW >= 3) || (MT == 32 && WS > 1 && taps == 9 && lTW >= 4)) ? 128 : 64;
 }
 
 WgradPlan make_wgrad_plan(int B, int K, int N, int Hi, int Wi, int ksize, int stride) {
@@ -1399,11 +1343,7 @@ WgradPlan make_wgrad_plan(int B, int K, int N, int Hi, int Wi, int ksize, int st
   p.ntiles = (N + p.WN * p.MT - 1) / (p.WN * p.MT);
   const int tiles = p.ktiles * p.ntiles;
   // blocks to aim for: the tap-split 3x3 tiles are 12-wave blocks of which one fits a CU -> one round of 256
-#ifdef HG_WGRAD_TARGET
-  const int target = HG_WGRAD_TARGET;
-#else
-  const int target = (ksize == 3 && p.MT == 32 && HG_WGRAD_TAPSPLIT) ? 256 : 512;
-#endif
+  const int target = (ksize == 3 && p.MT == 32) ? 256 : 512;
   int s = (target + tiles - 1) / tiles;
   if (s > p.nchunks) s = p.nchunks;
   if (s < 1) s = 1;
@@ -1419,7 +1359,7 @@ int launch_wgrad_k(const WgradArgs &a, const WgradPlan &p, hipStream_t st) {
   constexpr int PC = wgrad_chunk_pixels(IS, MT, LTW, WS, TAPS);
   using G = CGeom<PC, LTW, TAPS == 9 ? 1 : 0, IS>;
   size_t lds = ((size_t)WN * MT * (PC + 1) + (size_t)WK * MT * G::CHS) * sizeof(float);
-  if ((WS == 1 || (TS > 1 && HG_WGRAD_TS_DBUF)) && 2 * lds <= 160 * 1024) lds *= 2;   // double buffered (NBUF in k_wgrad)
+  if (WS == 1 && 2 * lds <= 160 * 1024) lds *= 2;   // double buffered (NBUF in k_wgrad)
   if (a.gw != nullptr && WS == 1 && MT == 32 && TAPS == 9) {   // room for the store transpose of the single-slab case
     const size_t need = (size_t)WN * WK * 32 * WG_TP * sizeof(float);
     if (need > lds) lds = need;
@@ -1445,15 +1385,12 @@ int launch_wgrad_g(const WgradArgs &a, const WgradPlan &p, hipStream_t st) {
     if (p.MT == 16) return launch_wgrad_k<1, 1, 4, TAPS, LTW, IS, 16>(a, p, st);
   }
   if (p.WN == 2 && p.WK == 2) {
-#if HG_WGRAD_TAPSPLIT
     if constexpr (TAPS == 9) {
       return launch_wgrad_k<2, 2, 1, TAPS, LTW, IS, 32, 3>(a, p, st);   // kernel rows split over waves
     }
-#endif
     return launch_wgrad_k<2, 2, 1, TAPS, LTW, IS>(a, p, st);
   }
   if constexpr (IS == 1) {
-#if HG_WGRAD_TAPSPLIT > 1
     if constexpr (TAPS == 9) {
       if (a.gw == nullptr) {
         if (p.WN == 2) return launch_wgrad_k<2, 1, 2, TAPS, LTW, IS, 32, 3>(a, p, st);
@@ -1461,15 +1398,12 @@ int launch_wgrad_g(const WgradArgs &a, const WgradPlan &p, hipStream_t st) {
         return launch_wgrad_k<1, 1, 4, TAPS, LTW, IS, 32, 3>(a, p, st);
       }
     }
-#endif
     if (p.WN == 2) return launch_wgrad_k<2, 1, 2, TAPS, LTW, IS>(a, p, st);
     if (p.WK == 2) return launch_wgrad_k<1, 2, 2, TAPS, LTW, IS>(a, p, st);
   }
-#if HG_WGRAD_TAPSPLIT > 1
   if constexpr (TAPS == 9 && IS == 2) {
     if (a.gw == nullptr) return launch_wgrad_k<1, 1, 4, TAPS, LTW, IS, 32, 3>(a, p, st);
   }
-#endif
   return launch_wgrad_k<1, 1, 4, TAPS, LTW, IS>(a, p, st);
 }
 
@@ -1564,8 +1498,8 @@ int hg_conv2d_plan(int32_t B, int32_t K, int32_t N, int32_t Hi, int32_t Wi, int3
   if (dgrad && stride != 1) return HG_EUNSUPPORTED;   // four parity-class launches: no single plan
   const int Hc = dgrad ? Hi : out_size(Hi, stride), Wc = dgrad ? Wi : out_size(Wi, stride);
   const ConvPlan p = plan_conv(B, K, N, Hc, Wc, dgrad ? 1 : stride, 1, true, true, ksize * ksize);
-  const bool k2 = ksize == 3 && stride == 1 && HG_CONV_KC == 4 && short_k_chunks(p, B, N, Hc, Wc);
-  const int base_kc = (dgrad ? 1 : stride) == 2 ? 4 : HG_CONV_KC;
+  const bool k2 = ksize == 3 && stride == 1 && short_k_chunks(p, B, N, Hc, Wc);
+  const int base_kc = (dgrad ? 1 : stride) == 2 ? 4 : kConvKC;
   out[0] = (int32_t)p.tile;
   out[1] = p.ksplit;
   out[2] = p.tile == TILE_16x256 ? 4 : (p.tile == TILE_64x64 ? 2 * base_kc : (k2 ? 2 : base_kc));
@@ -1697,28 +1631,26 @@ int hg_conv2d_dgrad(const float *gout, const float *wt, float *gin, const float 
             ++t.n;
           }
     }
-  static const int merge4 = getenv("HG_DGRAD_S2_MERGE") ? atoi(getenv("HG_DGRAD_S2_MERGE")) : 2;
-  if (merge4 >= 2 && !plan64 && Hi > 1 && Wi > 1) {
+  if (!plan64 && Hi > 1 && Wi > 1) {
     // large maps: the four classes in one launch as well, for the cache-line pairing of k_conv_parity4's block order
     const ConvPlan p = plan_conv(B, K, N, Hi / 2, Wi / 2, 1, 2, false, false, 4);   // (the smallest class)
     int rc = HG_EUNSUPPORTED;
     switch (p.tile) {
       case TILE_16x256: rc = launch_conv_parity4<1, 4, 1, 4, 4, false, 16, false>(ca, tps, 1, st); break;
-      case TILE_32x256: rc = launch_conv_parity4<1, 4, 1, 2, HG_CONV_KC, false, 32, false>(ca, tps, 1, st); break;
-      case TILE_64x256: rc = launch_conv_parity4<1, 4, 2, 2, HG_CONV_KC, false, 32, false>(ca, tps, 1, st); break;
-      case TILE_128x128: rc = launch_conv_parity4<2, 2, 2, 2, HG_CONV_KC, false, 32, false>(ca, tps, 1, st); break;
+      case TILE_32x256: rc = launch_conv_parity4<1, 4, 1, 2, kConvKC, false, 32, false>(ca, tps, 1, st); break;
+      case TILE_64x256: rc = launch_conv_parity4<1, 4, 2, 2, kConvKC, false, 32, false>(ca, tps, 1, st); break;
+      case TILE_128x128: rc = launch_conv_parity4<2, 2, 2, 2, kConvKC, false, 32, false>(ca, tps, 1, st); break;
       default: break;
     }
     if (rc != HG_EUNSUPPORTED) return rc;
   }
-  if (merge4 && plan64) {
+  if (plan64) {
     // small maps (the 64x64 tile): the four classes in one launch
     // (one launch has the blocks of all four classes: half the K split planned per class fills the chip as well, with
     // half the slab traffic -- measured best of 1 / 2 / 4)
-    static const int ksdiv = getenv("HG_DGRAD_S2_KSDIV") ? atoi(getenv("HG_DGRAD_S2_KSDIV")) : 2;
-    if (ksplit > 1) ksplit = ksplit / ksdiv > 1 ? ksplit / ksdiv : 1;
+    if (ksplit > 1) ksplit = ksplit / 2 > 1 ? ksplit / 2 : 1;
     for (int c = 0; c < 4; ++c) ca[c].slab = (float *)workspace;
-    const int rc = launch_conv_parity4<2, 2, 1, 1, 2 * HG_CONV_KC, true>(ca, tps, ksplit > 1 ? ksplit : 1, st);
+    const int rc = launch_conv_parity4<2, 2, 1, 1, 2 * kConvKC, true>(ca, tps, ksplit > 1 ? ksplit : 1, st);
     if (rc) return rc;
   } else {
     for (int c = 0; c < 4; ++c) {

@@ -22,7 +22,6 @@
 // loads + neighbour shuffles), LP lanes per plane and pass, 256 / LP planes per block on the small maps (4x4: 4 lanes per
 // plane, 64 planes per block -- the one-block-per-plane kernels it replaces ran 65 536 workgroups of 4 ... 16 live lanes
 // there); on the large maps a plane is split into chunks (grid y) whose partial sums the finish kernel adds in fixed order.
-#include <cstdlib>
 #include "hg_common.h"
 #include "../../include/hg_hist.h"
 #include "../../include/hg_nets.h"
@@ -265,8 +264,8 @@ inline Geom geom(long long planes, int H, int up) {
   g.yblocks = (int)((planes + g.PB - 1) / g.PB);
   g.chunks = 1;
   if (g.LP == 256) {      // large maps: split a plane so that the launch has ~2048 blocks, each with >= 4 passes
-    static const long long target = [] { const char *e = getenv("HG_GSTAGE_BLOCKS"); return e && atoll(e) > 0 ? atoll(e) : 2048LL; }();
-    long long c = (target + planes - 1) / planes;
+    constexpr long long kBlockTarget = 2048;
+    long long c = (kBlockTarget + planes - 1) / planes;
     const long long cmax = (V + 1023) / 1024;
     if (c > cmax) c = cmax;
     if (c > 64) c = 64;

@@ -32,36 +32,14 @@
 
 #define HG_VERSION_NUM 103   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight
 
-#ifndef HG_FWD_SCHED_GROUPS
-#define HG_FWD_SCHED_GROUPS 1
-#endif
-#ifndef HG_FWD_VALU_PER_MFMA
-#define HG_FWD_VALU_PER_MFMA 4
-#endif
-#ifndef HG_FWD_PACKED
-#define HG_FWD_PACKED 1   // packed-fp32 (v_pk_*) operand generation in k_hist_fwd
-#endif
-#ifndef HG_FWD_SHARE_ASM
-#define HG_FWD_SHARE_ASM 1   // shared-reciprocal operand generation of k_hist_fwd as one block of packed instructions
-#endif
-#ifndef HG_FWD_MFMA_GROUP
-#define HG_FWD_MFMA_GROUP 12  // k_hist_fwd at configs[1]: groups of 1: 505 us, 3: 498, 6: 473, 12: 465
-#endif
-#ifndef HG_BWD_SCHED_GROUPS
-#define HG_BWD_SCHED_GROUPS 1
-#endif
-#ifndef HG_BWD_MFMA_GROUP
-#define HG_BWD_MFMA_GROUP 1   // k_hist_bwd K loop: MFMAs per group between the VALU work of the next step (1: round 2's 1 : 2 interleave)
-#endif
-#ifndef HG_BWD_SCHED_BARRIER
-#define HG_BWD_SCHED_BARRIER 1
-#endif
-#ifndef HG_BWD_WAVES
-#define HG_BWD_WAVES 2  // min waves/SIMD the backward kernel is register-budgeted for
-#endif
-#if HG_BWD_WAVES > 2
-#error "HG_BWD_WAVES > 2: the shared-reciprocal assembly of k_hist_bwd clobbers v[240:255] (needs the 256-VGPR budget)"
-#endif
+// Settled schedule constants of the dense kernels (DESIGN.md sections 4 and 11 hold the measurements).
+constexpr int kFwdMfmaGroup = 12;    // k_hist_fwd at configs[1]: groups of 1: 505 us, 3: 498, 6: 473, 12: 465
+constexpr int kFwdValuPerMfma = 4;   // VALU slots the scheduler may place behind each MFMA of a forward group
+constexpr int kBwdMfmaGroup = 1;     // k_hist_bwd K loop: MFMAs per group between the VALU work of the next step (round 2's 1 : 2 interleave)
+// min waves/SIMD the backward kernel is register-budgeted for: its shared-reciprocal assembly clobbers v[240:255], which
+// needs the 256-VGPR budget, so this cannot go above 2
+constexpr int kBwdWaves = 2;
+static_assert(kBwdWaves <= 2, "the shared-reciprocal assembly of k_hist_bwd clobbers v[240:255] (needs the 256-VGPR budget)");
 
 #ifndef HG_HIST_PROBE
 #define HG_HIST_PROBE 0      // 1 (tagged experiment builds only): per-phase shader-cycle counters in k_hist_fwd / k_hist_bwd
@@ -338,12 +316,6 @@ __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const fl
     const f32x2 den = __builtin_elementwise_fma(t, t, one);
     return f32x2{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
   };
-  // denominators 1 + t^2 of the two tiles of one variable (no reciprocal yet)
-  auto den2 = [&](float u, const f32x2 &chi, const f32x2 &clo) __attribute__((always_inline)) -> f32x2 {
-    const f32x2 uu = {u, u}, is = {P.inv_sigma, P.inv_sigma}, one = {1.f, 1.f};
-    const f32x2 t = __builtin_elementwise_fma(uu, is, chi) + clo;
-    return __builtin_elementwise_fma(t, t, one);
-  };
   auto make_ops = [&](const f32x4 &q, Ops<T> &o) {
     if constexpr (SHARE) {
       // Shared reciprocals (round 4; PMC: profiles/r04_hist_pmc_stalls.txt).  fp32 MFMA and VALU instructions share
@@ -353,7 +325,6 @@ __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const fl
       // of 6 v_rcp + 2.  Each value picks up ~3 roundings instead of 1 (<= 2e-7 relative; the parity bars are 1e-5).
       // The launcher takes this instantiation only when (1 + t_max^2)^4 stays far below the fp32 range.
       static_assert(T == 2 && METHOD == HG_METHOD_INVERSE_QUADRATIC && SYM && DIAG && !GREEN, "shared-reciprocal path");
-#if HG_FWD_SHARE_ASM
       // Written as ONE block of packed instructions: clang 22 "unpacks" v_pk_* instructions that follow an MFMA into two
       // scalar ones (a peephole meant for the 16-bit MFMAs, whose shadow hides VALU work) -- on the fp32 MFMA, which
       // shares the fp32 lanes with the VALU, that doubles their cost.  20 VALU instructions + 2 v_rcp_f32 per K step;
@@ -387,22 +358,11 @@ __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const fl
           : "=&v"(a0), "=&v"(a2), "=&v"(b0), "=&v"(b1)
           : "v"(qxy), "v"(qzw), "s"(is2), "v"(chiA), "v"(cloA), "v"(chiAm), "v"(cloAm), "v"(chiB), "v"(cloB)
           : "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255");
-#else
-      const f32x2 da = den2(q.x, chiA, cloA), db = den2(q.y, chiAm, cloAm), dc = den2(q.z, chiB, cloB);
-      const f32x2 pab = da * db;                                    // (a0 b0, a1 b1)
-      const float r4 = __builtin_amdgcn_rcpf(pab.x * pab.y);
-      const f32x2 rab = f32x2{pab.y, pab.x} * f32x2{r4, r4};        // (1/(a0 b0), 1/(a1 b1))
-      const f32x2 wr = rab * f32x2{q.w, q.w};
-      const f32x2 a0 = db * wr, a2 = da * wr;                       // w ka, w kb
-      const f32x2 b0 = da * rab;                                    // kb
-      const float r2 = __builtin_amdgcn_rcpf(dc.x * dc.y);
-      const f32x2 b1 = f32x2{dc.y, dc.x} * f32x2{r2, r2};           // kc
-#endif
       o.A0[0] = a0.x; o.A0[1] = a0.y; o.A1[0] = a0.x; o.A1[1] = a0.y; o.A2[0] = a2.x; o.A2[1] = a2.y;
       o.B0[0] = b0.x; o.B0[1] = b0.y; o.B1[0] = b1.x; o.B1[1] = b1.y; o.B2[0] = b1.x; o.B2[1] = b1.y;
       return;
     }
-    if constexpr (T == 2 && METHOD == HG_METHOD_INVERSE_QUADRATIC && HG_FWD_PACKED) {
+    if constexpr (T == 2 && METHOD == HG_METHOD_INVERSE_QUADRATIC) {
       const f32x2 w2 = {q.w, q.w};
       const f32x2 ka = iq2(q.x, chiA, cloA), kbA = iq2(q.y, chiAm, cloAm);
       const f32x2 a0 = w2 * ka, a2 = w2 * kbA;
@@ -462,7 +422,7 @@ __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const fl
     const f32x4 *srow = reinterpret_cast<const f32x4 *>(stage) + wave * kFwdStage + half;
     auto kstep = [&](const Ops<T> &use, Ops<T> &gen, const f32x4 &qn, f32x4 &qf, int mf) __attribute__((always_inline)) {
       qf = srow[2 * mf];                                   // {a, b, c, weight}; broadcast per half-wave
-      if constexpr (!(SHARE && HG_FWD_SHARE_ASM)) make_ops(qn, gen);
+      if constexpr (!SHARE) make_ops(qn, gen);
 #pragma unroll
       for (int ti = 0; ti < T; ++ti)
 #pragma unroll
@@ -471,7 +431,7 @@ __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const fl
           acc[1][ti][tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(use.A1[ti], use.B1[tj], acc[1][ti][tj], 0, 0, 0);
           if (!green) acc[2][ti][tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(use.A2[ti], use.B2[tj], acc[2][ti][tj], 0, 0, 0);
         }
-      if constexpr (SHARE && HG_FWD_SHARE_ASM) {
+      if constexpr (SHARE) {
         // the LDS read, the 12 MFMAs as one group, then the operand block of the next step: nothing crosses the fences
         __builtin_amdgcn_sched_barrier(0);
         make_ops(qn, gen);
@@ -479,19 +439,17 @@ __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const fl
         asm volatile("" : "+v"(qf));
         return;
       }
-#if HG_FWD_SCHED_GROUPS
-      // MFMAs in groups of HG_FWD_MFMA_GROUP with the operand generation of the next step between the groups.  On
+      // MFMAs in groups of kFwdMfmaGroup with the operand generation of the next step between the groups.  On
       // gfx950 the fp32 MFMA does not hide VALU work (same issue path: tools/ubench/mfma_valu_overlap.hip -- 3 VALU
       // instructions per MFMA cost 0.79 of peak interleaved 1:3 and 0.86 as 6 MFMAs : 18 VALU), so what is left to
       // schedule is the number of MFMA <-> VALU switches.
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      constexpr int NM = (green ? 1 : 3) * T * T, GRP = HG_FWD_MFMA_GROUP < NM ? HG_FWD_MFMA_GROUP : NM;
+      constexpr int NM = (green ? 1 : 3) * T * T, GRP = kFwdMfmaGroup < NM ? kFwdMfmaGroup : NM;
 #pragma unroll
       for (int i = 0; i < NM; i += GRP) {
         __builtin_amdgcn_sched_group_barrier(0x008, GRP, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, HG_FWD_VALU_PER_MFMA * GRP, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, kFwdValuPerMfma * GRP, 0);
       }
-#endif
       // pin: qf is complete here (after a step's worth of MFMA issue) -- as ONE 128-bit tuple, so that the packed
       // operand generation can address its halves in place (op_sel) instead of through copies
       asm volatile("" : "+v"(qf));
@@ -634,7 +592,7 @@ __device__ __forceinline__ constexpr int beta0(int s) { return (s & 3) + 8 * ((s
 //   dL/da = Iy * sum_i k'(a-b_i) Wa[i]   (same for b, c),   dL/dIy = 1/2 sum_i (ka Wa + kb Wb + kc Wc)[i]
 //   dL_R = da+db, dL_G = -da+dc, dL_B = -db-dc,   dx_c = dL_c/(x_c+1e-6) + dIy x_c/Iy   
 template <int T, int METHOD, bool GREEN, bool SHARE = false, bool WGT = false>
-__global__ __launch_bounds__(256, HG_BWD_WAVES) void k_hist_bwd(const DevParams P, const float *__restrict__ x,
+__global__ __launch_bounds__(256, kBwdWaves) void k_hist_bwd(const DevParams P, const float *__restrict__ x,
                                                                 const float *__restrict__ gout,
                                                                 const float *__restrict__ hist,
                                                                 const float *__restrict__ sums,
@@ -920,20 +878,18 @@ __global__ __launch_bounds__(256, HG_BWD_WAVES) void k_hist_bwd(const DevParams 
         W[0][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.A[rt][4], cur.kc, W[0][rt], 0, 0, 0);
         W[2][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.A[rt][5], cur.ka, W[2][rt], 0, 0, 0);
       }
-#if HG_BWD_SCHED_GROUPS
-      // all LDS operand reads of the next step first, then the MFMAs in groups of HG_BWD_MFMA_GROUP with the next step's
+      // all LDS operand reads of the next step first, then the MFMAs in groups of kBwdMfmaGroup with the next step's
       // address arithmetic / kernel evaluations between the groups (fp32 MFMA and VALU issue exclude each other on gfx950:
       // what the schedule controls is the number of MFMA <-> VALU switches)
       __builtin_amdgcn_sched_group_barrier(0x100, 6 * T, 0);
       {
-        constexpr int NM = (green ? 2 : 6) * T, GRP = HG_BWD_MFMA_GROUP < NM ? HG_BWD_MFMA_GROUP : NM;
+        constexpr int NM = (green ? 2 : 6) * T, GRP = kBwdMfmaGroup < NM ? kBwdMfmaGroup : NM;
 #pragma unroll
         for (int i = 0; i < NM; i += GRP) {
           __builtin_amdgcn_sched_group_barrier(0x008, GRP, 0);
           __builtin_amdgcn_sched_group_barrier(0x002, 2 * GRP, 0);
         }
       }
-#endif
       // pin: the next step's operands are complete here, after a step's worth of MFMA issue; without
       // it the compiler rotates the loop and every MFMA waits on an LDS read issued just before it
 #pragma unroll
@@ -984,9 +940,7 @@ __global__ __launch_bounds__(256, HG_BWD_WAVES) void k_hist_bwd(const DevParams 
               is2 += kw2;
               gs2[v] = __builtin_elementwise_fma(t2[j] * kq[j], kw2, gs2[v]);
             }
-#if HG_BWD_SCHED_BARRIER
             if ((s & 7) == 4) __builtin_amdgcn_sched_barrier(0);
-#endif
           }
         } else
 #pragma unroll
@@ -1006,9 +960,7 @@ __global__ __launch_bounds__(256, HG_BWD_WAVES) void k_hist_bwd(const DevParams 
           is2 += kw2;
           if constexpr (METHOD == HG_METHOD_INVERSE_QUADRATIC) gs2[v] = __builtin_elementwise_fma(t2 * k2, kw2, gs2[v]);
           else gs2[v] = __builtin_elementwise_fma(t2, kw2, gs2[v]);
-#if HG_BWD_SCHED_BARRIER
           if ((s & 7) == 6) __builtin_amdgcn_sched_barrier(0);  // keep the re-evaluations from being hoisted en bloc
-#endif
         }
         gsum[v] = gs2[v].x + gs2[v].y;
       }
@@ -1156,14 +1108,12 @@ __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, c
           Wu[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.Au[rt], cur.kv, Wu[rt], 0, 0, 0);
           Wv[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.Av[rt], cur.ku, Wv[rt], 0, 0, 0);
         }
-#if HG_BWD_SCHED_GROUPS
         __builtin_amdgcn_sched_group_barrier(0x100, 2 * RT, 0);
 #pragma unroll
         for (int i = 0; i < 2 * RT; ++i) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
           __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
         }
-#endif
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) asm volatile("" : "+v"(nxt.Au[rt]), "+v"(nxt.Av[rt]));
         cur = nxt;
@@ -1198,9 +1148,7 @@ __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, c
           } else {
             gu2 = __builtin_elementwise_fma(tu, kwu, gu2); gv2 = __builtin_elementwise_fma(tv, kwv, gv2);
           }
-#if HG_BWD_SCHED_BARRIER
           if ((s & 7) == 6) __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         gu = gu2.x + gu2.y; gv = gv2.x + gv2.y; isum = is2.x + is2.y;
       }
@@ -2201,6 +2149,9 @@ inline int bwd_planes_rt(const hg_hist_params *p, int nbd) {
   return want ? (p->h + 31) / 32 : 0;
 }
 
+// workgroup target of the dense forward / backward pixel split (profiles/r04_hist_wgs_sweep.txt: 512 ... 2048 swept, 512 best)
+constexpr long long kDenseWgTarget = 512;
+
 Plan make_plan(const hg_hist_params *p) {
   Plan pl;
   pl.T = (p->h <= 32) ? 1 : 2;
@@ -2211,10 +2162,8 @@ Plan make_plan(const hg_hist_params *p) {
   const int P = (p->green_only || p->projection) ? 1 : 3;
   // forward: aim at ~2 workgroups per CU (256 CUs), >= 64 pixels per wave
   const long long wg_fixed = (long long)p->B * pl.nbd * pl.nbd;
-  long long target = 512;
   // the scatter kernel keeps up to 98 KB of LDS grids: one workgroup per CU is all that fits, more only add slabs
-  if (sparse_path(p)) target = 256;
-  if (const char *e = getenv("HG_FWD_WGS")) target = atoll(e) > 0 ? atoll(e) : target;  // tuning knob
+  const long long target = sparse_path(p) ? 256 : kDenseWgTarget;
   long long S = (target + wg_fixed - 1) / wg_fixed;
   const long long maxS = (npix + 255) / 256;
   if (S > maxS) S = maxS;
@@ -2232,9 +2181,7 @@ Plan make_plan(const hg_hist_params *p) {
   pl.part_bytes = ((size_t)p->B * S * pl.nbd * pl.nbd * sizeof(double) + 255) / 256 * 256;
   // backward: 1 workgroup per CU, rounds of 32 pixels per wave
   const long long rounds_total = (npix + 31) / 32;
-  long long targetb = 512;
-  if (const char *e = getenv("HG_BWD_WGS")) targetb = atoll(e) > 0 ? atoll(e) : targetb;  // tuning knob
-  long long Sb = (targetb + p->B - 1) / p->B;
+  long long Sb = (kDenseWgTarget + p->B - 1) / p->B;
   const long long maxSb = (rounds_total + 3) / 4;
   if (Sb > maxSb) Sb = maxSb;
   if (Sb < 1) Sb = 1;
@@ -2283,7 +2230,7 @@ DevParams make_dev(const hg_hist_params *p) {
 
 // The shared-reciprocal operand generation of k_hist_fwd forms products of four denominators 1 + t^2, |t| <= (13.9 +
 // max|boundary|) / sigma (log-chroma differences of clamped pixels lie in [-13.82, 13.82]): taken only when that product
-// stays below 1e30 (its reciprocal then is a normal float with room to spare).  HG_FWD_SHARE_RCP=0 switches it off (A/B).
+// stays below 1e30 (its reciprocal then is a normal float with room to spare).
 // (the kernels also evaluate the PADDED bins of a 32-wide tile, up to index 32 * ceil(h / 32) - 1 >= h - 1: the bound
 // takes the farthest padded bin centre lo + (padded - 1) * step, not only the boundary)
 static double share_rcp_tmax(const DevParams &d) {
@@ -2295,15 +2242,12 @@ static double share_rcp_tmax(const DevParams &d) {
 }
 
 bool fwd_share_rcp_ok(const DevParams &d) {
-  static const bool enabled = [] { const char *e = getenv("HG_FWD_SHARE_RCP"); return !(e && e[0] == '0'); }();
-  if (!enabled || d.proj != HG_PROJ_RGBUV) return false;
+  if (d.proj != HG_PROJ_RGBUV) return false;
   const double tmax = share_rcp_tmax(d), den = 1.0 + tmax * tmax;
   return den * den * den * den < 1e30;
 }
 
-bool bwd_share_rcp_ok(const DevParams &d) {      // the same product-of-four-denominators condition; HG_BWD_SHARE_RCP=0: A/B
-  static const bool enabled = [] { const char *e = getenv("HG_BWD_SHARE_RCP"); return !(e && e[0] == '0'); }();
-  if (!enabled) return false;
+bool bwd_share_rcp_ok(const DevParams &d) {      // the same product-of-four-denominators condition
   const double tmax = share_rcp_tmax(d), den = 1.0 + tmax * tmax;
   return den * den * den * den < 1e30;
 }

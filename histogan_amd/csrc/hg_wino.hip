@@ -24,10 +24,6 @@
 #include "../../include/hg_conv.h"
 #include "../../include/hg_wino.h"
 
-#ifndef HG_WINO_BPIPE
-#define HG_WINO_BPIPE 1
-#endif
-
 namespace {
 
 constexpr unsigned kOOB = 0xFFFFFFFFu;
@@ -219,7 +215,6 @@ __global__ __launch_bounds__(512) void k_wino(const WinoArgs a) {
   auto mfma_chunk = [&](int buf, auto SET) __attribute__((always_inline)) {
     constexpr int S = decltype(SET)::value;
     const float *Vc = smem + buf * VSZ + lk * TB + lm;
-#if HG_WINO_BPIPE
     // B operands one MFMA step ahead (the two-slot pipeline of k_conv, hg_conv.hip): the LDS read of step s + 1 is issued in
     // front of the MFMAs of step s.  The compiler's own order reads a step's operands right in front of its MFMAs, into the A
     // registers the previous step released: a full LDS round trip per group of TC x TP MFMAs, exposed whenever the SIMD's
@@ -246,21 +241,6 @@ __global__ __launch_bounds__(512) void k_wino(const WinoArgs a) {
       if (st + 1 < STEPS) __builtin_amdgcn_sched_group_barrier(0x100, DSN, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, TC * TP, 0);
     }
-#else
-#pragma unroll
-    for (int x2 = 0; x2 < 2; ++x2)
-#pragma unroll
-      for (int ks = 0; ks < KC / 2; ++ks) {
-        float bv[TP];
-#pragma unroll
-        for (int j = 0; j < TP; ++j) bv[j] = Vc[((2 * wave + x2) * KC + 2 * ks) * TB + 32 * j];
-#pragma unroll
-        for (int i = 0; i < TC; ++i)
-#pragma unroll
-          for (int j = 0; j < TP; ++j)
-            acc[x2][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[S][x2][ks * TC + i], bv[j], acc[x2][i][j], 0, 0, 0);
-      }
-#endif
   };
   auto clampc = [&](int c) __attribute__((always_inline)) { return c < c_end ? c : c_end - 1; };
 #define HG_WINO_BARRIER()               \
@@ -635,17 +615,6 @@ __global__ __launch_bounds__(512) void k_wino_wgrad(const WinoWgArgs a) {
   const unsigned m_tx0 = dtx == 0 ? kOOB : 0u, m_txl = dtx == PWm ? kOOB : 0u;
   const unsigned m_kbad = k0 + ch < K ? 0u : kOOB, m_nbad = n0 + ch < N ? 0u : kOOB;
   // patch element (r, c) relative to the chunk origin, against a base one row and one column BEFORE the image group
-#if HG_WINO_ROWLOAD
-  // one dword-aligned 16-byte load per patch row (as k_wino): the padding columns of border tiles arrive as neighbours'
-  // values and are cleared with the chunk's column masks when the patch is transformed; the one row that would begin
-  // one element before the tensor (image 0, channel 0, row 0, left border) is loaded from column 0 and shifted
-  unsigned vo[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) vo[r] = (unsigned)(((dimg * K + k0 + ch) * H + 2 * dty + r) * W + 2 * dtx) * 4u;
-  const unsigned m_first = (dimg == 0 && k0 + ch == 0 && dty == 0 && dtx == 0) ? kOOB : 0u;
-  const size_t in_elems = (size_t)a.B * K * HW;
-  unsigned cmask[2][3];      // [register set][left column, right column, shifted row 1]
-#else
   unsigned vo[4][3];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -654,7 +623,6 @@ __global__ __launch_bounds__(512) void k_wino_wgrad(const WinoWgArgs a) {
     vo[r][1] = (e + 1u) * 4u;
     vo[r][2] = (e + 3u) * 4u;
   }
-#endif
   const unsigned go = (unsigned)(((dimg * N + n0 + ch) * H + 2 * dty) * W + 2 * dtx) * 4u;
 
   f32x16 acc[2][2][2];
@@ -686,19 +654,6 @@ __global__ __launch_bounds__(512) void k_wino_wgrad(const WinoWgArgs a) {
     rm[0] = base | (top & m_row0);
     rm[1] = rm[2] = base;
     rm[3] = base | (bot & m_rowl);
-#if HG_WINO_ROWLOAD
-    // (the descriptor ends with the tensor: the last row's 16-byte load reaches one element past it)
-    const size_t rem = in_elems - (size_t)b0 * K * HW + (size_t)(W + 1);
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.in + (size_t)b0 * K * HW - (W + 1), rem < (1ull << 30) ? (unsigned)rem * 4u : kOOB);
-    const unsigned shm = (b0 == 0 && rg == 0 && cg == 0) ? m_first : 0u;
-    cmask[S][0] = c0; cmask[S][1] = c3; cmask[S][2] = shm;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const f32x4 m = buf_load4(rx, (vo[r] + (r == 1 ? (shm & 4u) : 0u)) | rm[r], (int)soff);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) pd[S][4 * r + e] = m[e];
-    }
-#else
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.in + (size_t)b0 * K * HW - (W + 1));
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -708,7 +663,6 @@ __global__ __launch_bounds__(512) void k_wino_wgrad(const WinoWgArgs a) {
       pd[S][4 * r + 2] = m[1];
       pd[S][4 * r + 3] = buf_load(rx, vo[r][2] | rm[r] | c3, (int)soff);
     }
-#endif
     const unsigned gm = m_nbad | m_img;
     const f32x2 g0 = buf_load2(rg_, go | gm, (int)soff);
     const f32x2 g1 = buf_load2(rg_, (go + (unsigned)W * 4u) | gm, (int)soff);
@@ -722,20 +676,6 @@ __global__ __launch_bounds__(512) void k_wino_wgrad(const WinoWgArgs a) {
     float d[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) d[e] = pd[S][e];
-#if HG_WINO_ROWLOAD
-    {
-      const bool sh = cmask[S][2] != 0u;
-      const float m0 = d[4], m1 = d[5], m2 = d[6];
-      d[5] = sh ? m0 : m1;
-      d[6] = sh ? m1 : m2;
-      d[7] = sh ? m2 : d[7];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        d[4 * r] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, d[4 * r]) & ~cmask[S][0]);
-        d[4 * r + 3] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, d[4 * r + 3]) & ~cmask[S][1]);
-      }
-    }
-#endif
     float q[16];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -1027,9 +967,8 @@ int hg_wino_supported(int32_t B, int32_t K, int32_t N, int32_t H, int32_t W) {
   // measured against the direct kernel at the C3 shapes (tools/wino_probe.py, profiles/r05_wino_probe_v5.txt): both variants
   // win from 32 input channels on -- the 64-channel variant 1.27x at 32 -> 64 and 1.5-2.2x from 64 up, the 32-channel variant
   // (twice the transform work per MFMA) 1.15-1.23x at 32 -> 32 and 1.38x at 64 -> 32 @256^2; 16 -> 32 loses (0.8-0.93x)
-  static const int min_k0 = getenv("HG_WINO_MIN_K") ? atoi(getenv("HG_WINO_MIN_K")) : 32;
-  static const int min_k1 = getenv("HG_WINO_MIN_K1") ? atoi(getenv("HG_WINO_MIN_K1")) : 32;
-  if (K < (p.variant ? min_k1 : min_k0)) return 0;
+  constexpr int kMinK = 32;
+  if (K < kMinK) return 0;
   return p.blocks * p.ksplit >= num_cus() / 2;
 }
 
@@ -1087,8 +1026,7 @@ int hg_wino_conv2d(const float *in, const float *u, float *out, const float *isc
   a.tiles_w = p.tiles_w; a.tiles_h = p.tiles_h; a.bt_x = p.bt_x; a.bt_y = p.bt_y;
   a.ksplit = p.ksplit; a.slab = (float *)workspace;
   a.blocks = (int)p.blocks; a.total_tiles = (int)(p.blocks * p.ksplit);
-  static const int xcd = getenv("HG_WINO_XCD") ? atoi(getenv("HG_WINO_XCD")) : 1;
-  a.xcd = xcd && p.nblk > 1 && p.nblk < 8 && (p.blocks / p.nblk) % 8 == 0;
+  a.xcd = p.nblk > 1 && p.nblk < 8 && (p.blocks / p.nblk) % 8 == 0;
   hipStream_t st = (hipStream_t)stream;
   const bool fe = iscale != nullptr;
   int rc = p.variant == 0 ? launch_wino<2, 2, 8>(a, p, fe, st) : launch_wino<1, 4, 4>(a, p, fe, st);
@@ -1116,9 +1054,8 @@ int hg_wino_wgrad_supported(int32_t B, int32_t K, int32_t N, int32_t H, int32_t 
   // 64 x 64 channel tiles: a layer with fewer channels on a side multiplies padding (and the transforms, done once per
   // 64 x 64 tile, stop amortising: 0.75x at 32 -> 64); 2x2 maps are slab traffic rather than arithmetic (0.84-0.95x);
   // measured 1.25-1.9x elsewhere (tools/wino_probe.py, profiles/r05_wino_probe_v5.txt)
-  static const int min_c = getenv("HG_WINO_WG_MIN_C") ? atoi(getenv("HG_WINO_WG_MIN_C")) : 64;
-  static const int min_s = getenv("HG_WINO_WG_MIN_S") ? atoi(getenv("HG_WINO_WG_MIN_S")) : 4;
-  if (K < min_c || N < min_c || H < min_s || W < min_s) return 0;
+  constexpr int kMinChannels = 64, kMinSide = 4;
+  if (K < kMinChannels || N < kMinChannels || H < kMinSide || W < kMinSide) return 0;
   return p.nchunks / p.splits >= 4;
 }
 
@@ -1144,8 +1081,7 @@ int hg_wino_wgrad(const float *in, const float *gout, float *gw, int32_t B, int3
     attr[dev] = true;
   }
   a.xtiles = p.ktiles * p.ntiles; a.total_blocks = a.xtiles * p.splits;
-  static const int xcd = getenv("HG_WINO_XCD") ? atoi(getenv("HG_WINO_XCD")) : 1;
-  a.xcd = xcd && p.splits % 8 == 0;
+  a.xcd = p.splits % 8 == 0;
   static const int persist = getenv("HG_WINO_PERSIST") ? atoi(getenv("HG_WINO_PERSIST")) : 1;
   const int grid = persist && a.total_blocks > num_cus() ? num_cus() : a.total_blocks;
   hipLaunchKernelGGL(k_wino_wgrad, dim3((unsigned)grid), dim3(512), lds, st, a);

@@ -101,3 +101,28 @@ def test_environment_switches_of_the_python_layer_are_the_documented_ones():
             break
         documented |= set(re.findall(r'`(HG_[A-Z0-9_]+)`', line.split('|')[1]))
     assert read and read == documented, (sorted(read - documented), sorted(documented - read))
+
+
+def test_switches_of_the_hip_sources_are_the_documented_ones():
+    """Every getenv("HG_...") name and every HG_... name a preprocessor conditional tests (#if, #ifdef, #ifndef, #elif:
+    with or without a default block) in histogan_amd/csrc/ is a row of the table under 'Launcher knobs and build flags' in
+    DESIGN.md, and the other way round.  The sources are read as text, so a knob added for an experiment shows up here
+    until it is documented or retired."""
+    import pathlib
+    import re
+    root = pathlib.Path(__file__).resolve().parents[1]
+    read = set()
+    for src in sorted(p for p in (root / 'histogan_amd' / 'csrc').iterdir() if p.suffix in ('.hip', '.h')):
+        text = src.read_text()
+        read |= set(re.findall(r'getenv\(\s*"(HG_[A-Z0-9_]+)"', text))
+        for cond in re.findall(r'^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$', text, re.M):
+            read |= set(re.findall(r'\bHG_[A-Z0-9_]+\b', cond))
+    lines = (root / 'DESIGN.md').read_text().split('\n')
+    at = lines.index('### Launcher knobs and build flags')
+    first = next(i for i in range(at, len(lines)) if lines[i].startswith('|'))
+    documented = set()
+    for line in lines[first + 2:]:                   # rows of the table (behind its header and separator)
+        if not line.startswith('|'):
+            break
+        documented |= set(re.findall(r'`(HG_[A-Z0-9_]+)`', line.split('|')[1]))
+    assert read and read == documented, (sorted(read - documented), sorted(documented - read))
