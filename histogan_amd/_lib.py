@@ -6,6 +6,8 @@ importing this module raises, and every op built on it is unusable.
 import ctypes
 import os
 
+import torch  # before the library is loaded, so that libamdhip64.so.7 resolves to the runtime torch uses
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _TAG = os.environ.get('HG_LIB_TAG', '')  # experiment builds only (histogan_amd/build.py)
 LIB_PATH = os.path.join(_PKG, 'libhistogan_hip' + ('_' + _TAG if _TAG else '') + '.so')
@@ -50,8 +52,6 @@ def _load():
         raise ImportError(
             f'{LIB_PATH} not found: the gfx950 HIP library has not been built. '
             f'Run `python -m histogan_amd.build` (needs hipcc). There is no CPU/PyTorch fallback.')
-    # torch must be imported first so that libamdhip64.so.7 resolves to the runtime torch uses
-    import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     vp, sz, i32, i64, f32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
     PP = ctypes.POINTER(HgHistParams)
@@ -247,7 +247,7 @@ def check(rc, what):
 
 
 # ---- cheap host-side plumbing (the train step makes ~1 500 C-ABI calls; each microsecond here is 1.5 ms per step) ------
-class _NullCtx:
+class NullCtx:
     def __enter__(self):
         return self
 
@@ -255,13 +255,12 @@ class _NullCtx:
         return False
 
 
-_NULL = _NullCtx()
+_NULL = NullCtx()
 
 
 def on_device(device):
     """`with torch.cuda.device(device)` only when `device` is not already current (the context manager costs two driver
     calls; one process drives one GPU, so this is almost always the no-op)."""
-    import torch
     idx = device.index
     if idx is None or idx == torch.cuda.current_device():
         return _NULL
@@ -270,6 +269,32 @@ def on_device(device):
 
 def raw_stream(device):
     """The caller's current HIP stream on `device` as the void* the C ABI takes."""
-    import torch
     idx = device.index if device.index is not None else torch.cuda.current_device()
     return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(idx))
+
+
+def stream_of(t):
+    """raw_stream of the tensor's device."""
+    return raw_stream(t.device)
+
+
+def f32c(t):
+    """`t` as the kernels read it: detached, float32, contiguous (the same storage when it already is both)."""
+    t = t.detach()
+    t = t if t.dtype == torch.float32 else t.float()
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def need_gpu(t, what, found='tensor on {}'):
+    """Raise unless `t` is a tensor on the GPU.  found: the module's wording of what it got instead ({}: the device)."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f'{what}: {found.format(getattr(t, "device", None))}; the MI355X-native path has no CPU implementation')
+
+
+def workspace(nbytes, device):
+    """Scratch of `nbytes` (what a *_workspace_bytes call returned), never empty: the launchers refuse a NULL workspace."""
+    return torch.empty(max(nbytes, 4), dtype=torch.uint8, device=device)

@@ -12,8 +12,7 @@ from random import random
 import torch
 from torch import nn
 
-from ._lib import check, lib, on_device, raw_stream
-from .ops import _f32c, _need_gpu, _st
+from ._lib import check, f32c, lib, need_gpu, on_device, stream_of, workspace
 
 NP = 9                                    # HG_AUG_NP
 _ID = (0, 0, 0, 0, 0, 1, 0, 1, 0)         # identity row: no flip/roll/shift, empty cutout (r0 > r1)
@@ -22,13 +21,13 @@ _ID = (0, 0, 0, 0, 0, 1, 0, 1, 0)         # identity row: no flip/roll/shift, em
 class _Spatial(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, params, adjoint):
-        _need_gpu(x, 'DiffAugment')
-        x = _f32c(x.detach())
+        need_gpu(x, 'DiffAugment')
+        x = f32c(x)
         B, C, H, W = x.shape
         with on_device(x.device):
             out = torch.empty_like(x)
             check(lib.hg_augment_spatial(x.data_ptr(), params.data_ptr(), out.data_ptr(), B, C, H, W, int(adjoint),
-                                         _st(x)), 'hg_augment_spatial')
+                                         stream_of(x)), 'hg_augment_spatial')
         ctx.params, ctx.adjoint = params, adjoint
         return out
 
@@ -40,22 +39,22 @@ class _Spatial(torch.autograd.Function):
 def _sample_mean(x):
     B = x.shape[0]
     n = lib.hg_augment_workspace_bytes(B)
-    ws = torch.empty(max(n, 4), dtype=torch.uint8, device=x.device)
+    ws = workspace(n, x.device)
     mean = torch.empty(B, dtype=torch.float32, device=x.device)
-    check(lib.hg_sample_mean(x.data_ptr(), mean.data_ptr(), B, x[0].numel(), ws.data_ptr(), n, _st(x)), 'hg_sample_mean')
+    check(lib.hg_sample_mean(x.data_ptr(), mean.data_ptr(), B, x[0].numel(), ws.data_ptr(), n, stream_of(x)), 'hg_sample_mean')
     return mean
 
 
 class _Color(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, color, adjoint):
-        _need_gpu(x, 'DiffAugment')
-        x = _f32c(x.detach())
+        need_gpu(x, 'DiffAugment')
+        x = f32c(x)
         B, C, H, W = x.shape
         with on_device(x.device):
             out = torch.empty_like(x)
             check(lib.hg_augment_color(x.data_ptr(), _sample_mean(x).data_ptr(), color.data_ptr(), out.data_ptr(), B, C,
-                                       H * W, int(adjoint), _st(x)), 'hg_augment_color')
+                                       H * W, int(adjoint), stream_of(x)), 'hg_augment_color')
         ctx.color, ctx.adjoint = color, adjoint
         return out
 

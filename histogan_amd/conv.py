@@ -16,7 +16,8 @@ import weakref
 
 import torch
 
-from ._lib import check, lib, on_device, raw_stream
+from ._lib import check, f32c, lib, on_device, ptr, raw_stream, stream_of, workspace
+from .launch import channel_sum
 
 PACK_FWD, PACK_DGRAD = 0, 1
 _skip_wgrad = False
@@ -56,7 +57,7 @@ def _wino_pack(w, mode):
         return False
     with on_device(w.device):
         u = torch.empty(n, dtype=torch.float32, device=w.device)
-        check(lib.hg_wino_pack_weights(w.data_ptr(), u.data_ptr(), Co, Ci, mode, _st(w)), 'hg_wino_pack_weights')
+        check(lib.hg_wino_pack_weights(w.data_ptr(), u.data_ptr(), Co, Ci, mode, stream_of(w)), 'hg_wino_pack_weights')
     return u
 
 
@@ -83,9 +84,9 @@ def wino_conv(x, u, N, iscale=None, oscale=None, bias=None, noise_w=None, noise_
         out = torch.empty((B, N, H, W), dtype=torch.float32, device=x.device)
         nb = lib.hg_wino_workspace_bytes(B, K, N, H, W)
         ws = torch.empty(nb, dtype=torch.uint8, device=x.device) if nb else None
-        check(lib.hg_wino_conv2d(x.data_ptr(), u.data_ptr(), out.data_ptr(), _ptr(iscale), _ptr(oscale), _ptr(bias),
-                                 _ptr(noise_w), _ptr(noise_img), noise_S, float(slope), _ptr(addend), B, K, N, H, W,
-                                 _ptr(ws), nb, _st(x)), 'hg_wino_conv2d')
+        check(lib.hg_wino_conv2d(x.data_ptr(), u.data_ptr(), out.data_ptr(), ptr(iscale), ptr(oscale), ptr(bias),
+                                 ptr(noise_w), ptr(noise_img), noise_S, float(slope), ptr(addend), B, K, N, H, W,
+                                 ptr(ws), nb, stream_of(x)), 'hg_wino_conv2d')
     return out
 
 
@@ -101,9 +102,9 @@ def modconv_fwd_packed(x, wt, N, ksize, iscale=None, oscale=None, bias=None, noi
         out = torch.empty((B, N, H, W), dtype=torch.float32, device=x.device)
         nb = lib.hg_conv2d_workspace_bytes(B, K, N, H, W, ksize, 1, 0)
         ws = torch.empty(nb, dtype=torch.uint8, device=x.device) if nb else None
-        check(lib.hg_modconv2d_fwd(x.data_ptr(), _direct_operand(wt).data_ptr(), out.data_ptr(), _ptr(iscale), _ptr(oscale), _ptr(bias),
-                                   _ptr(noise_w), _ptr(noise_img), noise_S, float(slope), B, K, N, H, W, ksize, _ptr(ws), nb,
-                                   _st(x)), 'hg_modconv2d_fwd')
+        check(lib.hg_modconv2d_fwd(x.data_ptr(), _direct_operand(wt).data_ptr(), out.data_ptr(), ptr(iscale), ptr(oscale), ptr(bias),
+                                   ptr(noise_w), ptr(noise_img), noise_S, float(slope), B, K, N, H, W, ksize, ptr(ws), nb,
+                                   stream_of(x)), 'hg_modconv2d_fwd')
     return out
 
 
@@ -118,20 +119,6 @@ def input_grads_only():
         yield
     finally:
         _skip_wgrad = old
-
-
-def _st(t):
-    return raw_stream(t.device)
-
-
-def _f32c(t):
-    t = t.detach()
-    t = t if t.dtype == torch.float32 else t.float()
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _out_size(n, stride):
@@ -165,7 +152,6 @@ def enable_pack_cache(params=None):
     and drops every registration.  Registration is ADDITIVE (a HistoGAN Trainer and a recoloring Trainer built side by
     side -- the reference CLI does that -- both keep their entries) and holds only a weak reference to the parameter:
     entries of a freed model are dropped on lookup, so a later tensor allocated at the same address cannot hit them."""
-    import weakref
     if params is None:
         _cache.clear()
         _cacheable.clear()
@@ -292,7 +278,7 @@ def _direct_operand(wt):
             raise RuntimeError('direct convolution operand requested for a weight that no longer exists')
         Co, Ci, k, _ = p.shape
         with on_device(p.device):
-            check(lib.hg_conv_pack_weights(p.data_ptr(), wt.data_ptr(), Co, Ci, k, mode, _st(p)), 'hg_conv_pack_weights')
+            check(lib.hg_conv_pack_weights(p.data_ptr(), wt.data_ptr(), Co, Ci, k, mode, stream_of(p)), 'hg_conv_pack_weights')
         wt.direct_stale = False
         _direct_needed.add(key)
         if p.is_cuda and not torch.cuda.is_current_stream_capturing():
@@ -441,7 +427,7 @@ def _pack_both(w):
     with on_device(w.device):
         wf = torch.empty(lib.hg_conv_packed_elems(Co, Ci, k, PACK_FWD), dtype=torch.float32, device=w.device)
         wd = torch.empty(lib.hg_conv_packed_elems(Co, Ci, k, PACK_DGRAD), dtype=torch.float32, device=w.device)
-        check(lib.hg_conv_pack_weights_both(w.data_ptr(), wf.data_ptr(), wd.data_ptr(), Co, Ci, k, _st(w)),
+        check(lib.hg_conv_pack_weights_both(w.data_ptr(), wf.data_ptr(), wd.data_ptr(), Co, Ci, k, stream_of(w)),
               'hg_conv_pack_weights_both')
     if k == 3:
         wf.wino_src = wd.wino_src = w      # Winograd operands: packed by the first launch that takes them (_wino_u)
@@ -455,7 +441,7 @@ def _pack_weights(w, mode):
         raise ValueError(f'conv weights {tuple(w.shape)}: only square 1x1 / 3x3 kernels are implemented')
     with on_device(w.device):
         wt = torch.empty(n, dtype=torch.float32, device=w.device)
-        check(lib.hg_conv_pack_weights(w.data_ptr(), wt.data_ptr(), Co, Ci, k, mode, _st(w)), 'hg_conv_pack_weights')
+        check(lib.hg_conv_pack_weights(w.data_ptr(), wt.data_ptr(), Co, Ci, k, mode, stream_of(w)), 'hg_conv_pack_weights')
     if k == 3:
         wt.wino_src = w
     return wt
@@ -472,8 +458,8 @@ def conv_fwd_packed(x, wt, N, ksize, stride=1, iscale=None, oscale=None, bias=No
         out = torch.empty((B, N, _out_size(H, stride), _out_size(W, stride)), dtype=torch.float32, device=x.device)
         nb = lib.hg_conv2d_workspace_bytes(B, K, N, H, W, ksize, stride, 0)
         ws = torch.empty(nb, dtype=torch.uint8, device=x.device) if nb else None
-        check(lib.hg_conv2d_fwd(x.data_ptr(), _direct_operand(wt).data_ptr(), out.data_ptr(), _ptr(iscale), _ptr(oscale), _ptr(bias),
-                                B, K, N, H, W, ksize, stride, _ptr(ws), nb, _st(x)), 'hg_conv2d_fwd')
+        check(lib.hg_conv2d_fwd(x.data_ptr(), _direct_operand(wt).data_ptr(), out.data_ptr(), ptr(iscale), ptr(oscale), ptr(bias),
+                                B, K, N, H, W, ksize, stride, ptr(ws), nb, stream_of(x)), 'hg_conv2d_fwd')
     return out
 
 
@@ -490,22 +476,22 @@ def conv_fwd_add_packed(x, wt, N, ksize, addend, bias=None, stride=1):
             raise ValueError(f'conv2d_add: addend {tuple(addend.shape)} does not match the output {tuple(out.shape)}')
         nb = lib.hg_conv2d_workspace_bytes(B, K, N, H, W, ksize, stride, 0)
         ws = torch.empty(nb, dtype=torch.uint8, device=x.device) if nb else None
-        check(lib.hg_conv2d_fwd_add(x.data_ptr(), _direct_operand(wt).data_ptr(), out.data_ptr(), addend.data_ptr(), _ptr(bias),
-                                    B, K, N, H, W, ksize, stride, _ptr(ws), nb, _st(x)), 'hg_conv2d_fwd_add')
+        check(lib.hg_conv2d_fwd_add(x.data_ptr(), _direct_operand(wt).data_ptr(), out.data_ptr(), addend.data_ptr(), ptr(bias),
+                                    B, K, N, H, W, ksize, stride, ptr(ws), nb, stream_of(x)), 'hg_conv2d_fwd_add')
     return out
 
 
 def lrelu_bwd_channel_sum(g, out, slope, want_sum=True):
     """(g * (out > 0 ? 1 : slope), its per-channel sum or None) in one pass (hg_lrelu_bwd_channel_sum)."""
-    g, out = _f32c(g), _f32c(out)
+    g, out = f32c(g), f32c(out)
     B, C, H, W = g.shape
     with on_device(g.device):
         gm = torch.empty_like(g)
         cs = torch.empty(C, dtype=torch.float32, device=g.device) if want_sum else None
         nb = lib.hg_nets_workspace_bytes(B, C, H, W)
-        ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=g.device)
-        check(lib.hg_lrelu_bwd_channel_sum(g.data_ptr(), out.data_ptr(), float(slope), gm.data_ptr(), _ptr(cs), B, C, H * W,
-                                           ws.data_ptr(), ws.numel(), _st(g)), 'hg_lrelu_bwd_channel_sum')
+        ws = workspace(nb, g.device)
+        check(lib.hg_lrelu_bwd_channel_sum(g.data_ptr(), out.data_ptr(), float(slope), gm.data_ptr(), ptr(cs), B, C, H * W,
+                                           ws.data_ptr(), ws.numel(), stream_of(g)), 'hg_lrelu_bwd_channel_sum')
     return gm, cs
 
 
@@ -520,8 +506,8 @@ def conv_dgrad_packed(g, wt, N, H, W, ksize, stride=1, iscale=None, oscale=None)
         gin = torch.empty((B, N, H, W), dtype=torch.float32, device=g.device)
         nb = lib.hg_conv2d_workspace_bytes(B, K, N, H, W, ksize, stride, 1)
         ws = torch.empty(nb, dtype=torch.uint8, device=g.device) if nb else None
-        check(lib.hg_conv2d_dgrad(g.data_ptr(), _direct_operand(wt).data_ptr(), gin.data_ptr(), _ptr(iscale), _ptr(oscale),
-                                  B, K, N, H, W, ksize, stride, _ptr(ws), nb, _st(g)), 'hg_conv2d_dgrad')
+        check(lib.hg_conv2d_dgrad(g.data_ptr(), _direct_operand(wt).data_ptr(), gin.data_ptr(), ptr(iscale), ptr(oscale),
+                                  B, K, N, H, W, ksize, stride, ptr(ws), nb, stream_of(g)), 'hg_conv2d_dgrad')
     return gin
 
 
@@ -535,15 +521,15 @@ def conv_wgrad(x, gout, ksize, stride=1, iscale=None, gscale=None, out=None):
             nbytes = lib.hg_wino_wgrad_workspace_bytes(B, K, N, H, W)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
             gw = out if out is not None else torch.empty((N, K, 3, 3), dtype=torch.float32, device=x.device)
-            check(lib.hg_wino_wgrad(x.data_ptr(), gout.data_ptr(), gw.data_ptr(), B, K, N, H, W, ws.data_ptr(), nbytes, _st(x)),
+            check(lib.hg_wino_wgrad(x.data_ptr(), gout.data_ptr(), gw.data_ptr(), B, K, N, H, W, ws.data_ptr(), nbytes, stream_of(x)),
                   'hg_wino_wgrad')
         return gw
     with on_device(x.device):
         nbytes = lib.hg_conv2d_wgrad_workspace_bytes(B, K, N, H, W, ksize, stride)
-        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=x.device)
+        ws = workspace(nbytes, x.device)
         gw = out if out is not None else torch.empty((N, K, ksize, ksize), dtype=torch.float32, device=x.device)
-        check(lib.hg_conv2d_wgrad(x.data_ptr(), gout.data_ptr(), gw.data_ptr(), _ptr(iscale), _ptr(gscale),
-                                  B, K, N, H, W, ksize, stride, ws.data_ptr(), ws.numel(), _st(x)), 'hg_conv2d_wgrad')
+        check(lib.hg_conv2d_wgrad(x.data_ptr(), gout.data_ptr(), gw.data_ptr(), ptr(iscale), ptr(gscale),
+                                  B, K, N, H, W, ksize, stride, ws.data_ptr(), ws.numel(), stream_of(x)), 'hg_conv2d_wgrad')
     return gw
 
 
@@ -564,7 +550,6 @@ _side_streams = {}   # device index -> torch.cuda.Stream
 def register_grad_slots(flat):
     """Called by FlatParams: convolution weights (4-d parameters) of `flat` may receive their gradient directly.
     Only a weak reference to the owner is kept (a dead owner's entries are dropped on lookup)."""
-    import weakref
     ref = weakref.ref(flat)
     off = 0
     for p in flat.params:
@@ -622,7 +607,7 @@ def _direct_wgrad(w, x, g, stride):
     if not getattr(flat, 'direct_ok', False):       # between zero_grad() and gather() only
         return False
     slot = flat.grad[off:off + n].view(w.shape)
-    xc, gc = _f32c(x), _f32c(g)
+    xc, gc = f32c(x), f32c(g)
     if _batch_pieces(xc, w, stride) != 1:
         return False
     skey = slot.data_ptr()
@@ -668,7 +653,7 @@ def direct_demod_weight_term(w, gd, d, s1):
         return False
     slot = flat.grad[off:off + n].view(w.shape)
     skey = slot.data_ptr()
-    gd, d, s1 = _f32c(gd), _f32c(d), _f32c(s1)
+    gd, d, s1 = f32c(gd), f32c(d), f32c(s1)
     B, N = d.shape
     K, taps = w.shape[1], w.shape[2] * w.shape[3]
 
@@ -703,8 +688,8 @@ class _Conv(torch.autograd.Function):
             raise ValueError(f'conv2d: x {tuple(x.shape)} does not match w {tuple(w.shape)}')
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.has_bias = stride, bias is not None
-        xc, wc = _f32c(x), _f32c(w)
-        bc = None if bias is None else _f32c(bias)
+        xc, wc = f32c(x), f32c(w)
+        bc = None if bias is None else f32c(bias)
         return conv_fwd_packed(xc, pack_weights(wc, PACK_FWD), w.shape[0], w.shape[2], stride, bias=bc)
 
     @staticmethod
@@ -720,7 +705,6 @@ class _Conv(torch.autograd.Function):
                 if torch.is_grad_enabled():     # higher-order pass: keep the sum on the autograd tape
                     gb = g.sum(dim=(0, 2, 3))
                 else:
-                    from .ops import channel_sum
                     gb = channel_sum(g)
         return gx, gw, gb, None
 
@@ -733,7 +717,7 @@ class _ConvDgrad(torch.autograd.Function):
         _check_args(g, w, stride)
         ctx.save_for_backward(g, w)
         ctx.stride = stride
-        gc, wc = _f32c(g), _f32c(w)
+        gc, wc = f32c(g), f32c(w)
         return conv_dgrad_packed(gc, pack_weights(wc, PACK_DGRAD), w.shape[1], H, W, w.shape[2], stride)
 
     @staticmethod
@@ -756,7 +740,7 @@ class _ConvWgrad(torch.autograd.Function):
             raise RuntimeError('conv2d: no CPU implementation')
         ctx.save_for_backward(g, x)
         ctx.stride = stride
-        return conv_wgrad(_f32c(x), _f32c(g), ksize, stride)
+        return conv_wgrad(f32c(x), f32c(g), ksize, stride)
 
     @staticmethod
     def backward(ctx, ggw):
@@ -780,11 +764,11 @@ class _ConvLrelu(torch.autograd.Function):
         _check_args(x, w, stride)
         if x.shape[1] != w.shape[1]:
             raise ValueError(f'conv2d: x {tuple(x.shape)} does not match w {tuple(w.shape)}')
-        xc, wc = _f32c(x), _f32c(w)
+        xc, wc = f32c(x), f32c(w)
         B, K, H, W = xc.shape
         N, k = w.shape[0], w.shape[2]
         wt = pack_weights(wc, PACK_FWD)
-        bc = None if bias is None else _f32c(bias)
+        bc = None if bias is None else f32c(bias)
         if stride != 1:
             raise ValueError('conv2d_lrelu: stride 1 only')
         out = modconv_fwd_packed(xc, wt, N, k, bias=bc, slope=slope)
@@ -823,9 +807,9 @@ class _ConvAdd(torch.autograd.Function):
             raise ValueError(f'conv2d: x {tuple(x.shape)} does not match w {tuple(w.shape)}')
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.has_bias = stride, bias is not None
-        xc, wc = _f32c(x), _f32c(w)
-        bc = None if bias is None else _f32c(bias)
-        return conv_fwd_add_packed(xc, pack_weights(wc, PACK_FWD), w.shape[0], w.shape[2], _f32c(addend), bc, stride)
+        xc, wc = f32c(x), f32c(w)
+        bc = None if bias is None else f32c(bias)
+        return conv_fwd_add_packed(xc, pack_weights(wc, PACK_FWD), w.shape[0], w.shape[2], f32c(addend), bc, stride)
 
     @staticmethod
     def backward(ctx, g):
@@ -840,7 +824,6 @@ class _ConvAdd(torch.autograd.Function):
                 if torch.is_grad_enabled():
                     gb = g.sum(dim=(0, 2, 3))
                 else:
-                    from .ops import channel_sum
                     gb = channel_sum(g)
         return gx, gw, gb, (g if ctx.needs_input_grad[3] else None), None
 

@@ -18,6 +18,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from ._lib import NullCtx
+
 # HG_DIST_FORCE=1: take the data-parallel code paths (broadcasts, gradient / statistics / Hellinger all-reduces) whenever
 # a process group exists, even at world size 1 -- lets a 1-GPU box run the whole step through RCCL (tests/test_bench_gpu.py)
 FORCE = os.environ.get('HG_DIST_FORCE', '0') == '1'
@@ -113,14 +115,6 @@ def _avg_in_collective():
 BUCKETS = max(1, int(os.environ.get('HG_DDP_BUCKETS', '4')))
 
 
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
 class GradAllReduce:
     """Averaging all-reduce of a flat gradient buffer in `chunks` contiguous buckets, asynchronous: `start()` launches all
     of them in order, `wait(i)` makes the current stream wait for bucket i only (`ranges[i]` = its element range),
@@ -161,7 +155,7 @@ class GradAllReduce:
         self.ranges = early + (self._split(hi, n, max(1, self.chunks // 2)) if n > hi else [])
         g = f.grad
         avg = _avg_in_collective()
-        ctx = torch.cuda.stream(stream) if dev.type == 'cuda' else _NullCtx()
+        ctx = torch.cuda.stream(stream) if dev.type == 'cuda' else NullCtx()
         with ctx:
             if not avg:
                 g[:hi].mul_(1.0 / world_size())

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import HgHistParams, check, lib, on_device, raw_stream
+from ._lib import HgHistParams, check, lib, need_gpu, on_device, raw_stream, workspace
 
 _IDX_CACHE = {}
 
@@ -107,20 +107,15 @@ def _ws_bytes(p):
     return f.value, b.value
 
 
-def _stream(device):
-    return raw_stream(device)
-
-
-def _require_gpu(x, what):
-    if not x.is_cuda:
-        raise RuntimeError(f'{what}: input is on {x.device}; the MI355X-native path has no CPU implementation')
+_FOUND = 'input is on {}'     # need_gpu's wording here
+_stream = raw_stream           # the former name, still bound: the C-ABI tests of the weighted histogram reach it
 
 
 class RGBuvHistFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg, pre_relu=False, weight=None):
         # weight: None or a map already validated by rgbuv_hist (check_weight): fp32 (B, H, W) on x's device, no grad
-        _require_gpu(x, 'RGBuvHistFunction')
+        need_gpu(x, 'RGBuvHistFunction', _FOUND)
         x = x.detach()
         if x.dtype != torch.float32:
             x = x.float()
@@ -140,9 +135,9 @@ class RGBuvHistFunction(torch.autograd.Function):
             P = 1 if (cfg.green_only or cfg.projection != 'rgbuv') else 3
             out = torch.empty((p.B, P, cfg.h, cfg.h), dtype=torch.float32, device=x.device)
             sums = torch.empty((p.B,), dtype=torch.float32, device=x.device)
-            ws = torch.empty((max(fwd_b, 4),), dtype=torch.uint8, device=x.device)
+            ws = workspace(fwd_b, x.device)
             check(lib.hg_rgbuv_hist_fwd(ctypes.byref(p), x.data_ptr(), out.data_ptr(), sums.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), _stream(x.device)), 'hg_rgbuv_hist_fwd')
+                                        ws.data_ptr(), ws.numel(), raw_stream(x.device)), 'hg_rgbuv_hist_fwd')
         ctx.cfg = cfg
         ctx.save_for_backward(x, out, sums)
         ctx._keep = keep
@@ -162,10 +157,10 @@ class RGBuvHistFunction(torch.autograd.Function):
         g = g.contiguous()
         with on_device(x.device):
             gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-            ws = torch.empty((max(bwd_b, 4),), dtype=torch.uint8, device=x.device)
+            ws = workspace(bwd_b, x.device)
             check(lib.hg_rgbuv_hist_bwd(ctypes.byref(p), x.data_ptr(), g.data_ptr(), out.data_ptr(),
                                         sums.data_ptr(), gx.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        _stream(x.device)), 'hg_rgbuv_hist_bwd')
+                                        raw_stream(x.device)), 'hg_rgbuv_hist_bwd')
         return gx, None, None, None
 
 
@@ -209,7 +204,7 @@ def rgbuv_hist(x, cfg, pre_relu=False, weight=None):
 class HellingerFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, target, gen, alpha):
-        _require_gpu(gen, 'HellingerFunction')
+        need_gpu(gen, 'HellingerFunction', _FOUND)
         t = target.detach().float().contiguous()
         g = gen.detach().float().contiguous()
         if t.shape != g.shape:
@@ -222,7 +217,7 @@ class HellingerFunction(torch.autograd.Function):
             ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
             check(lib.hg_hellinger_fwd_bwd(t.data_ptr(), g.data_ptr(), n, g.shape[0], float(alpha),
                                            loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), wsb,
-                                           _stream(g.device)), 'hg_hellinger_fwd_bwd')
+                                           raw_stream(g.device)), 'hg_hellinger_fwd_bwd')
         ctx.save_for_backward(grad)
         return loss
 

@@ -9,70 +9,30 @@ import ctypes
 
 import torch
 
-from ._lib import check, lib, on_device, raw_stream
+from . import conv as C
+from . import launch
+from ._lib import GlinLayer, check, f32c, lib, need_gpu, on_device, raw_stream, workspace
 
 
 SKINNY_SPLIT = os.environ.get('HG_SKINNY_SPLIT', '1') != '0'   # _skinny_mm: chunked bmm + sum (0: plain mm)
 
-
-def _st(t):
-    return raw_stream(t.device)
-
-
-def _f32c(t):
-    t = t if t.dtype == torch.float32 else t.float()
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _ws(t, B, C, H, W):
-    n = lib.hg_nets_workspace_bytes(B, C, H, W)
-    return torch.empty(max(n, 4), dtype=torch.uint8, device=t.device), n
-
-
-def channel_sum(g):
-    """(B, C, H, W) -> (C): sum over batch and pixels (bias gradient), deterministic two-stage reduction."""
-    g = _f32c(g.detach())
-    B, C, H, W = g.shape
-    with on_device(g.device):
-        out = torch.empty(C, dtype=torch.float32, device=g.device)
-        ws, n = _ws(g, B, C, H, W)
-        check(lib.hg_channel_sum(g.data_ptr(), out.data_ptr(), B, C, H * W, ws.data_ptr(), n, _st(g)), 'hg_channel_sum')
-    return out
-
-
-def _need_gpu(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f'{what}: tensor on {t.device}; the MI355X-native path has no CPU implementation')
+channel_sum = launch.channel_sum
 
 
 class _Modulate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, s, upsample):
-        _need_gpu(x, 'modulate')
-        x = _f32c(x.detach())
-        s = None if s is None else _f32c(s.detach())
-        B, C, H, W = x.shape
-        f = 2 if upsample else 1
-        with on_device(x.device):
-            out = torch.empty((B, C, H * f, W * f), dtype=torch.float32, device=x.device)
-            check(lib.hg_modulate_fwd(x.data_ptr(), None if s is None else s.data_ptr(), out.data_ptr(),
-                                      B, C, H, W, int(upsample), _st(x)), 'hg_modulate_fwd')
+        need_gpu(x, 'modulate')
+        x = f32c(x)
+        s = None if s is None else f32c(s)
         ctx.save_for_backward(x, s)
         ctx.upsample = bool(upsample)
-        return out
+        return launch.modulate_fwd(x, s, upsample)
 
     @staticmethod
     def backward(ctx, g):
         x, s = ctx.saved_tensors
-        g = _f32c(g.detach())
-        B, C, H, W = x.shape
-        with on_device(x.device):
-            gx = torch.empty_like(x)
-            gs = None if s is None else torch.empty_like(s)
-            ws, n = _ws(x, B, C, H, W)
-            check(lib.hg_modulate_bwd(g.data_ptr(), x.data_ptr(), None if s is None else s.data_ptr(),
-                                      gx.data_ptr(), None if gs is None else gs.data_ptr(), B, C, H, W,
-                                      int(ctx.upsample), ws.data_ptr(), n, _st(x)), 'hg_modulate_bwd')
+        gx, gs = launch.modulate_bwd(f32c(g), x, s, ctx.upsample)
         return gx, gs, None
 
 
@@ -86,22 +46,20 @@ def upsample2x(x):
     return _Modulate.apply(x, None, True)
 
 
+def _square(t):
+    if t.shape[2] != t.shape[3]:
+        raise ValueError('square feature maps only (the noise permute of the reference needs H == W)')
+
+
 class _DemodNoiseLrelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, conv, d, nzt, wn, bn):
-        _need_gpu(conv, 'demod_noise_lrelu')
-        conv = _f32c(conv.detach())
-        d = None if d is None else _f32c(d.detach())
-        nzt, wn, bn = _f32c(nzt.detach()), _f32c(wn.detach().reshape(-1)), _f32c(bn.detach())
-        B, O, H, W = conv.shape
-        if H != W:
-            raise ValueError('square feature maps only (the noise permute of the reference needs H == W)')
-        S = nzt.shape[-1]
-        with on_device(conv.device):
-            out = torch.empty_like(conv)
-            check(lib.hg_demod_noise_lrelu_fwd(conv.data_ptr(), None if d is None else d.data_ptr(), nzt.data_ptr(),
-                                               wn.data_ptr(), bn.data_ptr(), out.data_ptr(), B, O, H, S, _st(conv)),
-                  'hg_demod_noise_lrelu_fwd')
+        need_gpu(conv, 'demod_noise_lrelu')
+        conv = f32c(conv)
+        d = None if d is None else f32c(d)
+        nzt = f32c(nzt)
+        _square(conv)
+        out = launch.dnl_fwd(conv, d, nzt, f32c(wn.detach().reshape(-1)), f32c(bn))
         # The convolution output is kept for the backward (no recovery rounding); recovering conv*d from `out` there instead
         # was measured at C3 within noise: 45.86 against 45.99 ms per plain step.
         ctx.save_for_backward(conv, d, nzt, out)
@@ -110,20 +68,8 @@ class _DemodNoiseLrelu(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         conv, d, nzt, out = ctx.saved_tensors
-        g = _f32c(g.detach())
-        B, O, H, _ = out.shape
-        S = nzt.shape[-1]
-        with on_device(out.device):
-            gconv = torch.empty_like(out)
-            gd = None if d is None else torch.empty_like(d)
-            gw = torch.empty((B, O), dtype=torch.float32, device=out.device)
-            gb = torch.empty((B, O), dtype=torch.float32, device=out.device)
-            ws, n = _ws(out, B, O, H, H)
-            check(lib.hg_demod_noise_lrelu_bwd(g.data_ptr(), out.data_ptr(), conv.data_ptr(),
-                                               None if d is None else d.data_ptr(), nzt.data_ptr(), None, None, gconv.data_ptr(),
-                                               None if gd is None else gd.data_ptr(), gw.data_ptr(), gb.data_ptr(),
-                                               B, O, H, S, ws.data_ptr(), n, _st(out)), 'hg_demod_noise_lrelu_bwd')
-        return gconv, gd, None, gw.sum(0).reshape(-1, 1), gb.sum(0)
+        gconv, gd, gw_p, gb_p = launch.dnl_bwd(f32c(g), out, conv, d, nzt, None, None)
+        return gconv, gd, None, gw_p.sum(0).reshape(-1, 1), gb_p.sum(0)
 
 
 def demod_noise_lrelu(conv, d, nzt, wn, bn):
@@ -136,7 +82,7 @@ TORGB = os.environ.get('HG_TORGB', '1') != '0'      # the to-RGB path as one str
 
 def torgb_supported(x, weight):
     return (TORGB and x.is_cuda and x.dtype == torch.float32 and weight.shape[2] == 1 and weight.shape[3] == 1
-            and weight.shape[0] <= 4 and (x.shape[2] * x.shape[3]) % 4 == 0 and weight.shape[0] * weight.shape[1] * 4 <= 48 * 1024)
+            and weight.shape[0] <= 4 and (x.shape[2] * x.shape[3]) % 4 == 0 and launch.torgb_fits(weight.shape[0], weight.shape[1]))
 
 
 class _ToRGB(torch.autograd.Function):
@@ -147,33 +93,16 @@ class _ToRGB(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, style, weight, prev):
-        x_, s_, w_ = _f32c(x.detach()), _f32c(style.detach()), _f32c(weight.detach())
-        B, O, H, W = x_.shape
-        C = w_.shape[0]
-        p_ = None if prev is None else _f32c(prev.detach())
-        with on_device(x_.device):
-            out = torch.empty((B, C, H, W), dtype=torch.float32, device=x_.device)
-            check(lib.hg_torgb_fwd(x_.data_ptr(), s_.data_ptr(), w_.data_ptr(), None if p_ is None else p_.data_ptr(),
-                                   out.data_ptr(), B, O, C, H * W, _st(x_)), 'hg_torgb_fwd')
+        x_, s_, w_ = f32c(x), f32c(style), f32c(weight)
         ctx.save_for_backward(x_, s_, w_)
         ctx.has_prev = prev is not None
-        return out
+        return launch.torgb_fwd(x_, s_, w_, None if prev is None else f32c(prev))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        x_, s_, w_ = ctx.saved_tensors
-        g = _f32c(g.detach())
-        B, O, H, W = x_.shape
-        C = w_.shape[0]
-        with on_device(x_.device):
-            gx = torch.empty_like(x_)
-            gs = torch.empty_like(s_)
-            gw = torch.empty_like(w_)
-            nb = lib.hg_torgb_bwd_workspace_bytes(B, O, C, H * W)
-            ws = torch.empty(nb, dtype=torch.uint8, device=x_.device)
-            check(lib.hg_torgb_bwd(g.data_ptr(), x_.data_ptr(), s_.data_ptr(), w_.data_ptr(), gx.data_ptr(), gs.data_ptr(),
-                                   gw.data_ptr(), B, O, C, H * W, ws.data_ptr(), nb, _st(x_)), 'hg_torgb_bwd')
+        g = f32c(g)
+        gx, gs, gw = launch.torgb_bwd(g, *ctx.saved_tensors)
         return gx, gs, gw, (g if ctx.has_prev else None)
 
 
@@ -192,14 +121,12 @@ class _ConvDnl(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xm, w, d, nzt, wn, bn):
-        from . import conv as C
-        _need_gpu(xm, 'conv_dnl')
-        xm_, w_ = _f32c(xm.detach()), _f32c(w.detach())
-        d_ = None if d is None else _f32c(d.detach())
-        nzt_, wn_, bn_ = _f32c(nzt.detach()), _f32c(wn.detach().reshape(-1)), _f32c(bn.detach())
+        need_gpu(xm, 'conv_dnl')
+        xm_, w_ = f32c(xm), f32c(w)
+        d_ = None if d is None else f32c(d)
+        nzt_, wn_, bn_ = f32c(nzt), f32c(wn.detach().reshape(-1)), f32c(bn)
         N, k = w_.shape[0], w_.shape[2]
-        if xm_.shape[2] != xm_.shape[3]:
-            raise ValueError('square feature maps only (the noise permute of the reference needs H == W)')
+        _square(xm_)
         out = C.modconv_fwd_packed(xm_, C.pack_weights(w_, C.PACK_FWD), N, k, None, d_, bn_, wn_, nzt_, nzt_.shape[-1], 0.2)
         ctx.save_for_backward(xm, w, d_, nzt_, out, wn_, bn_)
         return out
@@ -207,27 +134,14 @@ class _ConvDnl(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        from . import conv as C
         xm, w, d, nzt_, out, wn_, bn_ = ctx.saved_tensors
-        g = _f32c(g.detach())
-        B, N, H, _ = out.shape
         K, k = w.shape[1], w.shape[2]
-        S = nzt_.shape[-1]
-        with on_device(out.device):
-            gconv = torch.empty_like(out)
-            gd = None if d is None else torch.empty_like(d)
-            gw_p = torch.empty((B, N), dtype=torch.float32, device=out.device)
-            gb_p = torch.empty((B, N), dtype=torch.float32, device=out.device)
-            ws, n = _ws(out, B, N, H, H)
-            check(lib.hg_demod_noise_lrelu_bwd(g.data_ptr(), out.data_ptr(), None, None if d is None else d.data_ptr(),
-                                               nzt_.data_ptr(), wn_.data_ptr(), bn_.data_ptr(), gconv.data_ptr(),
-                                               None if gd is None else gd.data_ptr(), gw_p.data_ptr(), gb_p.data_ptr(),
-                                               B, N, H, S, ws.data_ptr(), n, _st(out)), 'hg_demod_noise_lrelu_bwd')
+        gconv, gd, gw_p, gb_p = launch.dnl_bwd(f32c(g), out, None, d, nzt_, wn_, bn_)
         gx = gw = None
         if ctx.needs_input_grad[0]:
-            gx = C.conv_dgrad_packed(gconv, C.pack_weights(_f32c(w.detach()), C.PACK_DGRAD), K, xm.shape[2], xm.shape[3], k)
+            gx = C.conv_dgrad_packed(gconv, C.pack_weights(f32c(w), C.PACK_DGRAD), K, xm.shape[2], xm.shape[3], k)
         if ctx.needs_input_grad[1] and not C._skip_wgrad and not C._direct_wgrad(w, xm, gconv, 1):
-            gw = C.conv_wgrad(_f32c(xm.detach()), gconv, k)
+            gw = C.conv_wgrad(f32c(xm), gconv, k)
         return gx, gw, gd, None, gw_p.sum(0).reshape(-1, 1), gb_p.sum(0)
 
 
@@ -249,27 +163,17 @@ class _ModConvStage(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, style, weight, nzt, wn, bn, demod, upsample, act):
-        from . import conv as C
-        _need_gpu(x, 'modconv_stage')
-        x, style, w = _f32c(x.detach()), _f32c(style.detach()), _f32c(weight.detach())
-        B, K, H, W = x.shape
+        need_gpu(x, 'modconv_stage')
+        x, style, w = f32c(x), f32c(style), f32c(weight)
         N, _, k, _ = w.shape
-        s1 = style + 1.0
-        if upsample:
-            with on_device(x.device):
-                xin = torch.empty((B, K, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-                check(lib.hg_modulate_fwd(x.data_ptr(), style.data_ptr(), xin.data_ptr(), B, K, H, W, 1, _st(x)),
-                      'hg_modulate_fwd')
-            iscale = None
-        else:
-            xin, iscale = x, s1
-        Hi, Wi = xin.shape[2], xin.shape[3]
-        d = None
+        xin = launch.modulate_fwd(x, style, True) if upsample else x
         if demod:
-            wsq = C.cached(w, 'wsq', lambda t: t.pow(2).sum(dim=(2, 3)))
-            d = torch.rsqrt(_skinny_mm(s1 * s1, wsq, True) + 1e-8)
+            d, s1, _ = demod_fwd(style, w)
+        else:
+            d, s1 = None, style + 1.0
+        iscale = None if upsample else s1
         if act:
-            nzt_, wn_, bn_ = _f32c(nzt.detach()), _f32c(wn.detach().reshape(-1)), _f32c(bn.detach())
+            nzt_, wn_, bn_ = f32c(nzt), f32c(wn.detach().reshape(-1)), f32c(bn)
             S = nzt_.shape[-1]
         else:
             nzt_ = wn_ = bn_ = None
@@ -282,45 +186,28 @@ class _ModConvStage(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import conv as C
         x, xin, style, w, d, out, nzt_, wn_, bn_ = ctx.saved_tensors
         demod, upsample, act = ctx.cfg
-        g = _f32c(g.detach())
-        B, K, H, W = x.shape
-        N, _, k, _ = w.shape
+        g = f32c(g)
+        K = x.shape[1]
+        k = w.shape[2]
         s1 = style + 1.0
         if xin is None:
             xin = x
         Hi, Wi = xin.shape[2], xin.shape[3]
         gwn = gbn = gd = None
-        with on_device(x.device):
-            if act:
-                S = nzt_.shape[-1]
-                gconv = torch.empty_like(out)
-                gdr = torch.empty((B, N), dtype=torch.float32, device=x.device) if d is not None else None
-                gw_p = torch.empty((B, N), dtype=torch.float32, device=x.device)
-                gb_p = torch.empty((B, N), dtype=torch.float32, device=x.device)
-                ws, n = _ws(out, B, N, Hi, Wi)
-                check(lib.hg_demod_noise_lrelu_bwd(g.data_ptr(), out.data_ptr(), None,
-                                                   None if d is None else d.data_ptr(), nzt_.data_ptr(), wn_.data_ptr(),
-                                                   bn_.data_ptr(), gconv.data_ptr(),
-                                                   None if gdr is None else gdr.data_ptr(), gw_p.data_ptr(),
-                                                   gb_p.data_ptr(), B, N, Hi, S, ws.data_ptr(), n, _st(x)),
-                      'hg_demod_noise_lrelu_bwd')
-                gwn, gbn = gw_p.sum(0).reshape(-1, 1), gb_p.sum(0)
-                gd = gdr
-            else:
-                if d is not None:
-                    raise RuntimeError('modconv_stage: demodulation without activation is not implemented')
-                gconv = g
-            t = C.conv_dgrad_packed(gconv, C.pack_weights(w, C.PACK_DGRAD), K, Hi, Wi, k)
-            gx = torch.empty_like(x)
-            gs = torch.empty_like(style)
-            ws, n = _ws(x, B, K, H, W)
-            check(lib.hg_modulate_bwd(t.data_ptr(), x.data_ptr(), style.data_ptr(), gx.data_ptr(), gs.data_ptr(),
-                                      B, K, H, W, int(upsample), ws.data_ptr(), n, _st(x)), 'hg_modulate_bwd')
-            gw = C.conv_wgrad(xin, gconv, k, iscale=None if upsample else s1)
+        if act:
+            gconv, gd, gw_p, gb_p = launch.dnl_bwd(g, out, None, d, nzt_, wn_, bn_)
+            gwn, gbn = gw_p.sum(0).reshape(-1, 1), gb_p.sum(0)
+        else:
+            if d is not None:
+                raise RuntimeError('modconv_stage: demodulation without activation is not implemented')
+            gconv = g
+        t = C.conv_dgrad_packed(gconv, C.pack_weights(w, C.PACK_DGRAD), K, Hi, Wi, k)
+        gx, gs = launch.modulate_bwd(t, x, style, upsample)
+        gw = C.conv_wgrad(xin, gconv, k, iscale=None if upsample else s1)
         if d is not None:
+            # not demod_bwd: a recomputed wsq and a plain mm here round differently from the cached wsq and _skinny_mm there
             wsq = w.pow(2).sum(dim=(2, 3))
             gq = gd * (-0.5) * d * d * d
             gs = gs + 2.0 * s1 * torch.mm(gq, wsq)
@@ -347,45 +234,48 @@ def _skinny_mm(a, m, m_transposed):
     return torch.bmm(av, mv).sum(0)
 
 
+def demod_fwd(s, w):
+    """d[b,o] = rsqrt( sum_i (s[b,i]+1)^2 * wsq[o,i] + 1e-8 ),  wsq[o,i] = sum_k W[o,i,k]^2   (Conv2DMod demodulation,
+    histoGAN/histoGAN.py:427-429, on the shared weight) -> (d, s + 1, wsq); s and w detached.  wsq only depends on the weight,
+    so it is cached per optimizer step for registered training weights (conv.cached) instead of re-reducing up to 151 MB
+    three times a step."""
+    wsq = C.cached(w, 'wsq', lambda t: t.pow(2).sum(dim=(2, 3)))
+    s1 = s + 1.0
+    return torch.rsqrt(_skinny_mm(s1 * s1, wsq, True) + 1e-8), s1, wsq
+
+
+def demod_bwd(gd, d, s1, wsq, w, want_style=True, want_weight=True):
+    """d's adjoint -> (gy, gw): the style part (B, K), and the weight part -- None when it was added to the weight's flat
+    gradient slot on the weight-gradient stream, BEHIND the convolution's weight gradient that wrote the slot (training:
+    one kernel, hg_demod_weight_term)."""
+    gy = gw = gq = None
+    if want_style:
+        if gd.is_cuda and not torch.is_grad_enabled() and wsq.is_contiguous():
+            # one kernel pair (hg_demod_style_grad) instead of a skinny rocBLAS GEMM + five element-wise launches
+            gy = launch.demod_style_grad(f32c(gd), d, s1, wsq)
+        else:
+            gq = gd * (-0.5) * d * d * d
+            gy = 2.0 * s1 * _skinny_mm(gq, wsq, False)
+    if want_weight and not (w.is_contiguous() and C.direct_demod_weight_term(w, gd, d, s1)):
+        gq = gd * (-0.5) * d * d * d if gq is None else gq
+        gw = 2.0 * w.detach() * torch.mm(gq.t(), s1 * s1)[:, :, None, None]
+    return gy, gw
+
+
 class _DemodCoeff(torch.autograd.Function):
-    """d[b,o] = rsqrt( sum_i (y[b,i]+1)^2 * wsq[o,i] + 1e-8 ),  wsq[o,i] = sum_k W[o,i,k]^2   (Conv2DMod demodulation,
-    histoGAN/histoGAN.py:427-429, on the shared weight).  wsq only depends on the weight, so it is cached per optimizer
-    step for registered training weights (conv.cached) instead of re-reducing up to 151 MB three times a step."""
+    """demod_fwd / demod_bwd as an autograd node of the per-block path."""
 
     @staticmethod
     def forward(ctx, y, weight):
-        from . import conv as C
         w = weight.detach()
-        wsq = C.cached(w, 'wsq', lambda t: t.pow(2).sum(dim=(2, 3)))
-        s1 = y.detach() + 1.0
-        d = torch.rsqrt(_skinny_mm(s1 * s1, wsq, True) + 1e-8)
+        d, s1, wsq = demod_fwd(y.detach(), w)
         ctx.save_for_backward(s1, wsq, d, w)
         return d
 
     @staticmethod
     def backward(ctx, gd):
         s1, wsq, d, w = ctx.saved_tensors
-        gy = gw = gq = None
-        fused = gd.is_cuda and not torch.is_grad_enabled() and wsq.is_contiguous()
-        if ctx.needs_input_grad[0]:
-            if fused:       # one kernel pair (hg_demod_style_grad) instead of a skinny rocBLAS GEMM + five element-wise launches
-                gdc, B, N, K = _f32c(gd), d.shape[0], d.shape[1], s1.shape[1]
-                with on_device(gd.device):
-                    gy = torch.empty_like(s1)
-                    nb = lib.hg_demod_style_grad_workspace_bytes(B, N, K)
-                    ws = torch.empty(nb, dtype=torch.uint8, device=gd.device)
-                    check(lib.hg_demod_style_grad(gdc.data_ptr(), d.data_ptr(), s1.data_ptr(), wsq.data_ptr(), gy.data_ptr(),
-                                                  B, N, K, ws.data_ptr(), nb, _st(gd)), 'hg_demod_style_grad')
-            else:
-                gq = gd * (-0.5) * d * d * d
-                gy = 2.0 * s1 * _skinny_mm(gq, wsq, False)
-        if ctx.needs_input_grad[1]:
-            from . import conv as C
-            # training: added to the weight's flat gradient slot on the side stream (one kernel, hg_demod_weight_term)
-            if not (w.is_contiguous() and C.direct_demod_weight_term(w, gd, d, s1)):
-                gq = gd * (-0.5) * d * d * d if gq is None else gq
-                gw = 2.0 * w * torch.mm(gq.t(), s1 * s1)[:, :, None, None]
-        return gy, gw
+        return demod_bwd(gd, d, s1, wsq, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
 
 
 def demod_coeff(y, weight):
@@ -397,7 +287,6 @@ GROUPED_STYLES = os.environ.get('HG_GROUPED_STYLES', '1') != '0'   # 0: one F.li
 
 
 def _glin_table(xs, ws, bs, ys, groups, gws=None, gbs=None):
-    from ._lib import GlinLayer
     n = len(ws)
     tab = (GlinLayer * n)()
     for i in range(n):
@@ -461,7 +350,7 @@ class _GroupedLinear(torch.autograd.Function):
                 gxs = [torch.empty_like(x) for x in xs]
                 tab = _glin_table(xs, ws, None, gys, groups)
                 nb = lib.hg_grouped_linear_bwd_input_workspace_bytes(tab, n, B, K)
-                wsb = torch.empty((max(nb, 4),), dtype=torch.uint8, device=dev)
+                wsb = workspace(nb, dev)
                 ptrs = (ctypes.c_void_p * G)(*[g.data_ptr() for g in gxs])
                 check(lib.hg_grouped_linear_bwd_input(tab, n, ptrs, G, B, K, wsb.data_ptr(), wsb.numel(), st),
                       'hg_grouped_linear_bwd_input')

@@ -10,12 +10,8 @@ import ctypes
 
 import torch
 
-from ._lib import check, lib, on_device, raw_stream
+from ._lib import check, lib, on_device, stream_of
 from .conv import weights_changed
-
-
-def _st(t):
-    return raw_stream(t.device)
 
 
 def conv_first(params):
@@ -187,7 +183,7 @@ class DiffGrad:
             check(lib.hg_diffgrad_step(f.data.data_ptr() + o, f.grad.data_ptr() + o, self.exp_avg.data_ptr() + o,
                                        self.exp_avg_sq.data_ptr() + o, self.previous_grad.data_ptr() + o, hi - lo,
                                        float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                       step_count, _st(f.data)), 'hg_diffgrad_step')
+                                       step_count, stream_of(f.data)), 'hg_diffgrad_step')
 
     def step(self):
         f = self.flat
@@ -199,7 +195,7 @@ class DiffGrad:
                 check(lib.hg_diffgrad_step_dev(f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
                                                self.exp_avg_sq.data_ptr(), self.previous_grad.data_ptr(), f.numel,
                                                self._step_size_dev.data_ptr(), float(self.betas[0]),
-                                               float(self.betas[1]), float(self.eps), _st(f.data)),
+                                               float(self.betas[1]), float(self.eps), stream_of(f.data)),
                       'hg_diffgrad_step_dev')
             weights_changed(f.data)
             return
@@ -214,5 +210,5 @@ def ema_update(ma_flat, cur_flat, beta):
         raise ValueError('EMA buffers differ in size')
     with on_device(ma_flat.data.device):
         check(lib.hg_ema_update(ma_flat.data.data_ptr(), cur_flat.data.data_ptr(), ma_flat.numel, float(beta),
-                                _st(ma_flat.data)), 'hg_ema_update')
+                                stream_of(ma_flat.data)), 'hg_ema_update')
     weights_changed(ma_flat.data)

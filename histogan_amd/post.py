@@ -17,7 +17,7 @@ from math import ceil
 import numpy as np
 import torch
 
-from ._lib import check, lib, on_device, raw_stream
+from ._lib import check, lib, need_gpu, on_device, raw_stream
 
 EPS = 2.2204e-16          # utils/color_transfer_MKL.py:3
 
@@ -82,9 +82,7 @@ def _tables(n_in, n_out, scale, method, device):
             torch.from_numpy(np.ascontiguousarray(i, dtype=np.int32)).to(dev), w.shape[1])
 
 
-def _need_cuda(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f'{what}: expects a tensor on the GPU; the MI355X-native path has no CPU implementation')
+_FOUND = 'expects a tensor on the GPU'     # need_gpu's wording here
 
 
 # ---- device: resize ---------------------------------------------------------------------------------------------------
@@ -100,7 +98,7 @@ def imresize(x, output_shape=None, scalar_scale=None, method='bicubic', clamp=Fa
     (H, W, C) / (H, W).  Returns fp32 (C, H', W') / (H', W') contiguous, or uint8 (H', W', C) / (H', W') with the
     reference's clip + round-half-to-even after EACH pass (its uint8 path rounds the intermediate too).  The axis with
     the smaller scale is resized first (the reference's argsort).  clamp: clamp the input to [0, 1] as it is read."""
-    _need_cuda(x, 'imresize')
+    need_gpu(x, 'imresize', _FOUND)
     if method not in KERNELS:
         raise ValueError(f"imresize: method must be 'bicubic' or 'bilinear', not {method!r}")
     u8 = x.dtype == torch.uint8
@@ -143,7 +141,7 @@ def imresize(x, output_shape=None, scalar_scale=None, method='bicubic', clamp=Fa
 # ---- device: layout conversions -----------------------------------------------------------------------------------------
 def u8_hwc_to_float(x):
     """uint8 (H, W, C) -> fp32 (C, H, W) = x / 255 (torchvision ToTensor)."""
-    _need_cuda(x, 'u8_hwc_to_float')
+    need_gpu(x, 'u8_hwc_to_float', _FOUND)
     x = x.contiguous()
     H, W, C = x.shape
     out = torch.empty((C, H, W), dtype=torch.float32, device=x.device)
@@ -154,7 +152,7 @@ def u8_hwc_to_float(x):
 
 def float_to_u8_hwc(x):
     """fp32 (C, H, W) -> uint8 (H, W, C) = clamp(x*255 + 0.5, 0, 255) truncated (torchvision save_image)."""
-    _need_cuda(x, 'float_to_u8_hwc')
+    need_gpu(x, 'float_to_u8_hwc', _FOUND)
     x = x.float().contiguous()
     C, H, W = x.shape
     out = torch.empty((H, W, C), dtype=torch.uint8, device=x.device)
@@ -230,8 +228,8 @@ def pyramid_upsampling(target, reference, levels=5, swapping_levels=1, blending=
     reference's first `swapping_levels` entries [gp[levels-1], L_{levels-1}, ..., L_1]; with `blending` the remaining
     entries are mixed with linspace(0, 1, levels - swapping_levels + 1) weights."""
     ab = level_weights(levels, swapping_levels, blending)
-    _need_cuda(target, 'pyramid_upsampling')
-    _need_cuda(reference, 'pyramid_upsampling')
+    need_gpu(target, 'pyramid_upsampling', _FOUND)
+    need_gpu(reference, 'pyramid_upsampling', _FOUND)
     with on_device(reference.device):
         if reference.dtype == torch.uint8:
             if reference.dim() != 3 or reference.shape[2] != 3:
@@ -290,7 +288,7 @@ def MKL(A, B):
 
 def _pixels(t, what):
     """(tensor, n, pix_stride, chan_stride) of an (H, W, 3) fp32 view (a CHW image's .permute(1, 2, 0) is one)."""
-    _need_cuda(t, 'color_transfer_mkl')
+    need_gpu(t, 'color_transfer_mkl', _FOUND)
     if t.dim() != 3 or t.shape[2] != 3:
         raise ValueError(f'color_transfer_mkl: {what} must be an (H, W, 3) image, got {tuple(t.shape)}')
     t = t.float()

@@ -12,27 +12,26 @@ import ctypes
 
 import torch
 
-from ._lib import check, lib, on_device, raw_stream
-from .ops import _f32c, _need_gpu, _st
+from ._lib import check, f32c, lib, need_gpu, on_device, stream_of, workspace
 
 
 def _in_ws(t, P):
     n = lib.hg_instnorm_workspace_bytes(P)
-    return torch.empty(max(n, 4), dtype=torch.uint8, device=t.device), n
+    return workspace(n, t.device), n
 
 
 class _InstNormLrelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eps, slope):
-        _need_gpu(x, 'instnorm_lrelu')
-        x = _f32c(x.detach())
+        need_gpu(x, 'instnorm_lrelu')
+        x = f32c(x)
         B, C, H, W = x.shape
         with on_device(x.device):
             out = torch.empty_like(x)
             stats = torch.empty((B * C, 2), dtype=torch.float32, device=x.device)
             ws, n = _in_ws(x, B * C)
             check(lib.hg_instnorm_lrelu_fwd(x.data_ptr(), out.data_ptr(), stats.data_ptr(), B * C, H * W, eps, slope,
-                                            ws.data_ptr(), n, _st(x)), 'hg_instnorm_lrelu_fwd')
+                                            ws.data_ptr(), n, stream_of(x)), 'hg_instnorm_lrelu_fwd')
         ctx.save_for_backward(out, stats)
         ctx.slope = slope
         return out
@@ -40,13 +39,13 @@ class _InstNormLrelu(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         out, stats = ctx.saved_tensors
-        g = _f32c(g.detach())
+        g = f32c(g)
         B, C, H, W = out.shape
         with on_device(out.device):
             gx = torch.empty_like(out)
             ws, n = _in_ws(out, B * C)
             check(lib.hg_instnorm_lrelu_bwd(g.data_ptr(), out.data_ptr(), stats.data_ptr(), gx.data_ptr(), B * C, H * W,
-                                            ctx.slope, ws.data_ptr(), n, _st(out)), 'hg_instnorm_lrelu_bwd')
+                                            ctx.slope, ws.data_ptr(), n, stream_of(out)), 'hg_instnorm_lrelu_bwd')
         return gx, None, None
 
 
@@ -56,13 +55,13 @@ def instnorm_lrelu(x, eps=1e-5, slope=0.2):
 
 
 def _stencil_raw(x, taps, C, adjoint):
-    _need_gpu(x, 'stencil3')
-    x = _f32c(x.detach())
+    need_gpu(x, 'stencil3')
+    x = f32c(x)
     B, _, H, W = x.shape
     arr = (ctypes.c_float * 9)(*[float(v) for v in taps])
     with on_device(x.device):
         out = torch.empty((B, C if adjoint else 1, H, W), dtype=torch.float32, device=x.device)
-        check(lib.hg_stencil3(x.data_ptr(), out.data_ptr(), arr, B, C, H, W, int(adjoint), _st(x)), 'hg_stencil3')
+        check(lib.hg_stencil3(x.data_ptr(), out.data_ptr(), arr, B, C, H, W, int(adjoint), stream_of(x)), 'hg_stencil3')
     return out
 
 
@@ -86,14 +85,14 @@ def stencil3(x, taps):
 
 
 def _dw_raw(x, k, H, W, adjoint):
-    _need_gpu(x, 'gaussian_valid')
-    x = _f32c(x.detach())
+    need_gpu(x, 'gaussian_valid')
+    x = f32c(x)
     B, C = x.shape[:2]
     KS = k.shape[-1]
     with on_device(x.device):
         shape = (B, C, H, W) if adjoint else (B, C, H - KS + 1, W - KS + 1)
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        check(lib.hg_depthwise_valid(x.data_ptr(), k.data_ptr(), out.data_ptr(), B * C, H, W, KS, int(adjoint), _st(x)),
+        check(lib.hg_depthwise_valid(x.data_ptr(), k.data_ptr(), out.data_ptr(), B * C, H, W, KS, int(adjoint), stream_of(x)),
               'hg_depthwise_valid')
     return out
 
@@ -116,5 +115,5 @@ def gaussian_valid(x, kernel):
     k = kernel.detach()
     if k.dim() == 4:
         k = k[0, 0]
-    k = _f32c(k).to(x.device)
+    k = f32c(k).to(x.device)
     return _Depthwise.apply(x, k, x.shape[2], x.shape[3], False)

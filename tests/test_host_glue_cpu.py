@@ -126,3 +126,64 @@ def test_switches_of_the_hip_sources_are_the_documented_ones():
             break
         documented |= set(re.findall(r'`(HG_[A-Z0-9_]+)`', line.split('|')[1]))
     assert read and read == documented, (sorted(read - documented), sorted(documented - read))
+
+
+def test_launch_layer_has_one_place_per_kernel_and_per_helper():
+    """The binding layer's structure, read from the sources: every generator kernel of include/hg_nets.h that ops.py and gfused.py
+    share is marshalled in exactly one place (launch.py), the small host helpers exist once (in _lib.py), and ops.py / conv.py
+    do not import each other behind a function.  Then the helpers' own contract, on CPU tensors."""
+    import ast
+    import pathlib
+    import re
+    pkg = pathlib.Path(__file__).resolve().parents[1] / 'histogan_amd'
+    src = {p.name: p.read_text() for p in sorted(pkg.glob('*.py'))}
+    tree = {name: ast.parse(text) for name, text in src.items()}
+
+    def calls(fn):           # name of module -> number of `lib.<fn>(` call sites in it
+        return {name: len(re.findall(r'\blib\.' + fn + r'\(', text)) for name, text in src.items()
+                if re.search(r'\blib\.' + fn + r'\(', text)}
+
+    for fn in ('hg_modulate_fwd', 'hg_modulate_bwd', 'hg_demod_noise_lrelu_fwd', 'hg_demod_noise_lrelu_bwd', 'hg_torgb_fwd',
+               'hg_torgb_bwd', 'hg_demod_style_grad', 'hg_channel_sum'):
+        assert calls(fn) == {'launch.py': 1}, (fn, calls(fn))
+    assert set(calls('hg_nets_workspace_bytes').values()) == {1}, calls('hg_nets_workspace_bytes')     # one per wrapper module
+    assert not any(re.search(r'48\s*\*\s*1024', src[name]) for name in ('ops.py', 'gfused.py'))    # the to-RGB LDS limit: launch.py's
+
+    helpers = {'stream_of', 'f32c', 'ptr', 'need_gpu', 'workspace', 'NullCtx',                      # _lib's
+               '_st', '_stream', '_f32c', '_ptr', '_need_gpu', '_need_cuda', '_require_gpu', '_NullCtx'}   # the former copies
+    lib_defs = {n.name for n in tree['_lib.py'].body if isinstance(n, (ast.FunctionDef, ast.ClassDef))}
+    assert helpers & lib_defs == {'stream_of', 'f32c', 'ptr', 'need_gpu', 'workspace', 'NullCtx'}
+    for name, t in tree.items():
+        if name == '_lib.py':
+            continue
+        defs = {n.name for n in ast.walk(t) if isinstance(n, (ast.FunctionDef, ast.ClassDef))}
+        assert not defs & helpers, (name, sorted(defs & helpers))
+        assert not re.search(r'torch\.empty\(\(?max\(\w+, 4\)', src[name]), name     # the workspace pattern written out
+
+    def imports(node):       # module names an import statement reaches, relative ones without their dots
+        if isinstance(node, ast.Import):
+            return {a.name for a in node.names}
+        if isinstance(node, ast.ImportFrom):
+            return {node.module} if node.module else {a.name for a in node.names}
+        return set()
+
+    for name, other in (('ops.py', 'conv'), ('conv.py', 'ops')):
+        top = set(tree[name].body)
+        inner = [n for n in ast.walk(tree[name]) if n not in top and other in imports(n)]
+        assert not inner, (name, [n.lineno for n in inner])
+    assert not any('ops' in imports(n) for n in ast.walk(tree['conv.py']))        # conv sits below ops
+    for n in ast.walk(tree['launch.py']):                                        # and launch below both: _lib and torch only
+        assert imports(n) <= {'torch', '_lib'}, (n.lineno, imports(n))
+    assert not any(isinstance(n, ast.ImportFrom) and n.module == 'ops' and any(a.name.startswith('_') for a in n.names)
+                   for n in ast.walk(tree['reops.py']))
+
+    from histogan_amd._lib import f32c, ptr
+    a = torch.randn(3, 4, requires_grad=True)
+    b = f32c(a)
+    assert b.untyped_storage().data_ptr() == a.untyped_storage().data_ptr() and not b.requires_grad and b.shape == a.shape
+    c = f32c(torch.arange(6, dtype=torch.float64).reshape(2, 3))
+    assert c.dtype == torch.float32 and torch.equal(c, torch.arange(6.).reshape(2, 3))
+    s = torch.randn(4, 6)[:, ::2]
+    e = f32c(s)
+    assert not s.is_contiguous() and e.is_contiguous() and torch.equal(e, s)
+    assert ptr(None) is None and ptr(a) == a.data_ptr()
