@@ -209,6 +209,12 @@ def _load():
     lib.hg_u8_hwc_to_f32.argtypes = [vp, vp, i32, i64, vp]
     lib.hg_f32_to_u8_hwc.restype = ctypes.c_int
     lib.hg_f32_to_u8_hwc.argtypes = [vp, vp, i32, i64, vp]
+    lib.hg_bgu_normal_workspace_bytes.restype = sz
+    lib.hg_bgu_normal_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.hg_bgu_normal.restype = ctypes.c_int
+    lib.hg_bgu_normal.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.hg_bgu_slice.restype = ctypes.c_int
+    lib.hg_bgu_slice.argtypes = [vp, i32, i32, i32, vp, i64, i64, i64, vp, i32, i32, i32, vp]
     return lib
 
 
@@ -231,7 +237,8 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
            'hg_wino_wgrad_supported', 'hg_wino_wgrad_workspace_bytes', 'hg_wino_wgrad',
            'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd',
            'hg_resize_axis', 'hg_pyr_down', 'hg_pyr_up_add', 'hg_color_moments_workspace_bytes', 'hg_color_moments',
-           'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc')
+           'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc', 'hg_bgu_normal_workspace_bytes', 'hg_bgu_normal',
+           'hg_bgu_slice')
 
 
 class HgError(RuntimeError):

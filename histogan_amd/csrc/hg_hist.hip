@@ -30,7 +30,8 @@
 #include "../../include/hg_hist.h"
 #include <cstdlib>
 
-#define HG_VERSION_NUM 103   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight
+#define HG_VERSION_NUM 104   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
+                             // 104: hg_bgu_normal, hg_bgu_slice (hg_post.h)
 
 // Settled schedule constants of the dense kernels (DESIGN.md sections 4 and 11 hold the measurements).
 constexpr int kFwdMfmaGroup = 12;    // k_hist_fwd at configs[1]: groups of 1: 505 us, 3: 498, 6: 473, 12: 465

@@ -329,6 +329,228 @@ def color_transfer_mkl(source, target, quantize=False):
     return out, T
 
 
+# ---- bilateral guided upsampling (upsampling/BGU.m, bguFit.m, bguSlice.m) -----------------------------------------------
+BGU_DEPTH = 8             # luminance bins of the grid (getDefaultAffineGridSize.m)
+BGU_CELL = 16             # low-resolution pixels per spatial bin
+
+
+def _round_half_away(v):
+    """MATLAB round() of a non-negative value (Python's round is half-to-even: round(2.5) == 2)."""
+    return int(np.floor(v + 0.5))
+
+
+def bgu_grid_size(h, w):
+    """(gh, gw) = [round(h / 16), round(w / 16)] with MATLAB rounding, for an h x w low-resolution pair.  A side below 2
+    vertices cannot be interpolated (ValueError)."""
+    gh, gw = _round_half_away(h / BGU_CELL), _round_half_away(w / BGU_CELL)
+    if gh < 2 or gw < 2:
+        raise ValueError(f'bgu_grid_size: a {h}x{w} image gives a {gh}x{gw} grid; every side needs at least 2 vertices '
+                         f'(24 pixels)')
+    return gh, gw
+
+
+def bgu_slab_axis(gh, gw):
+    """0 when the slabs of the block-tridiagonal system run along y (gh >= gw), 1 when along x (include/hg_post.h)."""
+    return 0 if gh >= gw else 1
+
+
+def _path_laplacian(n):
+    """D^T D of the n-1 first differences of n samples."""
+    d = np.diff(np.eye(n), axis=0)
+    return d.T @ d
+
+
+@lru_cache(maxsize=8)
+def _bgu_regulariser(h, w, gh, gw, gd, lambda_spatial, lambda_z):
+    """(within, c_slab): the smoothness terms' part of N in the slab layout of hg_bgu_normal.  `within` (m, m) couples
+    the unknowns of one slab (first differences along the shorter axis, second differences in z with first differences
+    at both ends); along the slab axis the first differences add c_slab * (number of neighbouring slabs) to a slab's
+    diagonal and -c_slab to the diagonal of each off-diagonal block."""
+    bx, by, bz = w / gw, h / gh, 1.0 / gd
+    cy, cx = (bx * bz / by) * lambda_spatial, (by * bz / bx) * lambda_spatial
+    cz = (bx * by / (bz * bz)) * lambda_z
+    c_slab, c_in = (cy, cx) if bgu_slab_axis(gh, gw) == 0 else (cx, cy)
+    T = min(gh, gw)
+    dz = np.zeros((gd, gd))
+    dz[0, 0], dz[0, 1] = -1, 1
+    for z in range(gd - 2):
+        dz[z + 1, z:z + 3] = (1, -2, 1)
+    dz[gd - 1, gd - 2], dz[gd - 1, gd - 1] = 1, -1
+    within = c_in ** 2 * np.kron(_path_laplacian(T), np.eye(gd)) + cz ** 2 * np.kron(np.eye(T), dz.T @ dz)
+    return torch.from_numpy(np.kron(within, np.eye(4))), c_slab ** 2
+
+
+@lru_cache(maxsize=4)
+def _bgu_regulariser_on(h, w, gh, gw, gd, lambda_spatial, lambda_z, device):
+    """_bgu_regulariser with its block resident on `device`."""
+    within, c = _bgu_regulariser(h, w, gh, gw, gd, lambda_spatial, lambda_z)
+    return within.to(torch.device(device)), c
+
+
+def bgu_regulariser_blocks(h, w, gh, gw, gd=BGU_DEPTH, lambda_spatial=1.0, lambda_z=4e-7):
+    """The smoothness terms' R^T R as (diag (S, m, m), off (S - 1, m, m)) fp64 host tensors in the slab layout."""
+    within, c = _bgu_regulariser(h, w, gh, gw, gd, float(lambda_spatial), float(lambda_z))
+    S, m = max(gh, gw), within.shape[0]
+    diag = within.repeat(S, 1, 1)
+    off = torch.zeros((S - 1, m, m), dtype=torch.float64)
+    _add_slab_coupling(diag, off, c)
+    return diag, off
+
+
+def _add_slab_coupling(diag, off, c):
+    S = diag.shape[0]
+    nb = torch.full((S,), 2.0, dtype=torch.float64, device=diag.device)
+    nb[0] = nb[-1] = 1.0
+    diag.diagonal(dim1=1, dim2=2).add_((c * nb)[:, None])
+    off.diagonal(dim1=1, dim2=2).sub_(c)
+
+
+def block_tridiag_solve(diag, off, rhs):
+    """Solve the symmetric positive definite block-tridiagonal system with diagonal blocks diag (S, m, m) and
+    sub-diagonal blocks off (S - 1, m, m), off[s] = N[s + 1, s], for rhs (k, S, m) by block Cholesky.  Runs on the
+    tensors' device in their dtype; returns (k, S, m)."""
+    S = diag.shape[0]
+    L, B = [], [None]
+    y = []
+    for s in range(S):
+        d = diag[s]
+        r = rhs[:, s].transpose(0, 1)                     # (m, k)
+        if s:
+            # B_s = off[s-1] L_{s-1}^-T
+            b = torch.linalg.solve_triangular(L[s - 1], off[s - 1].transpose(0, 1), upper=False).transpose(0, 1)
+            B.append(b)
+            d = d - b @ b.transpose(0, 1)
+            r = r - b @ y[s - 1]
+        L.append(torch.linalg.cholesky(d))
+        y.append(torch.linalg.solve_triangular(L[s], r, upper=False))
+    x = [None] * S
+    for s in range(S - 1, -1, -1):
+        r = y[s]
+        if s + 1 < S:
+            r = r - B[s + 1].transpose(0, 1) @ x[s + 1]
+        x[s] = torch.linalg.solve_triangular(L[s].transpose(0, 1), r, upper=True)
+    return torch.stack(x, 0).permute(2, 0, 1).contiguous()
+
+
+def bgu_unknowns_to_gamma(x, gh, gw, gd=BGU_DEPTH):
+    """(3, S, m) solutions in the slab layout -> gamma (gh, gw, gd, 3, 4)."""
+    S, T = max(gh, gw), min(gh, gw)
+    x = x.reshape(3, S, T, gd, 4)                          # [i][s][t][z][j]
+    x = x.permute(1, 2, 3, 0, 4) if bgu_slab_axis(gh, gw) == 0 else x.permute(2, 1, 3, 0, 4)
+    return x.contiguous()
+
+
+def _bgu_pair(in_ds, out_ds, weight, what):
+    need_gpu(in_ds, what, _FOUND)
+    need_gpu(out_ds, what, _FOUND)
+    if in_ds.dim() != 3 or in_ds.shape[0] != 3 or in_ds.shape != out_ds.shape:
+        raise ValueError(f'{what}: in_ds and out_ds must both be (3, h, w), got {tuple(in_ds.shape)} and '
+                         f'{tuple(out_ds.shape)}')
+    if weight is not None:
+        need_gpu(weight, what, _FOUND)
+        if tuple(weight.shape) != tuple(in_ds.shape[1:]):
+            raise ValueError(f'{what}: weight must be (h, w) = {tuple(in_ds.shape[1:])}, got {tuple(weight.shape)}')
+        weight = weight.float().contiguous()
+        if not bool((weight >= 0).all()):                 # NaN included: the fit takes sqrt(weight)
+            raise ValueError(f'{what}: weight must be non-negative')
+    return in_ds.float().contiguous(), out_ds.float().contiguous(), weight
+
+
+def bgu_normal(in_ds, out_ds, weight=None, grid=None, gd=BGU_DEPTH):
+    """hg_bgu_normal: (diag, off, rhs) of the data term, fp64 on the device, in the slab layout of include/hg_post.h.
+    grid: (gh, gw), default bgu_grid_size."""
+    x, o, wt = _bgu_pair(in_ds, out_ds, weight, 'bgu_normal')
+    _, h, w = x.shape
+    gh, gw = grid if grid is not None else bgu_grid_size(h, w)
+    S, m = max(gh, gw), min(gh, gw) * gd * 4
+    dev = x.device
+    with on_device(dev):
+        diag = torch.empty((S, m, m), dtype=torch.float64, device=dev)
+        off = torch.empty((S - 1, m, m), dtype=torch.float64, device=dev)
+        rhs = torch.empty((3, S, m), dtype=torch.float64, device=dev)
+        nb = lib.hg_bgu_normal_workspace_bytes(gh, gw, gd)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
+        check(lib.hg_bgu_normal(x.data_ptr(), o.data_ptr(), None if wt is None else wt.data_ptr(), h, w, gh, gw, gd,
+                                diag.data_ptr(), off.data_ptr(), rhs.data_ptr(), ws.data_ptr(), nb, raw_stream(dev)),
+              'hg_bgu_normal')
+    return diag, off, rhs
+
+
+def bgu_fit(in_ds, out_ds, weight=None, lambda_spatial=1.0, lambda_z=4e-7):
+    """upsampling/bguFit.m with its defaults (second-derivative intensity constraint towards 0): the (gh, gw, 8) grid
+    of 3x4 affine models that maps in_ds onto out_ds, both fp32 (3, h, w) on the device; weight: optional non-negative
+    (h, w) map of where out_ds is defined.  The reference solves the stacked least-squares system with `A \\ b`; here
+    the data term's normal equations come from hg_bgu_normal in fp64, the smoothness terms are added from a cached
+    host table, and the block-tridiagonal system is solved by block Cholesky in fp64 on the device.  Returns gamma
+    fp32 (gh, gw, 8, 3, 4)."""
+    if lambda_spatial <= 0:
+        raise ValueError('bgu_fit: lambda_spatial must be positive')
+    in_ds, out_ds, weight = _bgu_pair(in_ds, out_ds, weight, 'bgu_fit')
+    _, h, w = in_ds.shape
+    gh, gw = bgu_grid_size(h, w)
+    diag, off, rhs = bgu_normal(in_ds, out_ds, weight, (gh, gw))
+    within, c = _bgu_regulariser_on(h, w, gh, gw, BGU_DEPTH, float(lambda_spatial), float(lambda_z), str(diag.device))
+    with on_device(diag.device):
+        diag += within
+        _add_slab_coupling(diag, off, c)
+        x = block_tridiag_solve(diag, off, rhs)
+        return bgu_unknowns_to_gamma(x, gh, gw).float()
+
+
+def bgu_slice(gamma, photo_u8, quantize=True):
+    """upsampling/bguSlice.m: gamma (gh, gw, gd, 3, 4) interpolated trilinearly at (x, y, luminance) of every pixel of
+    photo_u8, uint8 (H, W, 3) with any row stride, and applied to it.  Returns uint8 (H, W, 3) = round(255 clip(v, 0, 1))
+    (MATLAB imwrite of a double image) when quantize, else the unclipped fp32 (3, H, W)."""
+    need_gpu(gamma, 'bgu_slice', _FOUND)
+    need_gpu(photo_u8, 'bgu_slice', _FOUND)
+    if gamma.dim() != 5 or tuple(gamma.shape[3:]) != (3, 4):
+        raise ValueError(f'bgu_slice: gamma must be (gh, gw, gd, 3, 4), got {tuple(gamma.shape)}')
+    if photo_u8.dtype != torch.uint8 or photo_u8.dim() != 3 or photo_u8.shape[2] != 3:
+        raise ValueError(f'bgu_slice: the photo must be uint8 (H, W, 3), got {photo_u8.dtype} {tuple(photo_u8.shape)}')
+    g = gamma.float().contiguous()
+    gh, gw, gd = g.shape[:3]
+    H, W, _ = photo_u8.shape
+    if min(photo_u8.stride()) < 0:
+        photo_u8 = photo_u8.contiguous()
+    dev = photo_u8.device
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if quantize else \
+        torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    with on_device(dev):
+        check(lib.hg_bgu_slice(g.data_ptr(), gh, gw, gd, photo_u8.data_ptr(), photo_u8.stride(0), photo_u8.stride(1),
+                               photo_u8.stride(2), out.data_ptr(), int(quantize), H, W, raw_stream(dev)),
+              'hg_bgu_slice')
+    return out
+
+
+def bgu_upsampling(target, reference, weight=None, max_side=300, quantize=False):
+    """upsampling/BGU.m on the GPU: carry the low-resolution recolouring `target` back to the photo `reference` by
+    fitting a bilateral grid of affine colour models at low resolution and slicing it at full resolution, so the
+    result keeps the photo's own detail and its exact size (no padding).
+
+    target: float (1, 3, h, w) / (3, h, w); it is quantised to uint8 as torchvision's save_image writes it and read
+    back as v / 255, because the reference fits to the written file.  The JPEG loss of that file is deliberately NOT
+    modelled: the fit sees the exact 8-bit image.  A target with a side above max_side is resized to
+    max_side x max_side (bicubic, antialiased), as the reference does at 300.  reference: uint8 (H, W, 3), read as
+    v / 255 and resized to the target's size for the fit.  weight: optional (h, w) map at the fit's resolution.
+    Returns fp32 (1, 3, H, W), not clipped, or uint8 (H, W, 3) = round(255 clip(v, 0, 1)) when quantize."""
+    need_gpu(target, 'bgu_upsampling', _FOUND)
+    need_gpu(reference, 'bgu_upsampling', _FOUND)
+    if reference.dtype != torch.uint8 or reference.dim() != 3 or reference.shape[2] != 3:
+        raise ValueError(f'bgu_upsampling: reference must be uint8 (H, W, 3), got {reference.dtype} '
+                         f'{tuple(reference.shape)}')
+    with on_device(reference.device):
+        out_ds = u8_hwc_to_float(float_to_u8_hwc(_as_chw3(target, 'target')))
+        if out_ds.shape[1] > max_side or out_ds.shape[2] > max_side:
+            out_ds = imresize(out_ds, output_shape=(max_side, max_side))
+        if weight is not None and tuple(weight.shape) != tuple(out_ds.shape[1:]):
+            raise ValueError(f'bgu_upsampling: weight must have the size the fit runs at, {tuple(out_ds.shape[1:])} '
+                             f'(the target, or max_side x max_side when it is larger), got {tuple(weight.shape)}')
+        in_ds = imresize(u8_hwc_to_float(reference), output_shape=tuple(out_ds.shape[1:]))
+        gamma = bgu_fit(in_ds, out_ds, weight)
+        out = bgu_slice(gamma, reference, quantize=quantize)
+    return out if quantize else out.unsqueeze(0)
+
+
 # ---- writer -----------------------------------------------------------------------------------------------------------
 def save_rgb(u8_hwc, path):
     """Write one uint8 (H, W, 3) image with PIL's defaults -- what torchvision.utils.save_image writes for a batch of

@@ -450,12 +450,16 @@ class recoloringTrainer():
         it at the photo's size padded up to multiples of 2**pyramid_levels, as the reference does; `post_recoloring`
         then maps `original_image` (the photo, (H, W, 3) in [0, 1]) onto the colours of the unclamped network output
         with the Monge-Kantorovich transfer and overwrites the same file at the photo's size.  Both need a batch of
-        one (ValueError otherwise).  `resizing_method='BGU'` (an external Windows executable) raises
+        one (ValueError otherwise).  `resizing_method='BGU_native'` carries the result back with bilateral guided
+        upsampling instead (post.bgu_upsampling: the arithmetic of the reference's upsampling/BGU.m on the network's
+        8-bit output, without the JPEG round trip) and writes it at exactly the photo's size.
+        `resizing_method='BGU'`, which in the reference runs an external Windows executable, raises
         NotImplementedError."""
         upscale = resizing == 'upscaling'
-        if upscale and resizing_method != 'pyramid':
+        if upscale and resizing_method not in ('pyramid', 'BGU_native'):
             raise NotImplementedError(f"recoloringTrainer.evaluate: resizing_method={resizing_method!r} for 'upscaling' "
-                                      "(only 'pyramid' is implemented; BGU runs an external executable)")
+                                      "(implemented: 'pyramid' and 'BGU_native'; 'BGU' runs an external executable in "
+                                      "the reference -- its arithmetic is available here as 'BGU_native')")
         self.GAN.eval()
         if hist_batch is None or image_batch is None:
             batch = next(self.loader_evaluate)
@@ -485,7 +489,8 @@ class recoloringTrainer():
                 Image.open(output_name).resize((original_size[0], original_size[1])).save(output_name)
             if upscale or post_recoloring is True:
                 self._full_resolution(generated_images, output_name, upscale, pyramid_levels, swapping_levels,
-                                      level_blending, input_image_name, original_image, post_recoloring is True)
+                                      level_blending, input_image_name, original_image, post_recoloring is True,
+                                      resizing_method)
             if save_input is True:
                 save_image_grid(image_batch[:img_bt_sz] if multi else image_batch,
                                 str(self.results_dir / self.name / f'{str(num)}-input.{ext}'),
@@ -493,17 +498,21 @@ class recoloringTrainer():
         return generated_images
 
     def _full_resolution(self, generated_images, output_name, upscale, levels, swapping_levels, blending,
-                         input_image_name, original_image, recolor):
-        """The 'upscaling'/'pyramid' and post_recoloring branches of evaluate (ReHistoGAN/rehistoGAN.py:1142-1165) on
-        the kernels of include/hg_post.h; each writes one uint8 image through post.save_rgb."""
+                         input_image_name, original_image, recolor, method='pyramid'):
+        """The 'upscaling' ('pyramid' or 'BGU_native') and post_recoloring branches of evaluate
+        (ReHistoGAN/rehistoGAN.py:1142-1165) on the kernels of include/hg_post.h; each writes one uint8 image through
+        post.save_rgb."""
         from PIL import Image
         from . import post
         if upscale:
             with Image.open(input_image_name) as im:
                 ref = torch.from_numpy(np.array(im)).to(self.device)
-            out = post.pyramid_upsampling(generated_images, ref, levels=levels, swapping_levels=swapping_levels,
-                                          blending=blending)
-            post.save_rgb(post.float_to_u8_hwc(out[0]), output_name)
+            if method == 'BGU_native':
+                post.save_rgb(post.bgu_upsampling(generated_images, ref, quantize=True), output_name)
+            else:
+                out = post.pyramid_upsampling(generated_images, ref, levels=levels, swapping_levels=swapping_levels,
+                                              blending=blending)
+                post.save_rgb(post.float_to_u8_hwc(out[0]), output_name)
         if recolor:
             if original_image is None:
                 raise ValueError('recoloringTrainer.evaluate: post_recoloring needs original_image')

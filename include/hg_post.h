@@ -71,6 +71,37 @@ int hg_u8_hwc_to_f32(const uint8_t *x, float *out, int32_t C, int64_t HW, void *
 /* out (HW, C) uint8 = (uint8) clamp(x * 255 + 0.5, 0, 255) of x (C, HW) fp32. */
 int hg_f32_to_u8_hwc(const float *x, uint8_t *out, int32_t C, int64_t HW, void *stream);
 
+/* Bilateral guided upsampling.  The grid has gh x gw x gd vertices, each a 3 x 4 affine colour model gamma[i][j]
+ * (out_i = sum_j gamma[i][j] [r g b 1]_j).  Pixel (y, x) of an h x w image sits at cy = (y + 0.5)(gh - 1) / h,
+ * cx = (x + 0.5)(gw - 1) / w, cz = (0.25 r + 0.5 g + 0.25 b)(gd - 1) and weighs the 8 vertices around it trilinearly; a
+ * vertex outside the grid is dropped (luminance 1 has cz = gd - 1 and its upper vertex, of weight 0, is outside).
+ * Requires 2 <= gh, gw <= 4096, 2 <= gd <= 64, image sides <= 2^24.
+ *
+ * hg_bgu_normal: the three output channels share one normal matrix N = A^T W A over the n = gh gw gd 4 unknowns
+ * gamma[i][.] of a channel i.  Unknowns are ordered in S = max(gh, gw) slabs along the longer spatial axis (y when
+ * gh >= gw), and within a slab as a = (t * gd + z) * 4 + j with t the index along the other axis (T = min(gh, gw)
+ * vertices, m = T gd 4 unknowns per slab).  N is then block-tridiagonal:
+ *   diag[s][a][b] = N[(s, a), (s, b)]            (S, m, m)   row-major fp64
+ *   off [s][a][b] = N[(s + 1, a), (s, b)]        (S - 1, m, m)
+ *   rhs [i][s][a] = (A^T W out_i)[(s, a)]        (3, S, m)
+ * Every entry is written, the zeros between vertices more than 1 apart included.  in_ds, out_ds: fp32 planar (3, h, w);
+ * weight: fp32 (h, w), non-negative, or NULL for ones.  Accumulated in fp64 in a fixed order (per floor cell, then the
+ * up-to-four cells of a vertex pair), so repeats are bit-identical.  The smoothness terms are the caller's to add. */
+size_t hg_bgu_normal_workspace_bytes(int32_t gh, int32_t gw, int32_t gd);
+int hg_bgu_normal(const float *in_ds, const float *out_ds, const float *weight, int32_t h, int32_t w, int32_t gh,
+                  int32_t gw, int32_t gd, double *diag, double *off, double *rhs, void *workspace,
+                  size_t workspace_bytes, void *stream);
+
+/* out = the grid sliced at every pixel of `photo` and applied to it.  gamma: fp32 (gh, gw, gd, 3, 4) row-major, i.e.
+ * gamma[(((y * gw + x) * gd + z) * 3 + i) * 4 + j], 16-byte aligned.  photo: uint8 (H, W, 3) read as v / 255 with element
+ * strides xs_h, xs_w, xs_c (rows of a packed photo, xs_w = 3 and xs_c = 1, are read 12 bytes at a time whatever xs_h
+ * and W are).  out: uint8 (H, W, 3) contiguous = round(255 clip(v, 0, 1)), half away from zero (MATLAB imwrite of a
+ * double image), when out_u8 != 0; fp32 planar (3, H, W), not clipped, otherwise.  HG_EUNSUPPORTED when the grid is so
+ * fine against the photo (cells of about 6 pixels or fewer) that the vertices of a 256 x 4 pixel tile exceed 64 KiB of
+ * LDS. */
+int hg_bgu_slice(const float *gamma, int32_t gh, int32_t gw, int32_t gd, const uint8_t *photo, int64_t xs_h,
+                 int64_t xs_w, int64_t xs_c, void *out, int32_t out_u8, int32_t H, int32_t W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
