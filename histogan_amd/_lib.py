@@ -67,6 +67,10 @@ def _load():
     lib.hg_rgbuv_hist_fwd.argtypes = [PP, vp, vp, vp, vp, sz, vp]
     lib.hg_rgbuv_hist_bwd.restype = ctypes.c_int
     lib.hg_rgbuv_hist_bwd.argtypes = [PP, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.hg_rgbuv_hist_bwd_w_workspace_bytes.restype = ctypes.c_int
+    lib.hg_rgbuv_hist_bwd_w_workspace_bytes.argtypes = [PP, ctypes.POINTER(sz)]
+    lib.hg_rgbuv_hist_bwd_w.restype = ctypes.c_int
+    lib.hg_rgbuv_hist_bwd_w.argtypes = [PP, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.hg_hellinger_workspace_bytes.restype = sz
     lib.hg_hellinger_workspace_bytes.argtypes = [i64]
     lib.hg_hellinger_fwd_bwd.restype = ctypes.c_int
@@ -223,7 +227,7 @@ lib = _load()
 # every symbol include/hg_hist.h, hg_nets.h, hg_conv.h, hg_recolor.h, hg_augment.h, hg_linear.h, hg_wino.h and hg_post.h
 # declare
 EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg_rgbuv_hist_uses_proj_cache', 'hg_rgbuv_hist_fwd',
-           'hg_rgbuv_hist_bwd', 'hg_hellinger_workspace_bytes', 'hg_hellinger_fwd_bwd', 'hg_selftest_fastlog',
+           'hg_rgbuv_hist_bwd', 'hg_rgbuv_hist_bwd_w_workspace_bytes', 'hg_rgbuv_hist_bwd_w', 'hg_hellinger_workspace_bytes', 'hg_hellinger_fwd_bwd', 'hg_selftest_fastlog',
            'hg_modulate_fwd', 'hg_modulate_bwd', 'hg_demod_noise_lrelu_fwd', 'hg_demod_noise_lrelu_bwd',
            'hg_diffgrad_step', 'hg_diffgrad_step_size', 'hg_diffgrad_step_dev', 'hg_ema_update', 'hg_nets_workspace_bytes', 'hg_channel_sum', 'hg_lrelu_bwd_channel_sum', 'hg_demod_weight_term', 'hg_demod_style_grad', 'hg_demod_style_grad_workspace_bytes',
            'hg_conv_packed_elems', 'hg_conv_pack_weights', 'hg_conv_pack_weights_both', 'hg_conv_pack_blocks', 'hg_conv_pack_weights_multi', 'hg_conv2d_fwd', 'hg_conv2d_fwd_add', 'hg_modconv2d_fwd', 'hg_conv2d_workspace_bytes', 'hg_conv2d_plan', 'hg_conv2d_dgrad',

@@ -30,8 +30,8 @@
 #include "../../include/hg_hist.h"
 #include <cstdlib>
 
-#define HG_VERSION_NUM 104   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
-                             // 104: hg_bgu_normal, hg_bgu_slice (hg_post.h)
+#define HG_VERSION_NUM 105   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
+                             // 104: hg_bgu_normal, hg_bgu_slice (hg_post.h); 105: hg_rgbuv_hist_bwd_w (gradient of the weight map)
 
 // Settled schedule constants of the dense kernels (DESIGN.md sections 4 and 11 hold the measurements).
 constexpr int kFwdMfmaGroup = 12;    // k_hist_fwd at configs[1]: groups of 1: 505 us, 3: 498, 6: 473, 12: 465
@@ -72,6 +72,9 @@ struct DevParams {
   float4 *cache;            // optional [B][npix][2] float4: (a, b, c, Iy), (r, g, b, w) written by the forward, read by the backward
   const float *weight;      // optional per-pixel weight map (hg_hist_params.weight), element strides wsb / wsh / wsw
   long long wsb, wsh, wsw;
+  // hg_rgbuv_hist_bwd_w only (the WG instantiations): where the backward kernels leave dL/dw_n of histogram pixel n,
+  // [B][npix] -- grad_weight itself without a resize, else the map's plane of the resize adjoint's input
+  float *gw;
   int npix;
   double lo, hi, step;      // bins: i*step+lo, last == hi  (np.linspace)
   double inv_sigma_d;       // (double)(float)(1/sigma) -- pairs with inv_sigma
@@ -95,6 +98,20 @@ __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 
 // the relu's mask (x > 0) only removes the point x == 0 from the clamp's.
 __device__ __forceinline__ bool grad_mask(const DevParams &P, float raw) {
   return (P.pre_relu ? raw > 0.f : raw >= 0.f) && raw <= 1.f;
+}
+
+// Clamp mask of the weight map (stage 0 takes clamp(w, 0, 1)): torch.clamp's rule, both ends inclusive; pre_relu is about x only
+__device__ __forceinline__ bool weight_mask(float raw) { return raw >= 0.f && raw <= 1.f; }
+
+// Gradient of the weight map at histogram pixel n: v = m_n * A_n with A_n = sum_p k(u_p)^T Ghat_p k(v_p), the per-pixel sum
+// every backward kernel forms for dL/dIy, and m_n the pixel's non-map factor (Iy, 1 without intensity_scale, channel 0 for
+// HG_PROJ_DIRECT: what project() returns as iy).  Without a resize this is the map's own gradient: masked by its clamp.
+__device__ __forceinline__ void store_weight_grad(const DevParams &P, int b, int n, float v) {
+  if (P.mode == HG_RESIZE_NONE) {
+    const int ys = n / P.Ws, xs = n - ys * P.Ws;
+    if (!weight_mask(P.weight[(long long)b * P.wsb + ys * P.wsh + xs * P.wsw])) v = 0.f;
+  }
+  P.gw[(long long)b * P.npix + n] = v;
 }
 
 // Taps of the bilinear resize of histogram pixel (ys, xs): aten upsample_bilinear2d, align_corners=False:
@@ -592,7 +609,9 @@ __device__ __forceinline__ constexpr int beta0(int s) { return (s & 3) + 8 * ((s
 // as D[bin][pixel] MFMA tiles (A = Ghat from LDS, B = kernel values generated in registers), then
 //   dL/da = Iy * sum_i k'(a-b_i) Wa[i]   (same for b, c),   dL/dIy = 1/2 sum_i (ka Wa + kb Wb + kc Wc)[i]
 //   dL_R = da+db, dL_G = -da+dc, dL_B = -db-dc,   dx_c = dL_c/(x_c+1e-6) + dIy x_c/Iy   
-template <int T, int METHOD, bool GREEN, bool SHARE = false, bool WGT = false>
+// WG (with WGT): also store the weight map's gradient Iy * A_n, A_n = isum / 2 (every plane's bilinear form is counted twice
+// in isum, once from either side -- in the green and the thresholding branch too).
+template <int T, int METHOD, bool GREEN, bool SHARE = false, bool WGT = false, bool WG = false>
 __global__ __launch_bounds__(256, kBwdWaves) void k_hist_bwd(const DevParams P, const float *__restrict__ x,
                                                                 const float *__restrict__ gout,
                                                                 const float *__restrict__ hist,
@@ -988,6 +1007,9 @@ __global__ __launch_bounds__(256, kBwdWaves) void k_hist_bwd(const DevParams P, 
     if (valid && half == 1 && P.mode == HG_RESIZE_NONE) {
       for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
     }
+    if constexpr (WG) {
+      if (valid && half == 1) store_weight_grad(P, b, n, __fmul_rn(0.5f * isum, iy));
+    }
 #if HG_HIST_PROBE
     { HG_PROBE_T(pr3); p_state += pr1 - pr0; p_loop += pr2 - pr1; p_epi += pr3 - pr2; }
 #endif
@@ -1018,7 +1040,7 @@ __global__ __launch_bounds__(256, kBwdWaves) void k_hist_bwd(const DevParams P, 
 template <int RT>
 struct POps { float Au[RT], Av[RT]; float ku, kv; };
 
-template <int RT, int METHOD, bool WGT = false>
+template <int RT, int METHOD, bool WGT = false, bool WG = false>
 __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, const float *__restrict__ x,
                                                             const float *__restrict__ gout,
                                                             const float *__restrict__ hist,
@@ -1174,6 +1196,9 @@ __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, c
         } else {
           store_pixel_grad(P, xb, b, n, r_, g_, b_, iy, da, db, dc, P.intensity ? __fmul_rn(dIy, wn) : 0.f, gdst);
         }
+        if constexpr (WG) {   // dIy is the sum A_n over the planes (before the map's factor): dL/dw_n = m_n A_n
+          if (pi + 1 == nplanes) store_weight_grad(P, b, n, __fmul_rn(dIy, iy));
+        }
       }
       if (valid && half == 1 && pi + 1 == nplanes && P.mode == HG_RESIZE_NONE) {
         for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
@@ -1221,7 +1246,7 @@ __device__ __forceinline__ void kern_eval_d(const DevParams &P, float u, int i, 
   }
 }
 
-template <int METHOD>
+template <int METHOD, bool WG = false>
 __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, const float *__restrict__ x,
                                                          const float *__restrict__ gh, float *__restrict__ gdst) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1271,6 +1296,7 @@ __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, cons
       store_pixel_grad(P, xb, b, n, r_, g_, b_, iy, da, db, dc, dIy, gdst);
     if (P.mode == HG_RESIZE_NONE)
       for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
+    if constexpr (WG) store_weight_grad(P, b, n, __fmul_rn(isum, iy));
   }
 }
 
@@ -1561,6 +1587,9 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevPar
 
 // Backward of the thresholding histogram: the window has zero slope, so the only path to the pixel is the weight Iy:
 // dL/dIy = sum over planes of Ghat at the pixel's bin(s) -- a gather -- and dx_c = dL/dIy * x_c / Iy (store_pixel_grad).
+// WG: the weight map's gradient is that gather times the pixel's non-map factor -- also without intensity_scale, where the
+// colour gradient is identically zero.
+template <bool WG = false>
 __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const float *__restrict__ x,
                                                       const float *__restrict__ gh, float *__restrict__ gdst) {
   const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x, h = P.h;
@@ -1570,7 +1599,7 @@ __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const f
   sample_rgb(P, xb, n, r, g, bl);
   project(P, r, g, bl, a, bb, c, iy);
   float dIy = 0.f;
-  if (P.intensity) {
+  if (P.intensity || WG) {
     const double inv_step = P.step > 0.0 ? 1.0 / P.step : 0.0, w = P.half_eps * inv_step;
     const bool single = P.h > 1 && P.step > 2.0 * P.half_eps * (1.0 + 1e-9);
     for (int p = 0; p < 3; ++p) {
@@ -1591,6 +1620,10 @@ __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const f
           if (thr_hit(P, v, j)) dIy += G[i * h + j];
       }
     }
+  }
+  if constexpr (WG) {
+    store_weight_grad(P, b, n, __fmul_rn(dIy, iy));
+    if (!P.intensity) dIy = 0.f;
   }
   dIy = __fmul_rn(dIy, sample_weight(P, b, n));       // weight map: dL/dIy = w_n dL/d(w_n Iy)
   if (P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj(P, xb, b, n, r, g, bl, iy, 0.f, 0.f, dIy, gdst);
@@ -1728,8 +1761,9 @@ __global__ __launch_bounds__(1024) void k_thr_fwd_lean(const DevParams P, const 
 // One-launch backward: <G, out> is rebuilt per workgroup (2 x 48 KB from L2, as k_hist_bwd does) instead of a
 // k_hist_ghat launch + a Ghat buffer; the window has no slope, so the only path to the pixel is the weight Iy:
 // dL/dIy = sum_planes Ghat[bin] with Ghat = (G - <G,out>) / S' formed on the fly, dx_c = dL/dIy * x_c / Iy, clamp-masked.
-// Requires intensity_scale (without it the gradient is identically zero: the host clears grad_x instead).
-template <bool DIRECT, bool SYM>
+// Requires intensity_scale (without it the gradient is identically zero: the host clears grad_x instead) -- except WG, which
+// also stores the weight map's gradient Iy * sum_planes Ghat[bin] and then runs without intensity_scale too (colour gradient 0).
+template <bool DIRECT, bool SYM, bool WG = false>
 __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const float *__restrict__ x,
                                                        const float *__restrict__ gout, const float *__restrict__ hist,
                                                        const float *__restrict__ sums, float *__restrict__ gdst,
@@ -1795,7 +1829,7 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
   __syncthreads();
   const double inv_step = 1.0 / P.step;
   const ThrFast F = make_thr_fast(P);
-  auto pixel = [&](float r, float gg, float bl, float wn, float &dr, float &dg, float &db) __attribute__((always_inline)) {
+  auto pixel = [&](float r, float gg, float bl, float wn, float &dr, float &dg, float &db, float &gwn) __attribute__((always_inline)) {
     int idx[6];
     float iy;
     thr_lean_classify<SYM>(P, F, r, gg, bl, inv_step, exact_only, idx, iy);
@@ -1803,7 +1837,11 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
     if ((idx[0] | idx[1]) >= 0) dIy += gh[idx[0] * h + idx[1]];
     if ((idx[2] | idx[3]) >= 0) dIy += gh[hh + idx[2] * h + idx[3]];
     if ((idx[4] | idx[5]) >= 0) dIy += gh[2 * hh + idx[4] * h + idx[5]];
-    const float wgt = __fmul_rn(dIy, wn) / iy;           // weight map: dL/dIy = w_n dL/d(w_n Iy)
+    float wgt = __fmul_rn(dIy, wn) / iy;                 // weight map: dL/dIy = w_n dL/d(w_n Iy)
+    if constexpr (WG) {
+      gwn = __fmul_rn(dIy, iy);
+      if (!P.intensity) wgt = 0.f;
+    }
     dr = wgt * r; dg = wgt * gg; db = wgt * bl;
   };
   if constexpr (DIRECT) {
@@ -1817,10 +1855,16 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
         if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n + 4096);
       }
       float4 or4, og4, ob4;
-      pixel(clamp01(rc.x), clamp01(gc.x), clamp01(bc.x), clamp01(wc.x), or4.x, og4.x, ob4.x);
-      pixel(clamp01(rc.y), clamp01(gc.y), clamp01(bc.y), clamp01(wc.y), or4.y, og4.y, ob4.y);
-      pixel(clamp01(rc.z), clamp01(gc.z), clamp01(bc.z), clamp01(wc.z), or4.z, og4.z, ob4.z);
-      pixel(clamp01(rc.w), clamp01(gc.w), clamp01(bc.w), clamp01(wc.w), or4.w, og4.w, ob4.w);
+      [[maybe_unused]] float4 ow4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      pixel(clamp01(rc.x), clamp01(gc.x), clamp01(bc.x), clamp01(wc.x), or4.x, og4.x, ob4.x, ow4.x);
+      pixel(clamp01(rc.y), clamp01(gc.y), clamp01(bc.y), clamp01(wc.y), or4.y, og4.y, ob4.y, ow4.y);
+      pixel(clamp01(rc.z), clamp01(gc.z), clamp01(bc.z), clamp01(wc.z), or4.z, og4.z, ob4.z, ow4.z);
+      pixel(clamp01(rc.w), clamp01(gc.w), clamp01(bc.w), clamp01(wc.w), or4.w, og4.w, ob4.w, ow4.w);
+      if constexpr (WG) {   // DIRECT: no resize, so this is grad_weight itself -- masked by the map's clamp, one 16-byte store
+        *reinterpret_cast<float4 *>(P.gw + (long long)b * P.npix + n) =
+            make_float4(weight_mask(wc.x) ? ow4.x : 0.f, weight_mask(wc.y) ? ow4.y : 0.f, weight_mask(wc.z) ? ow4.z : 0.f,
+                        weight_mask(wc.w) ? ow4.w : 0.f);
+      }
       // clamp mask of RGBuvHistBlock.py:76, decided on the raw value
       auto m = [&](float raw, float v) { return grad_mask(P, raw) ? v : 0.f; };
       or4 = make_float4(m(rc.x, or4.x), m(rc.y, or4.y), m(rc.z, or4.z), m(rc.w, or4.w));
@@ -1835,9 +1879,11 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
   } else {
     for (int m = n0 + threadIdx.x; m < n1; m += 1024) {
       float r, gg, bl, dr, dg, db;
+      [[maybe_unused]] float gwn = 0.f;
       sample_rgb(P, xb, m, r, gg, bl);
-      pixel(r, gg, bl, sample_weight(P, b, m), dr, dg, db);
+      pixel(r, gg, bl, sample_weight(P, b, m), dr, dg, db, gwn);
       store_rgb_grad(P, xb, b, m, dr, dg, db, gdst);
+      if constexpr (WG) store_weight_grad(P, b, m, gwn);
       if (P.mode == HG_RESIZE_NONE)
         for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + m] = 0.f;
     }
@@ -1942,6 +1988,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_rbf_fwd(const DevPar
 
 // Backward of the truncated RBF histogram: the generic backward's two mat-vecs per plane restricted to the (2R+1)^2
 // support (kernel value and slope in fp64, as k_hist_bwd_generic).
+template <bool WG = false>
 __global__ __launch_bounds__(256) void k_hist_rbf_bwd(const DevParams P, const float *__restrict__ x,
                                                       const float *__restrict__ gh, float *__restrict__ gdst, int R) {
   const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x, h = P.h;
@@ -1994,12 +2041,17 @@ __global__ __launch_bounds__(256) void k_hist_rbf_bwd(const DevParams P, const f
   else store_pixel_grad(P, xb, b, n, r, g, bl, iy, da, db, dc, dIy, gdst);
   if (P.mode == HG_RESIZE_NONE)
     for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
+  if constexpr (WG) store_weight_grad(P, b, n, __fmul_rn(isum, iy));
 }
 
 // Adjoint of the bilinear resize (deterministic gather) fused with the clamp mask.
 // grad_x[b][c][y][x] = mask(x) * sum_{Y,X} wy(Y->y) wx(X->x) gxs[b][c][Y][X]
+// WG: one more plane, the weight map's -- P.gw [B][npix] gathered with the same taps into grad_weight (B, H, W), masked by
+// the clamp of the input-resolution map, read through its own strides.
+template <bool WG = false>
 __global__ __launch_bounds__(256) void k_bilinear_adjoint(const DevParams P, const float *__restrict__ x,
-                                                          const float *__restrict__ gxs, float *__restrict__ gx) {
+                                                          const float *__restrict__ gxs, float *__restrict__ gx,
+                                                          float *__restrict__ gweight) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long total = (long long)P.B * P.H * P.W;
   if (idx >= total) return;
@@ -2012,7 +2064,9 @@ __global__ __launch_bounds__(256) void k_bilinear_adjoint(const DevParams P, con
   const int Xlo = max(0, (int)floorf(((float)xx - 0.5f) * inv_w - 0.5f) - 1);
   const int Xhi = min(P.Ws - 1, (int)ceilf(((float)xx + 1.5f) * inv_w - 0.5f) + 1);
   float acc[3] = {0.f, 0.f, 0.f};
+  [[maybe_unused]] float accw = 0.f;
   const float *gb = gxs + (long long)b * 3 * P.npix;
+  [[maybe_unused]] const float *gwb = WG ? P.gw + (long long)b * P.npix : nullptr;
   for (int Y = Ylo; Y <= Yhi; ++Y) {
     const float sy = fmaxf(__fsub_rn(__fmul_rn(P.rscale_h, (float)Y + 0.5f), 0.5f), 0.f);
     const int y0 = min((int)sy, P.H - 1);
@@ -2036,6 +2090,7 @@ __global__ __launch_bounds__(256) void k_bilinear_adjoint(const DevParams P, con
       acc[0] = fmaf(w, gb[o], acc[0]);
       acc[1] = fmaf(w, gb[o + P.npix], acc[1]);
       acc[2] = fmaf(w, gb[o + 2LL * P.npix], acc[2]);
+      if constexpr (WG) accw = fmaf(w, gwb[o], accw);
     }
   }
   const float *xb = x + (long long)b * P.sb + yy * P.sh + xx * P.sw;
@@ -2045,12 +2100,19 @@ __global__ __launch_bounds__(256) void k_bilinear_adjoint(const DevParams P, con
     const float xv = xb[c * P.sc];
     dst[(long long)c * P.H * P.W] = grad_mask(P, xv) ? acc[c] : 0.f;
   }
+  if constexpr (WG) {
+    const float raw = P.weight[(long long)b * P.wsb + yy * P.wsh + xx * P.wsw];
+    gweight[((long long)b * P.H + yy) * P.W + xx] = weight_mask(raw) ? accw : 0.f;
+  }
 }
 
 // Adjoint of index_select sampling (RGBuvHistBlock.py:82-89): scatter-add (indices may repeat when
-// the image side is shorter than h), fused with the clamp mask.  grad_x pre-zeroed.
+// the image side is shorter than h), fused with the clamp mask.  grad_x pre-zeroed.  WG: the weight map's plane (P.gw) is
+// scattered the same way into grad_weight (pre-zeroed too).
+template <bool WG = false>
 __global__ __launch_bounds__(256) void k_sampling_adjoint(const DevParams P, const float *__restrict__ x,
-                                                          const float *__restrict__ gxs, float *__restrict__ gx) {
+                                                          const float *__restrict__ gxs, float *__restrict__ gx,
+                                                          float *__restrict__ gweight) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long total = (long long)P.B * P.npix;
   if (idx >= total) return;
@@ -2064,6 +2126,10 @@ __global__ __launch_bounds__(256) void k_sampling_adjoint(const DevParams P, con
     const float xv = xb[c * P.sc];
     if (grad_mask(P, xv)) atomicAdd(dst + (long long)c * P.H * P.W, gxs[((long long)b * 3 + c) * P.npix + n]);
   }
+  if constexpr (WG) {
+    if (weight_mask(P.weight[(long long)b * P.wsb + yy * P.wsh + xx * P.wsw]))
+      atomicAdd(gweight + ((long long)b * P.H + yy) * P.W + xx, P.gw[(long long)b * P.npix + n]);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2074,6 +2140,7 @@ struct Plan {
   int nparts;                // reduce blocks per image
   int S_bwd, rounds;         // backward: WGs per image, 32-pixel rounds per wave
   size_t slab_bytes, part_bytes, gh_bytes, gxs_bytes;
+  size_t gws_bytes;          // hg_rgbuv_hist_bwd_w, resized: the weight map's plane of the resize adjoint's input, [B][npix]
   int planes_rt;             // > 0: backward on k_hist_bwd_planes<planes_rt> (see bwd_planes_rt)
 };
 
@@ -2197,6 +2264,7 @@ Plan make_plan(const hg_hist_params *p) {
   else
     pl.gh_bytes = ((p->lo != -p->hi) || pl.nbd != 1 || p->projection || sparse_path(p)) ? ((size_t)p->B * n_per_img * sizeof(float) + 255) / 256 * 256 : 256;
   pl.gxs_bytes = (p->resize_mode == HG_RESIZE_NONE) ? 0 : ((size_t)p->B * 3 * npix * sizeof(float) + 255) / 256 * 256;
+  pl.gws_bytes = (p->resize_mode == HG_RESIZE_NONE) ? 0 : ((size_t)p->B * npix * sizeof(float) + 255) / 256 * 256;
   return pl;
 }
 
@@ -2210,6 +2278,7 @@ DevParams make_dev(const hg_hist_params *p) {
   d.cache = (float4 *)p->proj_cache;
   d.weight = p->weight;
   d.wsb = p->weight ? p->weight_stride_b : 0; d.wsh = p->weight ? p->weight_stride_h : 0; d.wsw = p->weight ? p->weight_stride_w : 0;
+  d.gw = nullptr;
   d.h = p->h; d.P = (p->green_only || p->projection) ? 1 : 3; d.method = p->method;
   d.intensity = p->intensity_scale ? 1 : 0; d.green = (p->green_only || p->projection) ? 1 : 0;
   d.npix = p->Hs * p->Ws;
@@ -2264,7 +2333,8 @@ void launch_fwd_w(const dim3 grid, const dim3 block, size_t lds, hipStream_t st,
 template <int T, int METHOD, bool GREEN, bool SHARE>
 void launch_bwd_w(const dim3 grid, const dim3 block, size_t lds, hipStream_t st, const DevParams &d, const float *x,
                   const float *gout, const float *hist, const float *sums, float *gdst, int rounds) {
-  if (d.weight) hipLaunchKernelGGL((k_hist_bwd<T, METHOD, GREEN, SHARE, true>), grid, block, lds, st, d, x, gout, hist, sums, gdst, rounds);
+  if (d.gw) hipLaunchKernelGGL((k_hist_bwd<T, METHOD, GREEN, SHARE, true, true>), grid, block, lds, st, d, x, gout, hist, sums, gdst, rounds);
+  else if (d.weight) hipLaunchKernelGGL((k_hist_bwd<T, METHOD, GREEN, SHARE, true>), grid, block, lds, st, d, x, gout, hist, sums, gdst, rounds);
   else hipLaunchKernelGGL((k_hist_bwd<T, METHOD, GREEN, SHARE, false>), grid, block, lds, st, d, x, gout, hist, sums, gdst, rounds);
 }
 
@@ -2333,21 +2403,21 @@ int launch_bwd_t(const DevParams &d, const Plan &pl, const float *x, const float
   }
 }
 
-template <int RT, bool WGT>
+template <int RT, bool WGT, bool WG = false>
 int launch_bwd_planes_rtw(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
                           const float *sums, float *part, float *gdst, hipStream_t st) {
   const dim3 grid(pl.S_bwd, d.B), block(256);
   const size_t lds = (size_t)(32 * RT) * (32 * RT + 1) * sizeof(float);
-  const void *kern = (d.method == HG_METHOD_RBF) ? (const void *)k_hist_bwd_planes<RT, HG_METHOD_RBF, WGT>
-                                                 : (const void *)k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC, WGT>;
+  const void *kern = (d.method == HG_METHOD_RBF) ? (const void *)k_hist_bwd_planes<RT, HG_METHOD_RBF, WGT, WG>
+                                                 : (const void *)k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC, WGT, WG>;
   if (lds > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
   if (d.method == HG_METHOD_RBF)
-    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_RBF, WGT>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
+    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_RBF, WGT, WG>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
   else
-    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC, WGT>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
+    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC, WGT, WG>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
   HG_LAUNCH_CHECK();
   return HG_OK;
 }
@@ -2355,6 +2425,7 @@ int launch_bwd_planes_rtw(const DevParams &d, const Plan &pl, const float *x, co
 template <int RT>
 int launch_bwd_planes_rt(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
                          const float *sums, float *part, float *gdst, hipStream_t st) {
+  if (d.gw) return launch_bwd_planes_rtw<RT, true, true>(d, pl, x, gout, hist, sums, part, gdst, st);
   return d.weight ? launch_bwd_planes_rtw<RT, true>(d, pl, x, gout, hist, sums, part, gdst, st)
                   : launch_bwd_planes_rtw<RT, false>(d, pl, x, gout, hist, sums, part, gdst, st);
 }
@@ -2488,17 +2559,20 @@ int hg_rgbuv_hist_fwd(const hg_hist_params *p, const float *x, float *hist_out, 
   return HG_OK;
 }
 
-int hg_rgbuv_hist_bwd(const hg_hist_params *p, const float *x, const float *grad_out, const float *hist_out,
-                      const float *sum_out, float *grad_x, void *workspace, size_t workspace_bytes, void *stream) {
-  const int rc = validate(p);
-  if (rc) return rc;
+// The backward behind both entry points.  grad_weight == NULL: hg_rgbuv_hist_bwd, the instantiations and launches it always
+// had.  Otherwise (hg_rgbuv_hist_bwd_w) the WG instantiations also leave dL/dw per histogram pixel in d.gw: grad_weight itself
+// without a resize, else [B][npix] floats at the end of the workspace, which the resize adjoint takes as one more plane.
+static int hist_bwd_impl(const hg_hist_params *p, const float *x, const float *grad_out, const float *hist_out,
+                         const float *sum_out, float *grad_x, float *grad_weight, void *workspace, size_t workspace_bytes,
+                         void *stream) {
   if (!x || !grad_out || !hist_out || !sum_out || !grad_x || !workspace) return HG_EINVAL;
+  const bool wg = grad_weight != nullptr;
   const Plan pl = make_plan(p);
-  if (workspace_bytes < pl.gxs_bytes + pl.gh_bytes) return HG_EWORKSPACE;
+  if (workspace_bytes < pl.gxs_bytes + pl.gh_bytes + (wg ? pl.gws_bytes : 0)) return HG_EWORKSPACE;
   const bool sym = (p->lo == -p->hi);
   const bool generic = !sym || pl.nbd != 1 || p->projection != HG_PROJ_RGBUV;
   hipStream_t st = (hipStream_t)stream;
-  const DevParams d = make_dev(p);
+  DevParams d = make_dev(p);
   float *gxs = (float *)workspace;
   const size_t gx_bytes = (size_t)d.B * d.C * d.H * d.W * sizeof(float);
   float *gdst = grad_x;
@@ -2508,22 +2582,35 @@ int hg_rgbuv_hist_bwd(const hg_hist_params *p, const float *x, const float *grad
       hipError_t e = hipMemsetAsync(grad_x, 0, gx_bytes, st);
       if (e != hipSuccess) return (int)e;
     }
+    if (wg && d.mode == HG_RESIZE_SAMPLING) {   // scatter-add destination, like grad_x
+      hipError_t e = hipMemsetAsync(grad_weight, 0, (size_t)d.B * d.H * d.W * sizeof(float), st);
+      if (e != hipSuccess) return (int)e;
+    }
   }
-  if (thr_lean(p) && !p->intensity_scale && d.mode == HG_RESIZE_NONE) {
+  if (wg) d.gw = (d.mode == HG_RESIZE_NONE) ? grad_weight : (float *)((char *)workspace + pl.gxs_bytes + pl.gh_bytes);
+  if (thr_lean(p) && !p->intensity_scale && d.mode == HG_RESIZE_NONE && !wg) {
     // a 0/1 window has no slope and there is no weight to differentiate: the gradient is identically zero
     hipError_t e = hipMemsetAsync(grad_x, 0, gx_bytes, st);
     if (e != hipSuccess) return (int)e;
-  } else if (thr_lean(p) && p->intensity_scale) {
-    const bool ex = thr_exact_only(), dir = thr_direct(p, x, grad_x);
+  } else if (thr_lean(p) && (p->intensity_scale || wg)) {
+    // (16-byte stores of the map's gradient need grad_weight aligned like grad_x)
+    const bool ex = thr_exact_only(), dir = thr_direct(p, x, grad_x) && !(wg && ((uintptr_t)grad_weight & 15));
     const dim3 grid(pl.S_fwd, d.B), block(1024);
     const size_t blds = (size_t)3 * d.h * d.h * sizeof(float);
+    const void *lk = wg ? (dir ? (sym ? (const void *)k_thr_bwd_lean<true, true, true> : (const void *)k_thr_bwd_lean<true, false, true>)
+                               : (sym ? (const void *)k_thr_bwd_lean<false, true, true> : (const void *)k_thr_bwd_lean<false, false, true>))
+                        : (dir ? (sym ? (const void *)k_thr_bwd_lean<true, true> : (const void *)k_thr_bwd_lean<true, false>)
+                               : (sym ? (const void *)k_thr_bwd_lean<false, true> : (const void *)k_thr_bwd_lean<false, false>));
     if (blds > 48 * 1024) {
-      const void *lk = dir ? (sym ? (const void *)k_thr_bwd_lean<true, true> : (const void *)k_thr_bwd_lean<true, false>)
-                           : (sym ? (const void *)k_thr_bwd_lean<false, true> : (const void *)k_thr_bwd_lean<false, false>);
       hipError_t e = hipFuncSetAttribute(lk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
       if (e != hipSuccess) return (int)e;
     }
-    if (dir && sym) hipLaunchKernelGGL((k_thr_bwd_lean<true, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
+    if (wg) {
+      if (dir && sym) hipLaunchKernelGGL((k_thr_bwd_lean<true, true, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
+      else if (dir) hipLaunchKernelGGL((k_thr_bwd_lean<true, false, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
+      else if (sym) hipLaunchKernelGGL((k_thr_bwd_lean<false, true, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
+      else hipLaunchKernelGGL((k_thr_bwd_lean<false, false, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
+    } else if (dir && sym) hipLaunchKernelGGL((k_thr_bwd_lean<true, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
     else if (dir) hipLaunchKernelGGL((k_thr_bwd_lean<true, false>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
     else if (sym) hipLaunchKernelGGL((k_thr_bwd_lean<false, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
     else hipLaunchKernelGGL((k_thr_bwd_lean<false, false>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
@@ -2533,8 +2620,11 @@ int hg_rgbuv_hist_bwd(const hg_hist_params *p, const float *x, const float *grad
     hipLaunchKernelGGL(k_hist_ghat, dim3(d.B), dim3(1024), 0, st, grad_out, hist_out, sum_out, gh, d.P * d.h * d.h);
     HG_LAUNCH_CHECK();
     const int R = rbf_radius(p);
-    if (R) hipLaunchKernelGGL(k_hist_rbf_bwd, dim3((d.npix + 255) / 256, d.B), dim3(256), 0, st, d, x, gh, gdst, R);
-    else hipLaunchKernelGGL(k_hist_thr_bwd, dim3((d.npix + 255) / 256, d.B), dim3(256), 0, st, d, x, gh, gdst);
+    const dim3 grid((d.npix + 255) / 256, d.B), block(256);
+    if (R && wg) hipLaunchKernelGGL(k_hist_rbf_bwd<true>, grid, block, 0, st, d, x, gh, gdst, R);
+    else if (R) hipLaunchKernelGGL(k_hist_rbf_bwd<false>, grid, block, 0, st, d, x, gh, gdst, R);
+    else if (wg) hipLaunchKernelGGL(k_hist_thr_bwd<true>, grid, block, 0, st, d, x, gh, gdst);
+    else hipLaunchKernelGGL(k_hist_thr_bwd<false>, grid, block, 0, st, d, x, gh, gdst);
     HG_LAUNCH_CHECK();
   } else if (pl.planes_rt) {
     float *part = (float *)((char *)workspace + pl.gxs_bytes);
@@ -2554,24 +2644,67 @@ int hg_rgbuv_hist_bwd(const hg_hist_params *p, const float *x, const float *grad
     const dim3 grid((d.npix + 63) / 64, d.B), block(64);
     switch (d.method) {
       case HG_METHOD_THRESHOLDING:
-        hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_THRESHOLDING>), grid, block, lds, st, d, x, gh, gdst); break;
+        if (wg) hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_THRESHOLDING, true>), grid, block, lds, st, d, x, gh, gdst);
+        else hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_THRESHOLDING>), grid, block, lds, st, d, x, gh, gdst);
+        break;
       case HG_METHOD_RBF:
-        hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_RBF>), grid, block, lds, st, d, x, gh, gdst); break;
+        if (wg) hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_RBF, true>), grid, block, lds, st, d, x, gh, gdst);
+        else hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_RBF>), grid, block, lds, st, d, x, gh, gdst);
+        break;
       default:
-        hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_INVERSE_QUADRATIC>), grid, block, lds, st, d, x, gh, gdst); break;
+        if (wg) hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_INVERSE_QUADRATIC, true>), grid, block, lds, st, d, x, gh, gdst);
+        else hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_INVERSE_QUADRATIC>), grid, block, lds, st, d, x, gh, gdst);
+        break;
     }
     HG_LAUNCH_CHECK();
   }
   if (d.mode == HG_RESIZE_BILINEAR) {
     const long long total = (long long)d.B * d.H * d.W;
-    hipLaunchKernelGGL(k_bilinear_adjoint, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d, x, gxs, grad_x);
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    if (wg) hipLaunchKernelGGL(k_bilinear_adjoint<true>, grid, block, 0, st, d, x, gxs, grad_x, grad_weight);
+    else hipLaunchKernelGGL(k_bilinear_adjoint<false>, grid, block, 0, st, d, x, gxs, grad_x, grad_weight);
     HG_LAUNCH_CHECK();
   } else if (d.mode == HG_RESIZE_SAMPLING) {
     const long long total = (long long)d.B * d.npix;
-    hipLaunchKernelGGL(k_sampling_adjoint, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d, x, gxs, grad_x);
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    if (wg) hipLaunchKernelGGL(k_sampling_adjoint<true>, grid, block, 0, st, d, x, gxs, grad_x, grad_weight);
+    else hipLaunchKernelGGL(k_sampling_adjoint<false>, grid, block, 0, st, d, x, gxs, grad_x, grad_weight);
     HG_LAUNCH_CHECK();
   }
   return HG_OK;
+}
+
+int hg_rgbuv_hist_bwd(const hg_hist_params *p, const float *x, const float *grad_out, const float *hist_out,
+                      const float *sum_out, float *grad_x, void *workspace, size_t workspace_bytes, void *stream) {
+  const int rc = validate(p);
+  if (rc) return rc;
+  return hist_bwd_impl(p, x, grad_out, hist_out, sum_out, grad_x, nullptr, workspace, workspace_bytes, stream);
+}
+
+// a differentiable map must own every element: a zero stride (broadcast) would make the elements' gradients collide
+static int validate_wgrad(const hg_hist_params *p) {
+  const int rc = validate(p);
+  if (rc) return rc;
+  if (!p->weight) return HG_EINVAL;
+  if (p->weight_stride_b == 0 || p->weight_stride_h == 0 || p->weight_stride_w == 0) return HG_EUNSUPPORTED;
+  return HG_OK;
+}
+
+int hg_rgbuv_hist_bwd_w_workspace_bytes(const hg_hist_params *p, size_t *bytes) {
+  const int rc = validate_wgrad(p);
+  if (rc) return rc;
+  const Plan pl = make_plan(p);
+  if (bytes) *bytes = pl.gxs_bytes + pl.gh_bytes + pl.gws_bytes;
+  return HG_OK;
+}
+
+int hg_rgbuv_hist_bwd_w(const hg_hist_params *p, const float *x, const float *grad_out, const float *hist_out,
+                        const float *sum_out, float *grad_x, float *grad_weight, void *workspace, size_t workspace_bytes,
+                        void *stream) {
+  const int rc = validate_wgrad(p);
+  if (rc) return rc;
+  if (!grad_weight) return HG_EINVAL;
+  return hist_bwd_impl(p, x, grad_out, hist_out, sum_out, grad_x, grad_weight, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

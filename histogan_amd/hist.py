@@ -46,12 +46,13 @@ class HistConfig:
         self.lo, self.hi = float(hb[0]), float(hb[1])
 
 
-def check_weight(x, weight):
+def check_weight(x, weight, weight_grad=False):
     """Validate a per-pixel weight map for x (B, C, H, W) and return it as a detached fp32 (B, H, W) view (no copy for
-    fp32 input: the kernels take any strides).  (B, 1, H, W) or (B, H, W); it is a constant of the histogram."""
+    fp32 input: the kernels take any strides).  (B, 1, H, W) or (B, H, W); it is a constant of the histogram -- unless
+    weight_grad: then a map that requires grad is accepted and the view stays in its autograd graph."""
     if not torch.is_tensor(weight):
         raise ValueError(f'weight must be a tensor, got {type(weight).__name__}')
-    if weight.requires_grad:
+    if weight.requires_grad and not weight_grad:
         raise ValueError('weight requires grad, but the histogram produces no gradient for its weight map '
                          '(pass weight.detach())')
     B, _, H, W = x.shape
@@ -114,21 +115,23 @@ _stream = raw_stream           # the former name, still bound: the C-ABI tests o
 class RGBuvHistFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg, pre_relu=False, weight=None):
-        # weight: None or a map already validated by rgbuv_hist (check_weight): fp32 (B, H, W) on x's device, no grad
+        # weight: None or a map already validated by rgbuv_hist (check_weight): fp32 (B, H, W) on x's device.  It is an
+        # autograd input like x: a map that requires grad (weight_grad=True callers only) gets its gradient in backward
         need_gpu(x, 'RGBuvHistFunction', _FOUND)
         x = x.detach()
         if x.dtype != torch.float32:
             x = x.float()
         p, keep = _make_params(x, cfg, pre_relu, weight)
         ctx.pre_relu = pre_relu
-        ctx.weight = weight                   # a constant of the backward (never differentiated): kept alive, not saved
+        ctx.weight = None if weight is None else weight.detach()      # kept alive for the backward call, not saved
+        ctx.weight_grad = weight is not None and ctx.needs_input_grad[3]
         fwd_b, _ = _ws_bytes(p)
         with on_device(x.device):
             # per-pixel projection cache for the backward (32 B per histogram pixel): only when a gradient will be asked
             # for and only when the dense MFMA kernels will run (the scatter paths -- thresholding, narrow RBF --
             # re-classify pixels cheaply and ignore it)
             cache = None
-            if ctx.needs_input_grad[0] and lib.hg_rgbuv_hist_uses_proj_cache(ctypes.byref(p)) == 1:
+            if (ctx.needs_input_grad[0] or ctx.weight_grad) and lib.hg_rgbuv_hist_uses_proj_cache(ctypes.byref(p)) == 1:
                 cache = torch.empty((p.B, p.Hs * p.Ws, 8), dtype=torch.float32, device=x.device)
                 p.proj_cache = cache.data_ptr()
             ctx.cache = cache
@@ -150,7 +153,13 @@ class RGBuvHistFunction(torch.autograd.Function):
         p, keep = _make_params(x, cfg, ctx.pre_relu, ctx.weight)
         if ctx.cache is not None:
             p.proj_cache = ctx.cache.data_ptr()
-        _, bwd_b = _ws_bytes(p)
+        if ctx.weight_grad:
+            nb = ctypes.c_size_t(0)
+            check(lib.hg_rgbuv_hist_bwd_w_workspace_bytes(ctypes.byref(p), ctypes.byref(nb)),
+                  'hg_rgbuv_hist_bwd_w_workspace_bytes')
+            bwd_b = nb.value
+        else:
+            _, bwd_b = _ws_bytes(p)
         g = grad_out.detach()
         if g.dtype != torch.float32:
             g = g.float()
@@ -158,15 +167,32 @@ class RGBuvHistFunction(torch.autograd.Function):
         with on_device(x.device):
             gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
             ws = workspace(bwd_b, x.device)
+            if ctx.weight_grad:               # (B, H, W), the shape forward was given; autograd undoes the caller's views
+                gw = torch.empty(ctx.weight.shape, dtype=torch.float32, device=x.device)
+                check(lib.hg_rgbuv_hist_bwd_w(ctypes.byref(p), x.data_ptr(), g.data_ptr(), out.data_ptr(),
+                                              sums.data_ptr(), gx.data_ptr(), gw.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              raw_stream(x.device)), 'hg_rgbuv_hist_bwd_w')
+                return gx, None, None, gw
             check(lib.hg_rgbuv_hist_bwd(ctypes.byref(p), x.data_ptr(), g.data_ptr(), out.data_ptr(),
                                         sums.data_ptr(), gx.data_ptr(), ws.data_ptr(), ws.numel(),
                                         raw_stream(x.device)), 'hg_rgbuv_hist_bwd')
         return gx, None, None, None
 
 
-def run_block(x, cfg, device, what, pre_relu=False, weight=None):
+class WeightGradCall:
+    """Mixin of the drop-in histogram modules: `block(x, ..., weight=w, weight_grad=True)`.  The keyword is taken by the
+    call, not by forward() (whose parameter list stays the reference's plus the documented extensions), and runs the
+    module's forward_weight_grad(); without it the call is nn.Module's, unchanged."""
+
+    def __call__(self, *args, weight_grad=False, **kwargs):
+        if not weight_grad:
+            return super().__call__(*args, **kwargs)
+        return self.forward_weight_grad(*args, **kwargs)
+
+
+def run_block(x, cfg, device, what, pre_relu=False, weight=None, weight_grad=False):
     """forward() of the drop-in histogram modules: resolves the module's `device` argument the way the reference does
-    ('cuda', 'cpu', an ordinal, a torch.device).
+    ('cuda', 'cpu', an ordinal, a torch.device).  weight_grad: the weight map is a differentiable input (rgbuv_hist_wgrad).
 
     device='cpu' is what the reference's Dataset uses inside forked DataLoader workers (histoGAN/histoGAN.py:263-266,
     296-302): that call runs `hist_cpu.hist_cpu` -- PyTorch CPU ops only, no HIP call, no GPU memory (SURVEY.md
@@ -177,12 +203,12 @@ def run_block(x, cfg, device, what, pre_relu=False, weight=None):
         from .hist_cpu import hist_cpu
         if weight is not None and torch.is_tensor(weight) and weight.is_cuda:
             weight = weight.cpu()
-        return hist_cpu(x if not x.is_cuda else x.cpu(), cfg, pre_relu, weight)
+        return hist_cpu(x if not x.is_cuda else x.cpu(), cfg, pre_relu, weight, weight_grad=weight_grad)
     if not x.is_cuda:
         x = x.to(dev)
     if weight is not None and torch.is_tensor(weight) and weight.device != x.device:
         weight = weight.to(x.device)          # a CPU weight map follows x to the module's GPU
-    return rgbuv_hist(x, cfg, pre_relu, weight)
+    return _rgbuv_hist(x, cfg, pre_relu, weight, weight_grad)
 
 
 def rgbuv_hist(x, cfg, pre_relu=False, weight=None):
@@ -191,13 +217,30 @@ def rgbuv_hist(x, cfg, pre_relu=False, weight=None):
     weight: optional per-pixel weight map (B, 1, H, W) or (B, H, W), taken as clamp(weight, 0, 1) and resized with the
     image; pixel n counts with weight_n * I_y,n.  A constant: the gradient goes to x only, and a weight that requires
     grad is refused (ValueError).  None = every pixel counts (bit-identical to a map of ones)."""
+    return _rgbuv_hist(x, cfg, pre_relu, weight, False)
+
+
+def rgbuv_hist_wgrad(x, cfg, pre_relu=False, weight=None):
+    """rgbuv_hist with the weight map as a differentiable input (`weight_grad=True` of the modules): the map may require
+    grad and receives dL/dw -- per histogram pixel (I_y or its stand-in) * sum over planes of k(u)^T Ghat k(v), through the
+    adjoint of the resize, and 0 outside the clamp (w < 0, w > 1).  The gradient comes back in the map's own shape; a map
+    expanded over an axis is materialised first and autograd reduces its gradient.  The gradient for x is unchanged."""
+    return _rgbuv_hist(x, cfg, pre_relu, weight, True)
+
+
+def _rgbuv_hist(x, cfg, pre_relu, weight, weight_grad):
     if weight is None:
+        if weight_grad:
+            raise ValueError('weight_grad=True needs a weight map (weight=None)')
         return RGBuvHistFunction.apply(x, cfg, pre_relu)
     if x.dim() != 4 or x.shape[1] < 3:
         raise ValueError(f'expected (B, C>=3, H, W) input, got {tuple(x.shape)}')
-    weight = check_weight(x, weight)
+    weight = check_weight(x, weight, weight_grad)
     if weight.device != x.device:
         raise ValueError(f'weight is on {weight.device}, the input on {x.device}')
+    if weight_grad and weight.requires_grad and 0 in weight.stride():
+        # a broadcast map has no element of its own per pixel for the kernels to write a gradient to
+        weight = weight.clone(memory_format=torch.contiguous_format)
     return RGBuvHistFunction.apply(x, cfg, pre_relu, weight)
 
 

@@ -71,11 +71,11 @@ def _kernel(coord, bins, cfg):
     return k.to(torch.float32)
 
 
-def _check_weight(x, weight):
+def _check_weight(x, weight, weight_grad=False):
     """The rules of histogan_amd.hist.check_weight (this module must not import the HIP binding)."""
     if not torch.is_tensor(weight):
         raise ValueError(f'weight must be a tensor, got {type(weight).__name__}')
-    if weight.requires_grad:
+    if weight.requires_grad and not weight_grad:
         raise ValueError('weight requires grad, but the histogram produces no gradient for its weight map '
                          '(pass weight.detach())')
     B, _, H, W = x.shape
@@ -89,10 +89,11 @@ def _check_weight(x, weight):
     return weight if weight.dtype == torch.float32 else weight.float()
 
 
-def hist_cpu(x, cfg, pre_relu=False, weight=None):
+def hist_cpu(x, cfg, pre_relu=False, weight=None, weight_grad=False):
     """x: CPU float (B, C>=3, H, W) -> CPU float32 (B, 3|1, h, h), L1-normalised per image (:224-228).
     weight: optional per-pixel weight map (B, 1, H, W) or (B, H, W), clamp(weight, 0, 1), resized with the image; pixel n
-    counts with weight_n * I_y,n (the definition of the HIP kernels, include/hg_hist.h).  A constant: no gradient for it."""
+    counts with weight_n * I_y,n (the definition of the HIP kernels, include/hg_hist.h).  A constant: no gradient for it --
+    unless weight_grad=True: then the map may require grad and simply stays in the autograd graph of these torch ops."""
     if x.is_cuda:
         raise RuntimeError('hist_cpu: GPU tensor on the CPU path')
     if x.dim() != 4 or x.shape[1] < 3:
@@ -100,7 +101,9 @@ def hist_cpu(x, cfg, pre_relu=False, weight=None):
     if x.dtype != torch.float32:
         x = x.float()
     if weight is not None:
-        weight = _check_weight(x, weight)
+        weight = _check_weight(x, weight, weight_grad)
+    elif weight_grad:
+        raise ValueError('weight_grad=True needs a weight map (weight=None)')
     if pre_relu:
         x = F.relu(x)
     xs = _resize(x, cfg, weight)

@@ -308,6 +308,16 @@ def _alpha_weight(images):
     return torch.where(empty, torch.ones_like(w), w)
 
 
+def _alpha_weight_grad(images):
+    """_alpha_weight with the generated alpha kept in the autograd graph (hist_alpha_grad=True): the histogram loss then also
+    moves the mask, through the weight map's gradient.  The raw channel is passed -- the histogram clamps it itself and masks
+    the gradient where alpha is below 0 or above 1.  The same rule for an image whose alpha is nowhere positive: uniform
+    ones, chosen by torch.where, so such an image sends no gradient to its alpha."""
+    a = images[:, 3]
+    empty = a.detach().amax(dim=(1, 2), keepdim=True) <= 0
+    return torch.where(empty, torch.ones_like(a), a)
+
+
 class Trainer():
     d_loss, g_loss, h_loss = _lazy_field('d_loss'), _lazy_field('g_loss'), _lazy_field('h_loss')
     last_gp_loss, q_loss, pl_mean = _lazy_field('last_gp_loss'), _lazy_field('q_loss'), _lazy_field('pl_mean')
@@ -317,7 +327,7 @@ class Trainer():
                  save_every=1000, trunc_psi=0.6, fp16=False, fq_layers=[], fq_dict_size=256, attn_layers=[],
                  hist_method='inverse-quadratic', hist_resizing='sampling', hist_sigma=0.02, hist_bin=64,
                  hist_insz=150, aug_prob=0.0, dataset_aug_prob=0.0, aug_types=None, rng='device',
-                 hist_alpha_weight=False, *args, **kwargs):
+                 hist_alpha_weight=False, hist_alpha_grad=False, *args, **kwargs):
         from histogram_classes.RGBuvHistBlock import RGBuvHistBlock
         # opt-in (transparent=True only): histograms weigh every pixel by its alpha -- the targets by the image's alpha
         # channel (FolderData), the generator-side histogram of the G loss by the generated alpha, detached -- so the
@@ -325,6 +335,11 @@ class Trainer():
         if hist_alpha_weight and not transparent:
             raise ValueError('hist_alpha_weight=True needs transparent=True (there is no alpha channel to weigh by)')
         self.hist_alpha_weight = bool(hist_alpha_weight)
+        # opt-in on top of it: the generated alpha is a differentiable input of the generator-side histogram, so the
+        # histogram loss reaches channel 3 of the generator output (the colour loss can then move the mask too)
+        if hist_alpha_grad and not hist_alpha_weight:
+            raise ValueError('hist_alpha_grad=True needs hist_alpha_weight=True (there is no weight map to differentiate)')
+        self.hist_alpha_grad = bool(hist_alpha_grad)
         if aug_types is None:
             aug_types = ['translation', 'cutout']
         self.GAN_params = [args, kwargs]
@@ -771,7 +786,10 @@ class Trainer():
             self._mark('g_forward_joined_d_updated')
             fake_output, _ = Disc(aug(generated_images))
             self._mark('g_phase_d_forward')
-            if self.hist_alpha_weight:   # weigh by the generated alpha (a constant of this histogram: no gradient through it)
+            if self.hist_alpha_grad:     # weigh by the generated alpha, with its graph: the loss also moves the mask
+                generated_histograms = self.histBlock(generated_images, pre_relu=True,
+                                                      weight=_alpha_weight_grad(generated_images), weight_grad=True)
+            elif self.hist_alpha_weight:   # weigh by the generated alpha (a constant of this histogram: no gradient through it)
                 generated_histograms = self.histBlock(generated_images, pre_relu=True,
                                                       weight=_alpha_weight(generated_images))
             else:

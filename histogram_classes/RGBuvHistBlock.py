@@ -7,12 +7,12 @@ gfx950 kernels of histogan_amd/csrc/hg_hist.hip through the C ABI of include/hg_
 import torch
 import torch.nn as nn
 
-from histogan_amd.hist import HistConfig, run_block
+from histogan_amd.hist import HistConfig, WeightGradCall, run_block
 
 EPS = 1e-6
 
 
-class RGBuvHistBlock(nn.Module):
+class RGBuvHistBlock(WeightGradCall, nn.Module):
   def __init__(self, h=64, insz=150, resizing='interpolation',
                method='inverse-quadratic', sigma=0.02, intensity_scale=True,
                hist_boundary=None, green_only=False, device='cuda'):
@@ -55,5 +55,12 @@ class RGBuvHistBlock(nn.Module):
     weight (an extension too): optional per-pixel weight map (B, 1, H, W) or (B, H, W) -- a mask, an alpha channel --
     taken as clamp(weight, 0, 1) and resized with the image; pixel n counts with weight_n * I_y,n (weight_n alone
     without intensity_scale).  A constant: the gradient goes to x only (exactly 0 where the weight is 0), and a weight
-    that requires grad raises ValueError.  None: every pixel counts, bit-identical to a map of ones."""
+    that requires grad raises ValueError.  None: every pixel counts, bit-identical to a map of ones.
+    Calling the module with weight_grad=True -- block(x, weight=w, weight_grad=True) -- runs forward_weight_grad."""
     return run_block(x, self._config(), self.device, 'RGBuvHistBlock', pre_relu, weight)
+
+  def forward_weight_grad(self, x, pre_relu=False, weight=None):
+    """forward() with the weight map as a differentiable input: the map may require grad and receives the histogram's
+    gradient (in its own shape; exactly 0 where the map is below 0 or above 1, the clamp's mask); the gradient for x is
+    the same as forward()'s.  weight=None raises ValueError."""
+    return run_block(x, self._config(), self.device, 'RGBuvHistBlock', pre_relu, weight, weight_grad=True)

@@ -5,12 +5,12 @@ include/hg_hist.h: one plane, shared clamp / resize / soft-binning / normalisati
 import torch
 import torch.nn as nn
 
-from histogan_amd.hist import HistConfig, run_block
+from histogan_amd.hist import HistConfig, WeightGradCall, run_block
 
 EPS = 1e-6
 
 
-class rgChromaHistBlock(nn.Module):
+class rgChromaHistBlock(WeightGradCall, nn.Module):
   def __init__(self, h=64, insz=150, resizing='interpolation',
                method='inverse-quadratic', sigma=0.02, intensity_scale=False,
                hist_boundary=None, device='cuda'):
@@ -33,12 +33,20 @@ class rgChromaHistBlock(nn.Module):
     else:
       self.sigma = sigma
 
+  def _config(self):
+    return HistConfig(h=self.h, insz=self.insz, resizing=self.resizing, method=self.method,
+                      sigma=getattr(self, 'sigma', 0.02), intensity_scale=self.intensity_scale,
+                      hist_boundary=list(self.hist_boundary), projection='rgchroma')
+
   def forward(self, x, weight=None):
     """x: float (B, C>=3, H, W) -> float32 (B, 1, h, h), L1-normalised per image, on `device`.
     weight (an extension; the reference signature is forward(x)): optional per-pixel weight map (B, 1, H, W) or
     (B, H, W), taken as clamp(weight, 0, 1) and resized with the image; pixel n counts with
-    weight_n * I_y,n (weight_n alone without intensity_scale).  A constant: no gradient is produced for it."""
-    cfg = HistConfig(h=self.h, insz=self.insz, resizing=self.resizing, method=self.method,
-                     sigma=getattr(self, 'sigma', 0.02), intensity_scale=self.intensity_scale,
-                     hist_boundary=list(self.hist_boundary), projection='rgchroma')
-    return run_block(x, cfg, self.device, 'rgChromaHistBlock', weight=weight)
+    weight_n * I_y,n (weight_n alone without intensity_scale).  A constant: no gradient is produced for it.
+    Calling the module with weight_grad=True -- block(x, weight=w, weight_grad=True) -- runs forward_weight_grad."""
+    return run_block(x, self._config(), self.device, 'rgChromaHistBlock', weight=weight)
+
+  def forward_weight_grad(self, x, weight=None):
+    """forward() with the weight map as a differentiable input: the map may require grad and receives the histogram's
+    gradient (in its own shape; exactly 0 where the map is below 0 or above 1); weight=None raises ValueError."""
+    return run_block(x, self._config(), self.device, 'rgChromaHistBlock', weight=weight, weight_grad=True)

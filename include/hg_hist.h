@@ -82,9 +82,10 @@ typedef struct hg_hist_params {
    * + x*weight_stride_w], element strides, any layout; a stride of 0 broadcasts the map over that axis (one map for the
    * whole batch: weight_stride_b = 0).  Values are taken as clamp(w, 0, 1).  Stage 0 resizes the map exactly like a
    * colour channel (same bilinear taps / same row_idx, col_idx gather); histogram pixel n then enters with the weight
-   * w_n * Iy_n (w_n * 1 without intensity_scale, w_n * channel 0 for HG_PROJ_DIRECT).  The map is a constant of the
-   * backward: grad_x is the gradient with w fixed (exactly 0 where w_n == 0), no gradient is produced for it, and the
-   * backward call must be given the same map as the forward.  Every kernel path honours it. */
+   * w_n * Iy_n (w_n * 1 without intensity_scale, w_n * channel 0 for HG_PROJ_DIRECT).  grad_x is the gradient with w fixed
+   * (exactly 0 where w_n == 0); hg_rgbuv_hist_bwd treats the map as a constant, hg_rgbuv_hist_bwd_w (since version 105)
+   * also produces its gradient.  Either backward call must be given the same map as the forward.  Every kernel path
+   * honours it. */
   const float *weight;
   int64_t weight_stride_b, weight_stride_h, weight_stride_w;
 } hg_hist_params;
@@ -119,6 +120,19 @@ int hg_rgbuv_hist_fwd(const hg_hist_params *p, const float *x, float *hist_out, 
 int hg_rgbuv_hist_bwd(const hg_hist_params *p, const float *x, const float *grad_out,
                       const float *hist_out, const float *sum_out, float *grad_x,
                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* Backward with the gradient of the weight map (since version 105): hg_rgbuv_hist_bwd, same grad_x bit for bit, plus
+ * grad_weight (B, H, W) contiguous, fully written: dL/dw at the INPUT resolution of the map -- per histogram pixel
+ * m_n * sum_p k(u_p)^T Ghat_p k(v_p) with m_n the pixel's non-map factor (Iy, 1 without intensity_scale, channel 0 for
+ * HG_PROJ_DIRECT), taken through the adjoint of the resize and masked by the map's clamp (passes where 0 <= w <= 1, both
+ * ends inclusive; exactly 0 elsewhere).  Thresholding included (a gather of Ghat at the pixel's bins), also without
+ * intensity_scale, where grad_x is identically zero.  p->weight == NULL or grad_weight == NULL: HG_EINVAL; a map with a
+ * zero stride (broadcast): HG_EUNSUPPORTED -- expand it into memory first and reduce the gradient afterwards.
+ * Workspace: hg_rgbuv_hist_bwd_w_workspace_bytes (the resized paths carry one more plane than hg_rgbuv_hist_bwd). */
+int hg_rgbuv_hist_bwd_w_workspace_bytes(const hg_hist_params *p, size_t *bytes);
+int hg_rgbuv_hist_bwd_w(const hg_hist_params *p, const float *x, const float *grad_out, const float *hist_out,
+                        const float *sum_out, float *grad_x, float *grad_weight, void *workspace,
+                        size_t workspace_bytes, void *stream);
 
 /* Hellinger histogram loss, histoGAN/histoGAN.py:957-960:
  *   loss = alpha / sqrt(2) * sqrt( sum_{b,p,i,j} (sqrt(t) - sqrt(g))^2 ) / B
