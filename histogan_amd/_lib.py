@@ -15,6 +15,9 @@ LIB_PATH = os.path.join(_PKG, 'libhistogan_hip' + ('_' + _TAG if _TAG else '') +
 HG_METHOD = {'thresholding': 0, 'RBF': 1, 'inverse-quadratic': 2}
 HG_RESIZE_NONE, HG_RESIZE_BILINEAR, HG_RESIZE_SAMPLING = 0, 1, 2
 HG_PROJ = {'rgbuv': 0, 'rgchroma': 1, 'direct': 2}
+# hg_hist_route.fwd / .bwd (the HG_ROUTE_FWD_* / HG_ROUTE_BWD_* enums of include/hg_hist.h), by value
+HG_ROUTE_FWD = ('DENSE', 'THR_SCATTER', 'THR_LEAN', 'RBF_SCATTER')
+HG_ROUTE_BWD = ('MIRRORED', 'PLANES', 'GENERIC', 'THR_GATHER', 'RBF_GATHER', 'THR_LEAN', 'ZERO')
 
 
 class HgHistParams(ctypes.Structure):
@@ -41,6 +44,12 @@ class HgHistParams(ctypes.Structure):
     ]
 
 
+class HgHistRoute(ctypes.Structure):
+    """struct hg_hist_route (include/hg_hist.h): what hg_rgbuv_hist_route fills in."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'fwd', 'bwd', 'fwd_slices', 'bwd_workgroups', 'planes_rt',
+                                              'rbf_radius', 'uses_proj_cache')]
+
+
 class GlinLayer(ctypes.Structure):
     """struct hg_glin_layer (include/hg_linear.h)."""
     _fields_ = [('x', ctypes.c_void_p), ('w', ctypes.c_void_p), ('b', ctypes.c_void_p), ('y', ctypes.c_void_p),
@@ -63,6 +72,8 @@ def _load():
     lib.hg_rgbuv_hist_workspace_bytes.argtypes = [PP, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     lib.hg_rgbuv_hist_uses_proj_cache.restype = ctypes.c_int
     lib.hg_rgbuv_hist_uses_proj_cache.argtypes = [PP]
+    lib.hg_rgbuv_hist_route.restype = ctypes.c_int
+    lib.hg_rgbuv_hist_route.argtypes = [PP, ctypes.c_int, ctypes.POINTER(HgHistRoute)]
     lib.hg_rgbuv_hist_fwd.restype = ctypes.c_int
     lib.hg_rgbuv_hist_fwd.argtypes = [PP, vp, vp, vp, vp, sz, vp]
     lib.hg_rgbuv_hist_bwd.restype = ctypes.c_int
@@ -226,7 +237,7 @@ lib = _load()
 
 # every symbol include/hg_hist.h, hg_nets.h, hg_conv.h, hg_recolor.h, hg_augment.h, hg_linear.h, hg_wino.h and hg_post.h
 # declare
-EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg_rgbuv_hist_uses_proj_cache', 'hg_rgbuv_hist_fwd',
+EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg_rgbuv_hist_uses_proj_cache', 'hg_rgbuv_hist_route', 'hg_rgbuv_hist_fwd',
            'hg_rgbuv_hist_bwd', 'hg_rgbuv_hist_bwd_w_workspace_bytes', 'hg_rgbuv_hist_bwd_w', 'hg_hellinger_workspace_bytes', 'hg_hellinger_fwd_bwd', 'hg_selftest_fastlog',
            'hg_modulate_fwd', 'hg_modulate_bwd', 'hg_demod_noise_lrelu_fwd', 'hg_demod_noise_lrelu_bwd',
            'hg_diffgrad_step', 'hg_diffgrad_step_size', 'hg_diffgrad_step_dev', 'hg_ema_update', 'hg_nets_workspace_bytes', 'hg_channel_sum', 'hg_lrelu_bwd_channel_sum', 'hg_demod_weight_term', 'hg_demod_style_grad', 'hg_demod_style_grad_workspace_bytes',
@@ -247,6 +258,13 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
 
 class HgError(RuntimeError):
     pass
+
+
+def hist_route(p, weight_grad=False):
+    """hg_rgbuv_hist_route for the HgHistParams `p`: the filled HgHistRoute (host only, no launch)."""
+    r = HgHistRoute(struct_size=ctypes.sizeof(HgHistRoute))
+    check(lib.hg_rgbuv_hist_route(ctypes.byref(p), int(weight_grad), ctypes.byref(r)), 'hg_rgbuv_hist_route')
+    return r
 
 
 def check(rc, what):

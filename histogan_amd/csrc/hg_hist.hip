@@ -30,8 +30,9 @@
 #include "../../include/hg_hist.h"
 #include <cstdlib>
 
-#define HG_VERSION_NUM 105   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
-                             // 104: hg_bgu_normal, hg_bgu_slice (hg_post.h); 105: hg_rgbuv_hist_bwd_w (gradient of the weight map)
+#define HG_VERSION_NUM 106   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
+                             // 104: hg_bgu_normal, hg_bgu_slice (hg_post.h); 105: hg_rgbuv_hist_bwd_w (gradient of the weight map);
+                             // 106: hg_rgbuv_hist_route
 
 // Settled schedule constants of the dense kernels (DESIGN.md sections 4 and 11 hold the measurements).
 constexpr int kFwdMfmaGroup = 12;    // k_hist_fwd at configs[1]: groups of 1: 505 us, 3: 498, 6: 473, 12: 465
@@ -2134,14 +2135,27 @@ __global__ __launch_bounds__(256) void k_sampling_adjoint(const DevParams P, con
 
 // ------------------------------------------------------------------------------------------------
 // host side
+
+// Which kernel families a call runs on (the HG_ROUTE_* of include/hg_hist.h; DESIGN.md section 4 has the table).
+// make_route decides it once per entry-point call; workspace sizes, launches and hg_rgbuv_hist_route only read it.
+struct Route {
+  int fwd, bwd;
+  int rbf_R;                 // RBF_SCATTER / RBF_GATHER: support radius in bins
+  int planes_rt;             // PLANES: k_hist_bwd_planes<planes_rt>, 32-bin row tiles
+  bool all3;                 // scatter forwards: every plane's 64-bit grid in LDS at once (else plane after plane)
+  bool sym;                  // lo == -hi
+  bool exact_only;           // lean kernels, HG_THR_EXACT=1: every window decision by the fp64 path
+};
+
 struct Plan {
+  Route rt;
   int T, BLK, nbd, HP;
   int S_fwd, chunk;          // forward: splits per image, pixels per wave (multiple of 64)
   int nparts;                // reduce blocks per image
-  int S_bwd, rounds;         // backward: WGs per image, 32-pixel rounds per wave
-  size_t slab_bytes, part_bytes, gh_bytes, gxs_bytes;
+  int S_bwd, rounds;         // MFMA backwards: WGs per image, 32-pixel rounds per wave
+  int bwd_wgs;               // workgroups per image of the backward kernel rt.bwd names (0: ZERO launches none)
+  size_t slab_bytes, tot_bytes, gh_bytes, gxs_bytes;
   size_t gws_bytes;          // hg_rgbuv_hist_bwd_w, resized: the weight map's plane of the resize adjoint's input, [B][npix]
-  int planes_rt;             // > 0: backward on k_hist_bwd_planes<planes_rt> (see bwd_planes_rt)
 };
 
 int validate(const hg_hist_params *p) {
@@ -2162,15 +2176,18 @@ int validate(const hg_hist_params *p) {
   return HG_OK;
 }
 
-// thresholding runs on the scatter kernels when the h x h 64-bit LDS grid fits (h <= 140)
-inline bool thr_scatter(const hg_hist_params *p) {
-  return p->method == HG_METHOD_THRESHOLDING && (size_t)p->h * p->h * 8 <= 156 * 1024;
+// a differentiable map must own every element: a zero stride (broadcast) would make the elements' gradients collide
+int validate_wgrad(const hg_hist_params *p) {
+  const int rc = validate(p);
+  if (rc) return rc;
+  if (!p->weight) return HG_EINVAL;
+  if (p->weight_stride_b == 0 || p->weight_stride_h == 0 || p->weight_stride_w == 0) return HG_EUNSUPPORTED;
+  return HG_OK;
 }
 
 // RBF: support radius in bins beyond which exp(-d^2/sigma^2) < 1e-12; 0 = use the dense MFMA path
 inline int rbf_radius(const hg_hist_params *p) {
-  if (p->method != HG_METHOD_RBF || p->h < 2 || (size_t)p->h * p->h * 8 > 156 * 1024) return 0;
-  if (const char *e = getenv("HG_RBF_DENSE")) if (atoi(e)) return 0;     // A/B switch for measurements
+  if (p->h < 2) return 0;
   const double step = (p->hi - p->lo) / (double)(p->h - 1);
   if (!(step > 0.0)) return 0;
   const double r = 5.2565 * p->sigma / step;          // sqrt(-ln 1e-12) = 5.2565
@@ -2178,25 +2195,68 @@ inline int rbf_radius(const hg_hist_params *p) {
   return (R >= 1 && R <= HG_RBF_RMAX) ? R : 0;
 }
 
-inline bool sparse_path(const hg_hist_params *p) { return thr_scatter(p) || rbf_radius(p) > 0; }
-
-// HG_THR_EXACT=1: every window decision by the fp64 path (A/B switch of the fast classification)
-inline bool thr_exact_only() {
-  if (const char *e = getenv("HG_THR_EXACT")) return atoi(e) != 0;
-  return false;
-}
-
-// The lean scatter kernels (k_thr_fwd_lean / k_thr_bwd_lean) apply to: RGB-uv, three planes, `single` windows (narrower
-// than the bin spacing: every symmetric boundary), all three 64-bit grids in LDS at once (h <= 79).
-inline bool thr_lean(const hg_hist_params *p) {
-  if (!thr_scatter(p) || p->projection != HG_PROJ_RGBUV || p->green_only || p->h < 2) return false;
-  if ((size_t)3 * p->h * p->h * 8 > 150 * 1024) return false;
+// `single` windows: narrower than the bin spacing, so a value falls into at most one bin (every symmetric boundary)
+inline bool thr_single(const hg_hist_params *p) {
+  if (p->h < 2) return false;
   const double step = (p->hi - p->lo) / (double)(p->h - 1);
   const double half_eps = ((p->lo < 0 ? -p->lo : p->lo) + (p->hi < 0 ? -p->hi : p->hi)) / (double)p->h / 2.0;
   return step > 2.0 * half_eps * (1.0 + 1e-9);
 }
 
-// no resize, contiguous planes, 16-byte aligned rows of four pixels: the float4 variant
+// The one place the dispatch rule lives, and the one reader of the three A/B switches (read on every call):
+//   HG_RBF_DENSE=1   narrow RBF on the dense MFMA kernels instead of the truncated scatter / gather pair
+//   HG_THR_EXACT=1   lean kernels: every window decision by the fp64 path (A/B switch of the fast classification)
+//   HG_BWD_PLANES    1: the symmetric h <= 64 RGB-uv backward on k_hist_bwd_planes too; 0: never k_hist_bwd_planes
+//                    (k_hist_bwd where it applies, else k_hist_bwd_generic); unset or anything else: the rule below
+// nbd: bin blocks per axis of the dense kernels (1 for h <= 64).  weight_grad: the call is hg_rgbuv_hist_bwd_w.
+Route make_route(const hg_hist_params *p, int nbd, bool weight_grad) {
+  Route r = {};
+  r.sym = p->lo == -p->hi;
+  const bool rgbuv3 = p->projection == HG_PROJ_RGBUV && !p->green_only;     // three planes
+  const size_t grid = (size_t)p->h * p->h * 8;                              // one plane's 64-bit LDS grid
+  const bool grid_fits = grid <= 156 * 1024;                                // h <= 141
+  r.all3 = grid * (rgbuv3 ? 3 : 1) <= 150 * 1024;                           // three planes: h <= 80
+  // forward.  The scatter kernels take thresholding and a narrow RBF while one grid fits; the lean pair of them applies
+  // to RGB-uv, three planes, `single` windows, all three grids in LDS at once.
+  r.fwd = HG_ROUTE_FWD_DENSE;
+  if (p->method == HG_METHOD_THRESHOLDING && grid_fits) {
+    r.fwd = (rgbuv3 && r.all3 && thr_single(p)) ? HG_ROUTE_FWD_THR_LEAN : HG_ROUTE_FWD_THR_SCATTER;
+  } else if (p->method == HG_METHOD_RBF && grid_fits) {
+    const char *e = getenv("HG_RBF_DENSE");
+    if (!(e && atoi(e))) r.rbf_R = rbf_radius(p);
+    if (r.rbf_R) r.fwd = HG_ROUTE_FWD_RBF_SCATTER;
+  }
+  // backward
+  switch (r.fwd) {
+    case HG_ROUTE_FWD_THR_LEAN: {
+      const char *e = getenv("HG_THR_EXACT");
+      r.exact_only = e && atoi(e) != 0;
+      // a 0/1 window has no slope: without intensity_scale and without a map to differentiate the gradient is identically
+      // zero (a resized call still goes through the gather and the resize adjoint)
+      if (p->intensity_scale || weight_grad) r.bwd = HG_ROUTE_BWD_THR_LEAN;
+      else r.bwd = (p->resize_mode == HG_RESIZE_NONE) ? HG_ROUTE_BWD_ZERO : HG_ROUTE_BWD_THR_GATHER;
+      break;
+    }
+    case HG_ROUTE_FWD_THR_SCATTER: r.bwd = HG_ROUTE_BWD_THR_GATHER; break;
+    case HG_ROUTE_FWD_RBF_SCATTER: r.bwd = HG_ROUTE_BWD_RBF_GATHER; break;
+    default: {
+      // k_hist_bwd merges mirrored bins: symmetric boundary, one bin block (h <= 64), RGB-uv.  k_hist_bwd_planes takes the
+      // other smooth-kernel cases up to h = 128; k_hist_bwd_generic the rest (dense thresholding, h > 128).
+      const bool mirrored = r.sym && nbd == 1 && p->projection == HG_PROJ_RGBUV;
+      bool planes = false;
+      if (p->method != HG_METHOD_THRESHOLDING && p->h <= 128) {
+        planes = !mirrored;
+        if (const char *e = getenv("HG_BWD_PLANES")) { if (atoi(e) == 1) planes = true; else if (atoi(e) == 0) planes = false; }
+      }
+      r.bwd = planes ? HG_ROUTE_BWD_PLANES : mirrored ? HG_ROUTE_BWD_MIRRORED : HG_ROUTE_BWD_GENERIC;
+      if (planes) r.planes_rt = (p->h + 31) / 32;
+    }
+  }
+  return r;
+}
+
+// no resize, contiguous planes, 16-byte aligned rows of four pixels: the float4 variant of the lean kernels (it depends on
+// the pointers, so it is a launch-time refinement of the THR_LEAN routes)
 inline bool thr_direct(const hg_hist_params *p, const float *x, const float *gx) {
   const long long npix = (long long)p->H * p->W;
   // a weight map takes the 16-byte loads too: rows contiguous like the image's (a batch stride of 0 is fine)
@@ -2206,32 +2266,24 @@ inline bool thr_direct(const hg_hist_params *p, const float *x, const float *gx)
          (p->stride_c & 3) == 0 && (p->stride_b & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)gx & 15) == 0;
 }
 
-// Which backward kernel?  0: k_hist_bwd (symmetric boundary, h <= 64, RGB-uv) or, for thresholding beyond the scatter
-// path / h > 128, k_hist_bwd_generic.  RT > 0: k_hist_bwd_planes<RT> -- smooth kernels with an asymmetric boundary,
-// 64 < h <= 128, or a one-plane projection.  HG_BWD_PLANES=1 sends the symmetric h <= 64 case there too (A/B runs,
-// and the parity test of one MFMA formulation against the other).
-inline int bwd_planes_rt(const hg_hist_params *p, int nbd) {
-  if (p->method == HG_METHOD_THRESHOLDING || sparse_path(p) || p->h > 128) return 0;
-  bool want = (p->lo != -p->hi) || nbd != 1 || p->projection != HG_PROJ_RGBUV;
-  if (const char *e = getenv("HG_BWD_PLANES")) { if (atoi(e) == 1) want = true; else if (atoi(e) == 0) want = false; }
-  return want ? (p->h + 31) / 32 : 0;
-}
-
 // workgroup target of the dense forward / backward pixel split (profiles/r04_hist_wgs_sweep.txt: 512 ... 2048 swept, 512 best)
 constexpr long long kDenseWgTarget = 512;
 
-Plan make_plan(const hg_hist_params *p) {
+inline size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+Plan make_plan(const hg_hist_params *p, bool weight_grad) {
   Plan pl;
   pl.T = (p->h <= 32) ? 1 : 2;
   pl.BLK = 32 * pl.T;
   pl.nbd = (p->h + pl.BLK - 1) / pl.BLK;
   pl.HP = pl.nbd * pl.BLK;
+  pl.rt = make_route(p, pl.nbd, weight_grad);
   const long long npix = (long long)p->Hs * p->Ws;
   const int P = (p->green_only || p->projection) ? 1 : 3;
   // forward: aim at ~2 workgroups per CU (256 CUs), >= 64 pixels per wave
   const long long wg_fixed = (long long)p->B * pl.nbd * pl.nbd;
-  // the scatter kernel keeps up to 98 KB of LDS grids: one workgroup per CU is all that fits, more only add slabs
-  const long long target = sparse_path(p) ? 256 : kDenseWgTarget;
+  // the scatter kernels keep up to 98 KB of LDS grids: one workgroup per CU is all that fits, more only add slabs
+  const long long target = (pl.rt.fwd == HG_ROUTE_FWD_DENSE) ? kDenseWgTarget : 256;
   long long S = (target + wg_fixed - 1) / wg_fixed;
   const long long maxS = (npix + 255) / 256;
   if (S > maxS) S = maxS;
@@ -2243,11 +2295,10 @@ Plan make_plan(const hg_hist_params *p) {
   pl.chunk = (int)chunk;
   const long long n_per_img = (long long)P * p->h * p->h;
   pl.nparts = (int)((n_per_img + 1023) / 1024);
-  pl.slab_bytes = ((size_t)p->B * S * n_per_img * sizeof(float) + 255) / 256 * 256;
-  pl.part_bytes = ((size_t)p->B * pl.nparts * sizeof(float) + 255) / 256 * 256;
+  pl.slab_bytes = round256((size_t)p->B * S * n_per_img * sizeof(float));
   // slab_tot[B][S (x bin blocks)] doubles for k_hist_finish
-  pl.part_bytes = ((size_t)p->B * S * pl.nbd * pl.nbd * sizeof(double) + 255) / 256 * 256;
-  // backward: 1 workgroup per CU, rounds of 32 pixels per wave
+  pl.tot_bytes = round256((size_t)p->B * S * pl.nbd * pl.nbd * sizeof(double));
+  // MFMA backwards: 1 workgroup per CU, rounds of 32 pixels per wave
   const long long rounds_total = (npix + 31) / 32;
   long long Sb = (kDenseWgTarget + p->B - 1) / p->B;
   const long long maxSb = (rounds_total + 3) / 4;
@@ -2257,14 +2308,28 @@ Plan make_plan(const hg_hist_params *p) {
   Sb = (rounds_total + 4 * rpw - 1) / (4 * rpw);
   pl.S_bwd = (int)Sb;
   pl.rounds = (int)rpw;
-  // generic backward only (h > 64 or asymmetric boundary): Ghat in natural layout
-  pl.planes_rt = bwd_planes_rt(p, pl.nbd);
-  if (pl.planes_rt)   // (da, db, dc, dIy) per pixel, carried from plane to plane
-    pl.gh_bytes = (P == 3) ? ((size_t)p->B * 4 * npix * sizeof(float) + 255) / 256 * 256 : 256;
-  else
-    pl.gh_bytes = ((p->lo != -p->hi) || pl.nbd != 1 || p->projection || sparse_path(p)) ? ((size_t)p->B * n_per_img * sizeof(float) + 255) / 256 * 256 : 256;
-  pl.gxs_bytes = (p->resize_mode == HG_RESIZE_NONE) ? 0 : ((size_t)p->B * 3 * npix * sizeof(float) + 255) / 256 * 256;
-  pl.gws_bytes = (p->resize_mode == HG_RESIZE_NONE) ? 0 : ((size_t)p->B * npix * sizeof(float) + 255) / 256 * 256;
+  // what the backward kernel keeps behind the resize adjoint's input, and its workgroups per image
+  const size_t ghat_bytes = round256((size_t)p->B * n_per_img * sizeof(float));      // Ghat in natural layout
+  switch (pl.rt.bwd) {
+    case HG_ROUTE_BWD_MIRRORED:
+      pl.gh_bytes = 256; pl.bwd_wgs = pl.S_bwd; break;
+    case HG_ROUTE_BWD_PLANES:     // (da, db, dc, dIy) per pixel, carried from plane to plane
+      pl.gh_bytes = (P == 3) ? round256((size_t)p->B * 4 * npix * sizeof(float)) : 256; pl.bwd_wgs = pl.S_bwd; break;
+    case HG_ROUTE_BWD_GENERIC:
+      pl.gh_bytes = ghat_bytes; pl.bwd_wgs = (int)((npix + 63) / 64); break;
+    case HG_ROUTE_BWD_THR_GATHER:
+    case HG_ROUTE_BWD_RBF_GATHER:
+      pl.gh_bytes = ghat_bytes; pl.bwd_wgs = (int)((npix + 255) / 256); break;
+    // these two read no Ghat, but share their params with THR_GATHER up to the weight_grad flag, which the workspace
+    // query of hg_rgbuv_hist_bwd does not know: one size for all three
+    case HG_ROUTE_BWD_THR_LEAN:
+      pl.gh_bytes = ghat_bytes; pl.bwd_wgs = pl.S_fwd; break;
+    default:   // HG_ROUTE_BWD_ZERO
+      pl.gh_bytes = ghat_bytes; pl.bwd_wgs = 0; break;
+  }
+  const bool resized = p->resize_mode != HG_RESIZE_NONE;
+  pl.gxs_bytes = resized ? round256((size_t)p->B * 3 * npix * sizeof(float)) : 0;
+  pl.gws_bytes = resized ? round256((size_t)p->B * npix * sizeof(float)) : 0;
   return pl;
 }
 
@@ -2298,146 +2363,67 @@ DevParams make_dev(const hg_hist_params *p) {
   return d;
 }
 
-// The shared-reciprocal operand generation of k_hist_fwd forms products of four denominators 1 + t^2, |t| <= (13.9 +
-// max|boundary|) / sigma (log-chroma differences of clamped pixels lie in [-13.82, 13.82]): taken only when that product
-// stays below 1e30 (its reciprocal then is a normal float with room to spare).
+// The shared-reciprocal operand generation of k_hist_fwd / k_hist_bwd (RGB-uv, three planes) forms products of four
+// denominators 1 + t^2, |t| <= (13.9 + max|boundary|) / sigma (log-chroma differences of clamped pixels lie in [-13.82,
+// 13.82]): taken only when that product stays below 1e30 (its reciprocal then is a normal float with room to spare).
 // (the kernels also evaluate the PADDED bins of a 32-wide tile, up to index 32 * ceil(h / 32) - 1 >= h - 1: the bound
 // takes the farthest padded bin centre lo + (padded - 1) * step, not only the boundary)
-static double share_rcp_tmax(const DevParams &d) {
+bool share_rcp_ok(const DevParams &d) {
+  if (d.proj != HG_PROJ_RGBUV || d.green) return false;
   const int padded = (d.h + 31) / 32 * 32;
   const double far_hi = d.lo + (double)(padded - 1) * d.step;
   double bmax = fabs(d.lo) > fabs(d.hi) ? fabs(d.lo) : fabs(d.hi);
   bmax = fabs(far_hi) > bmax ? fabs(far_hi) : bmax;
-  return (13.9 + bmax) * d.inv_sigma_x;
-}
-
-bool fwd_share_rcp_ok(const DevParams &d) {
-  if (d.proj != HG_PROJ_RGBUV) return false;
-  const double tmax = share_rcp_tmax(d), den = 1.0 + tmax * tmax;
+  const double tmax = (13.9 + bmax) * d.inv_sigma_x, den = 1.0 + tmax * tmax;
   return den * den * den * den < 1e30;
 }
 
-bool bwd_share_rcp_ok(const DevParams &d) {      // the same product-of-four-denominators condition
-  const double tmax = share_rcp_tmax(d), den = 1.0 + tmax * tmax;
-  return den * den * den * den < 1e30;
+// ---- runtime values -> template arguments ---------------------------------------------------------------------------
+// dispatch(f, picks...) calls the generic lambda f with one compile-time constant per pick: a bool becomes a
+// std::bool_constant, among<V0, V1, ...>(v) the std::integral_constant<int, Vi> with Vi == v (the last one when none is).
+template <int... Vs> struct Among { int v; };
+template <int... Vs> Among<Vs...> among(int v) { return {v}; }
+
+template <class F> int dispatch(F &&f) { return f(); }
+template <class F, int V0, int... Vs, class... Rest> int dispatch(F &&f, Among<V0, Vs...> a, Rest... rest);
+
+template <class F, class... Rest> int dispatch(F &&f, bool b, Rest... rest) {
+  auto with = [&](auto c) { return dispatch([&](auto... cs) { return f(c, cs...); }, rest...); };
+  return b ? with(std::true_type{}) : with(std::false_type{});
 }
 
-// the instantiation with or without the weight map (pixel_state: WGT)
-template <int T, int METHOD, bool SYM, bool DIAG, bool GREEN, bool SHARE>
-void launch_fwd_w(const dim3 grid, const dim3 block, size_t lds, hipStream_t st, const DevParams &d, const float *x,
-                  float *slabs, double *slab_tot, int chunk) {
-  if (d.weight) hipLaunchKernelGGL((k_hist_fwd<T, METHOD, SYM, DIAG, GREEN, SHARE, true>), grid, block, lds, st, d, x, slabs, slab_tot, chunk);
-  else hipLaunchKernelGGL((k_hist_fwd<T, METHOD, SYM, DIAG, GREEN, SHARE, false>), grid, block, lds, st, d, x, slabs, slab_tot, chunk);
+template <class F, int V0, int... Vs, class... Rest> int dispatch(F &&f, Among<V0, Vs...> a, Rest... rest) {
+  auto head = [&] { return dispatch([&](auto... cs) { return f(std::integral_constant<int, V0>{}, cs...); }, rest...); };
+  if constexpr (sizeof...(Vs) == 0) return head();
+  else return a.v == V0 ? head() : dispatch(f, Among<Vs...>{a.v}, rest...);
 }
 
-template <int T, int METHOD, bool GREEN, bool SHARE>
-void launch_bwd_w(const dim3 grid, const dim3 block, size_t lds, hipStream_t st, const DevParams &d, const float *x,
-                  const float *gout, const float *hist, const float *sums, float *gdst, int rounds) {
-  if (d.gw) hipLaunchKernelGGL((k_hist_bwd<T, METHOD, GREEN, SHARE, true, true>), grid, block, lds, st, d, x, gout, hist, sums, gdst, rounds);
-  else if (d.weight) hipLaunchKernelGGL((k_hist_bwd<T, METHOD, GREEN, SHARE, true>), grid, block, lds, st, d, x, gout, hist, sums, gdst, rounds);
-  else hipLaunchKernelGGL((k_hist_bwd<T, METHOD, GREEN, SHARE, false>), grid, block, lds, st, d, x, gout, hist, sums, gdst, rounds);
-}
-
-template <int T, int METHOD, bool GREEN>
-int launch_fwd_tmg(const DevParams &d, const Plan &pl, bool sym, const float *x, float *slabs, double *slab_tot,
-                   hipStream_t st) {
-  const dim3 grid(pl.S_fwd, pl.nbd * pl.nbd, d.B), block(256);
-  const size_t lds = 4 * kFwdStage * 16 + (size_t)3 * pl.BLK * pl.BLK * sizeof(float);
-  const bool diag = pl.nbd == 1;
-  if constexpr (T == 2 && METHOD == HG_METHOD_INVERSE_QUADRATIC && !GREEN) {
-    if (sym && diag && fwd_share_rcp_ok(d)) {
-      launch_fwd_w<T, METHOD, true, true, GREEN, true>(grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
-      HG_LAUNCH_CHECK();
-      return HG_OK;
-    }
-  }
-  if (sym && diag) launch_fwd_w<T, METHOD, true, true, GREEN, false>(grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
-  else if (sym) launch_fwd_w<T, METHOD, true, false, GREEN, false>(grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
-  else launch_fwd_w<T, METHOD, false, false, GREEN, false>(grid, block, lds, st, d, x, slabs, slab_tot, pl.chunk);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
-}
-
-template <int T, int METHOD>
-int launch_fwd_tm(const DevParams &d, const Plan &pl, bool sym, const float *x, float *slabs, double *slab_tot,
-                  hipStream_t st) {
-  return d.green ? launch_fwd_tmg<T, METHOD, true>(d, pl, sym, x, slabs, slab_tot, st)
-                 : launch_fwd_tmg<T, METHOD, false>(d, pl, sym, x, slabs, slab_tot, st);
-}
-
-template <int T>
-int launch_fwd_t(const DevParams &d, const Plan &pl, bool sym, const float *x, float *slabs, double *slab_tot,
-                 hipStream_t st) {
-  switch (d.method) {
-    case HG_METHOD_THRESHOLDING: return launch_fwd_tm<T, HG_METHOD_THRESHOLDING>(d, pl, sym, x, slabs, slab_tot, st);
-    case HG_METHOD_RBF: return launch_fwd_tm<T, HG_METHOD_RBF>(d, pl, sym, x, slabs, slab_tot, st);
-    default: return launch_fwd_tm<T, HG_METHOD_INVERSE_QUADRATIC>(d, pl, sym, x, slabs, slab_tot, st);
-  }
-}
-
-template <int T, int METHOD>
-int launch_bwd_tm(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
-                  const float *sums, float *gdst, hipStream_t st) {
-  const dim3 grid(pl.S_bwd, d.B), block(256);
-  const size_t lds = (size_t)3 * pl.BLK * (pl.BLK + 1) * sizeof(float);
-  if constexpr (METHOD == HG_METHOD_INVERSE_QUADRATIC) {
-    if (!d.green && bwd_share_rcp_ok(d)) {
-      launch_bwd_w<T, METHOD, false, true>(grid, block, lds, st, d, x, gout, hist, sums, gdst, pl.rounds);
-      HG_LAUNCH_CHECK();
-      return HG_OK;
-    }
-  }
-  if (d.green) launch_bwd_w<T, METHOD, true, false>(grid, block, lds, st, d, x, gout, hist, sums, gdst, pl.rounds);
-  else launch_bwd_w<T, METHOD, false, false>(grid, block, lds, st, d, x, gout, hist, sums, gdst, pl.rounds);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
-}
-
-template <int T>
-int launch_bwd_t(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
-                 const float *sums, float *gdst, hipStream_t st) {
-  switch (d.method) {
-    case HG_METHOD_THRESHOLDING: return launch_bwd_tm<T, HG_METHOD_THRESHOLDING>(d, pl, x, gout, hist, sums, gdst, st);
-    case HG_METHOD_RBF: return launch_bwd_tm<T, HG_METHOD_RBF>(d, pl, x, gout, hist, sums, gdst, st);
-    default: return launch_bwd_tm<T, HG_METHOD_INVERSE_QUADRATIC>(d, pl, x, gout, hist, sums, gdst, st);
-  }
-}
-
-template <int RT, bool WGT, bool WG = false>
-int launch_bwd_planes_rtw(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
-                          const float *sums, float *part, float *gdst, hipStream_t st) {
-  const dim3 grid(pl.S_bwd, d.B), block(256);
-  const size_t lds = (size_t)(32 * RT) * (32 * RT + 1) * sizeof(float);
-  const void *kern = (d.method == HG_METHOD_RBF) ? (const void *)k_hist_bwd_planes<RT, HG_METHOD_RBF, WGT, WG>
-                                                 : (const void *)k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC, WGT, WG>;
+// the one launch: dynamic LDS above 48 KB is asked for on the kernel that is launched
+template <class... KArgs>
+int launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, std::decay_t<KArgs>... args) {
   if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
-  if (d.method == HG_METHOD_RBF)
-    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_RBF, WGT, WG>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
-  else
-    hipLaunchKernelGGL((k_hist_bwd_planes<RT, HG_METHOD_INVERSE_QUADRATIC, WGT, WG>), grid, block, lds, st, d, x, gout, hist, sums, part, gdst, pl.rounds);
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
   HG_LAUNCH_CHECK();
   return HG_OK;
 }
 
-template <int RT>
-int launch_bwd_planes_rt(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
-                         const float *sums, float *part, float *gdst, hipStream_t st) {
-  if (d.gw) return launch_bwd_planes_rtw<RT, true, true>(d, pl, x, gout, hist, sums, part, gdst, st);
-  return d.weight ? launch_bwd_planes_rtw<RT, true>(d, pl, x, gout, hist, sums, part, gdst, st)
-                  : launch_bwd_planes_rtw<RT, false>(d, pl, x, gout, hist, sums, part, gdst, st);
-}
+constexpr Among<HG_METHOD_THRESHOLDING, HG_METHOD_RBF, HG_METHOD_INVERSE_QUADRATIC> any_method(int m) { return {m}; }
+
+// the weight map's three cases of the MFMA backwards: 0 none, 1 a constant map (WGT), 2 its gradient too (WGT, WG) --
+// one choice, not two bools: (WG without WGT) does not exist
+inline Among<2, 1, 0> weight_case(const DevParams &d) { return {d.gw ? 2 : d.weight ? 1 : 0}; }
 
 int launch_bwd_planes(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
                       const float *sums, float *part, float *gdst, hipStream_t st) {
-  switch (pl.planes_rt) {
-    case 1: return launch_bwd_planes_rt<1>(d, pl, x, gout, hist, sums, part, gdst, st);
-    case 2: return launch_bwd_planes_rt<2>(d, pl, x, gout, hist, sums, part, gdst, st);
-    case 3: return launch_bwd_planes_rt<3>(d, pl, x, gout, hist, sums, part, gdst, st);
-    default: return launch_bwd_planes_rt<4>(d, pl, x, gout, hist, sums, part, gdst, st);
-  }
+  const int rt = pl.rt.planes_rt;
+  const size_t lds = (size_t)(32 * rt) * (32 * rt + 1) * sizeof(float);
+  return dispatch([&](auto RT, auto W, auto METHOD) {
+    return launch(k_hist_bwd_planes<RT, METHOD, W >= 1, W == 2>, dim3(pl.bwd_wgs, d.B), dim3(256), lds, st, d, x, gout, hist,
+                  sums, part, gdst, pl.rounds);
+  }, among<1, 2, 3, 4>(rt), weight_case(d), among<HG_METHOD_RBF, HG_METHOD_INVERSE_QUADRATIC>(d.method));
 }
 
 }  // namespace
@@ -2456,10 +2442,25 @@ int hg_debug_hist_probe(unsigned long long *out16) {
 
 int hg_version(void) { return HG_VERSION_NUM; }
 
+int hg_rgbuv_hist_route(const hg_hist_params *p, int weight_grad, hg_hist_route *out) {
+  const int rc = weight_grad ? validate_wgrad(p) : validate(p);
+  if (rc) return rc;
+  if (!out || out->struct_size != (int32_t)sizeof(hg_hist_route)) return HG_EINVAL;
+  const Plan pl = make_plan(p, weight_grad != 0);
+  out->fwd = pl.rt.fwd;
+  out->bwd = pl.rt.bwd;
+  out->fwd_slices = pl.S_fwd;
+  out->bwd_workgroups = pl.bwd_wgs;
+  out->planes_rt = pl.rt.planes_rt;
+  out->rbf_radius = pl.rt.rbf_R;
+  out->uses_proj_cache = pl.rt.fwd == HG_ROUTE_FWD_DENSE;
+  return HG_OK;
+}
+
 int hg_rgbuv_hist_uses_proj_cache(const hg_hist_params *p) {
   const int rc = validate(p);
   if (rc) return rc;
-  return sparse_path(p) ? 0 : 1;
+  return make_route(p, /* nbd: read for the backward only */ 1, false).fwd == HG_ROUTE_FWD_DENSE;
 }
 
 const char *hg_error_string(int code) {
@@ -2481,82 +2482,76 @@ int hg_selftest_fastlog(float *out2, void *stream) {
   if (e != hipSuccess) return (int)e;
   union { float f; uint32_t u; } a, b;
   a.f = 1e-6f; b.f = 1.000002f;
-  hipLaunchKernelGGL(k_selftest_fastlog, dim3(2048), dim3(256), 0, st, a.u, b.u - a.u + 1u, (unsigned int *)out2);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_selftest_fastlog, dim3(2048), dim3(256), 0, st, a.u, b.u - a.u + 1u, (unsigned int *)out2);
 }
 
 int hg_rgbuv_hist_workspace_bytes(const hg_hist_params *p, size_t *fwd_bytes, size_t *bwd_bytes) {
   const int rc = validate(p);
   if (rc) return rc;
-  const Plan pl = make_plan(p);
-  if (fwd_bytes) *fwd_bytes = pl.part_bytes + pl.slab_bytes;
+  const Plan pl = make_plan(p, false);
+  if (fwd_bytes) *fwd_bytes = pl.tot_bytes + pl.slab_bytes;
   if (bwd_bytes) *bwd_bytes = pl.gxs_bytes + pl.gh_bytes;
   return HG_OK;
 }
 
 int hg_rgbuv_hist_fwd(const hg_hist_params *p, const float *x, float *hist_out, float *sum_out, void *workspace,
                       size_t workspace_bytes, void *stream) {
-  const int rc = validate(p);
+  int rc = validate(p);
   if (rc) return rc;
   if (!x || !hist_out || !sum_out || !workspace) return HG_EINVAL;
-  const Plan pl = make_plan(p);
-  if (workspace_bytes < pl.part_bytes + pl.slab_bytes) return HG_EWORKSPACE;
+  const Plan pl = make_plan(p, false);
+  const Route &rt = pl.rt;
+  if (workspace_bytes < pl.tot_bytes + pl.slab_bytes) return HG_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const DevParams d = make_dev(p);
-  float *slabs = (float *)((char *)workspace + pl.part_bytes);
-  const bool sym = (p->lo == -p->hi);
-  if (sparse_path(p)) {
-    const size_t one = (size_t)d.h * d.h * sizeof(unsigned long long);
-    const bool all3 = one * d.P <= 150 * 1024;
-    const size_t lds = ((all3 ? one * d.P : one) + 15) / 16 * 16;
-    const int R = rbf_radius(p);
-    const void *kern = R ? (all3 ? (const void *)k_hist_rbf_fwd<true> : (const void *)k_hist_rbf_fwd<false>)
-                         : (all3 ? (const void *)k_hist_thr_fwd<true> : (const void *)k_hist_thr_fwd<false>);
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-    }
-    const dim3 grid(pl.S_fwd, d.B), block(all3 ? 1024 : 256);
-    double *slab_tot = (double *)workspace;
-    if (R) {
-      if (all3) hipLaunchKernelGGL(k_hist_rbf_fwd<true>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk, R);
-      else hipLaunchKernelGGL(k_hist_rbf_fwd<false>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk, R);
-    } else if (thr_lean(p)) {
-      const bool ex = thr_exact_only(), dir = thr_direct(p, x, x);
-      const void *lk = dir ? (sym ? (const void *)k_thr_fwd_lean<true, true> : (const void *)k_thr_fwd_lean<true, false>)
-                           : (sym ? (const void *)k_thr_fwd_lean<false, true> : (const void *)k_thr_fwd_lean<false, false>);
-      if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(lk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-      }
+  double *slab_tot = (double *)workspace;
+  float *slabs = (float *)((char *)workspace + pl.tot_bytes);
+  // the scatter kernels: one workgroup per split, h x h 64-bit grids in LDS (one plane's, or every plane's at once)
+  const size_t one = (size_t)d.h * d.h * sizeof(unsigned long long);
+  const size_t lds = ((rt.all3 ? one * d.P : one) + 15) / 16 * 16;
+  const dim3 grid(pl.S_fwd, d.B), block(rt.all3 ? 1024 : 256);
+  int tot_per_split = 1;          // slab_tot entries every split of an image leaves
+  switch (rt.fwd) {
+    case HG_ROUTE_FWD_RBF_SCATTER:
+      rc = dispatch([&](auto ALL3) {
+        return launch(k_hist_rbf_fwd<ALL3>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk, rt.rbf_R);
+      }, rt.all3);
+      break;
+    case HG_ROUTE_FWD_THR_SCATTER:
+      rc = dispatch([&](auto ALL3) {
+        return launch(k_hist_thr_fwd<ALL3>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk);
+      }, rt.all3);
+      break;
+    case HG_ROUTE_FWD_THR_LEAN:
       // (S > 1: k_hist_finish sums the slabs.  Round 3 tried ONE launch -- the last-arriving workgroup of an image, found
       // through arrival flags, summing them -- and measured 152 us instead of 22: the device-scope release / acquire fences
       // that make another XCD's slabs visible write back and invalidate whole L2s, once per wave of every workgroup.)
-      if (dir && sym) hipLaunchKernelGGL((k_thr_fwd_lean<true, true>), grid, block, lds, st, d, x, slabs, slab_tot, hist_out, sum_out, 4 * pl.chunk, ex);
-      else if (dir) hipLaunchKernelGGL((k_thr_fwd_lean<true, false>), grid, block, lds, st, d, x, slabs, slab_tot, hist_out, sum_out, 4 * pl.chunk, ex);
-      else if (sym) hipLaunchKernelGGL((k_thr_fwd_lean<false, true>), grid, block, lds, st, d, x, slabs, slab_tot, hist_out, sum_out, 4 * pl.chunk, ex);
-      else hipLaunchKernelGGL((k_thr_fwd_lean<false, false>), grid, block, lds, st, d, x, slabs, slab_tot, hist_out, sum_out, 4 * pl.chunk, ex);
-    } else {
-      if (all3) hipLaunchKernelGGL(k_hist_thr_fwd<true>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk);
-      else hipLaunchKernelGGL(k_hist_thr_fwd<false>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk);
+      rc = dispatch([&](auto DIRECT, auto SYM) {
+        return launch(k_thr_fwd_lean<DIRECT, SYM>, grid, block, lds, st, d, x, slabs, slab_tot, hist_out, sum_out,
+                      4 * pl.chunk, rt.exact_only);
+      }, thr_direct(p, x, x), rt.sym);
+      if (pl.S_fwd == 1) return rc;          // normalised in the scatter kernel
+      break;
+    default: {   // HG_ROUTE_FWD_DENSE: the MFMA kernel leaves every workgroup's share of the image total
+      // the boundary's four cases -- 0: asymmetric, 1: symmetric (SYM), 2: symmetric and one bin block (SYM, DIAG), 3: that
+      // with shared reciprocals (SHARE), which exists for T = 2, inverse-quadratic, three planes only
+      const bool diag = rt.sym && pl.nbd == 1;
+      const bool share = diag && pl.T == 2 && d.method == HG_METHOD_INVERSE_QUADRATIC && share_rcp_ok(d);
+      // (`share` repeats, at run time, the condition under which the lambda below instantiates BND == 3: keep the two together)
+      const int boundary = !rt.sym ? 0 : !diag ? 1 : !share ? 2 : 3;
+      tot_per_split = pl.nbd * pl.nbd;
+      rc = dispatch([&](auto T, auto METHOD, auto GREEN, auto BND, auto WGT) {
+        if constexpr (BND == 3 && !(T == 2 && METHOD == HG_METHOD_INVERSE_QUADRATIC && !GREEN)) return (int)HG_EINVAL;   // never picked
+        else return launch(k_hist_fwd<T, METHOD, BND >= 1, BND >= 2, GREEN, BND == 3, WGT>, dim3(pl.S_fwd, tot_per_split, d.B),
+                           dim3(256), 4 * kFwdStage * 16 + (size_t)3 * pl.BLK * pl.BLK * sizeof(float), st, d, x, slabs,
+                           slab_tot, pl.chunk);
+      }, among<1, 2>(pl.T), any_method(d.method), d.green != 0, among<3, 2, 1, 0>(boundary), d.weight != nullptr);
     }
-    HG_LAUNCH_CHECK();
-    if (!R && thr_lean(p) && pl.S_fwd == 1) return HG_OK;          // normalised in the scatter kernel
-    hipLaunchKernelGGL(k_hist_finish, dim3(pl.nparts, d.B), dim3(256), 0, st, slabs, slab_tot, hist_out, sum_out,
-                       pl.S_fwd, pl.S_fwd, d.P * d.h * d.h);
-    HG_LAUNCH_CHECK();
-    return HG_OK;
-  } else {
-    double *slab_tot = (double *)workspace;
-    int r = (pl.T == 1) ? launch_fwd_t<1>(d, pl, sym, x, slabs, slab_tot, st) : launch_fwd_t<2>(d, pl, sym, x, slabs, slab_tot, st);
-    if (r) return r;
   }
-  // slab sum + normalisation in one launch (the MFMA kernel left every workgroup's share of the image total)
-  hipLaunchKernelGGL(k_hist_finish, dim3(pl.nparts, d.B), dim3(256), 0, st, slabs, (const double *)workspace, hist_out,
-                     sum_out, pl.S_fwd, pl.S_fwd * pl.nbd * pl.nbd, d.P * d.h * d.h);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  if (rc) return rc;
+  // slab sum + normalisation in one launch
+  return launch(k_hist_finish, dim3(pl.nparts, d.B), dim3(256), 0, st, slabs, slab_tot, hist_out, sum_out, pl.S_fwd,
+                pl.S_fwd * tot_per_split, d.P * d.h * d.h);
 }
 
 // The backward behind both entry points.  grad_weight == NULL: hg_rgbuv_hist_bwd, the instantiations and launches it always
@@ -2567,13 +2562,13 @@ static int hist_bwd_impl(const hg_hist_params *p, const float *x, const float *g
                          void *stream) {
   if (!x || !grad_out || !hist_out || !sum_out || !grad_x || !workspace) return HG_EINVAL;
   const bool wg = grad_weight != nullptr;
-  const Plan pl = make_plan(p);
+  const Plan pl = make_plan(p, wg);
+  const Route &rt = pl.rt;
   if (workspace_bytes < pl.gxs_bytes + pl.gh_bytes + (wg ? pl.gws_bytes : 0)) return HG_EWORKSPACE;
-  const bool sym = (p->lo == -p->hi);
-  const bool generic = !sym || pl.nbd != 1 || p->projection != HG_PROJ_RGBUV;
   hipStream_t st = (hipStream_t)stream;
   DevParams d = make_dev(p);
   float *gxs = (float *)workspace;
+  float *gh = (float *)((char *)workspace + pl.gxs_bytes);     // Ghat, or the planes kernel's per-pixel carry
   const size_t gx_bytes = (size_t)d.B * d.C * d.H * d.W * sizeof(float);
   float *gdst = grad_x;
   if (d.mode != HG_RESIZE_NONE) {
@@ -2588,90 +2583,65 @@ static int hist_bwd_impl(const hg_hist_params *p, const float *x, const float *g
     }
   }
   if (wg) d.gw = (d.mode == HG_RESIZE_NONE) ? grad_weight : (float *)((char *)workspace + pl.gxs_bytes + pl.gh_bytes);
-  if (thr_lean(p) && !p->intensity_scale && d.mode == HG_RESIZE_NONE && !wg) {
-    // a 0/1 window has no slope and there is no weight to differentiate: the gradient is identically zero
-    hipError_t e = hipMemsetAsync(grad_x, 0, gx_bytes, st);
-    if (e != hipSuccess) return (int)e;
-  } else if (thr_lean(p) && (p->intensity_scale || wg)) {
-    // (16-byte stores of the map's gradient need grad_weight aligned like grad_x)
-    const bool ex = thr_exact_only(), dir = thr_direct(p, x, grad_x) && !(wg && ((uintptr_t)grad_weight & 15));
-    const dim3 grid(pl.S_fwd, d.B), block(1024);
-    const size_t blds = (size_t)3 * d.h * d.h * sizeof(float);
-    const void *lk = wg ? (dir ? (sym ? (const void *)k_thr_bwd_lean<true, true, true> : (const void *)k_thr_bwd_lean<true, false, true>)
-                               : (sym ? (const void *)k_thr_bwd_lean<false, true, true> : (const void *)k_thr_bwd_lean<false, false, true>))
-                        : (dir ? (sym ? (const void *)k_thr_bwd_lean<true, true> : (const void *)k_thr_bwd_lean<true, false>)
-                               : (sym ? (const void *)k_thr_bwd_lean<false, true> : (const void *)k_thr_bwd_lean<false, false>));
-    if (blds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(lk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-      if (e != hipSuccess) return (int)e;
+  const dim3 grid(pl.bwd_wgs, d.B);
+  auto ghat = [&] { return launch(k_hist_ghat, dim3(d.B), dim3(1024), 0, st, grad_out, hist_out, sum_out, gh, d.P * d.h * d.h); };
+  int rc = HG_OK;
+  switch (rt.bwd) {
+    case HG_ROUTE_BWD_ZERO:
+      // a 0/1 window has no slope and there is no weight to differentiate: the gradient is identically zero
+      rc = (int)hipMemsetAsync(grad_x, 0, gx_bytes, st);
+      break;
+    case HG_ROUTE_BWD_THR_LEAN: {
+      // (16-byte stores of the map's gradient need grad_weight aligned like grad_x)
+      const bool direct = thr_direct(p, x, grad_x) && !(wg && ((uintptr_t)grad_weight & 15));
+      rc = dispatch([&](auto WG, auto DIRECT, auto SYM) {
+        return launch(k_thr_bwd_lean<DIRECT, SYM, WG>, grid, dim3(1024), (size_t)3 * d.h * d.h * sizeof(float), st, d, x,
+                      grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, rt.exact_only);
+      }, wg, direct, rt.sym);
+      break;
     }
-    if (wg) {
-      if (dir && sym) hipLaunchKernelGGL((k_thr_bwd_lean<true, true, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
-      else if (dir) hipLaunchKernelGGL((k_thr_bwd_lean<true, false, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
-      else if (sym) hipLaunchKernelGGL((k_thr_bwd_lean<false, true, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
-      else hipLaunchKernelGGL((k_thr_bwd_lean<false, false, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
-    } else if (dir && sym) hipLaunchKernelGGL((k_thr_bwd_lean<true, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
-    else if (dir) hipLaunchKernelGGL((k_thr_bwd_lean<true, false>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
-    else if (sym) hipLaunchKernelGGL((k_thr_bwd_lean<false, true>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
-    else hipLaunchKernelGGL((k_thr_bwd_lean<false, false>), grid, block, blds, st, d, x, grad_out, hist_out, sum_out, gdst, 4 * pl.chunk, ex);
-    HG_LAUNCH_CHECK();
-  } else if (sparse_path(p)) {
-    float *gh = (float *)((char *)workspace + pl.gxs_bytes);
-    hipLaunchKernelGGL(k_hist_ghat, dim3(d.B), dim3(1024), 0, st, grad_out, hist_out, sum_out, gh, d.P * d.h * d.h);
-    HG_LAUNCH_CHECK();
-    const int R = rbf_radius(p);
-    const dim3 grid((d.npix + 255) / 256, d.B), block(256);
-    if (R && wg) hipLaunchKernelGGL(k_hist_rbf_bwd<true>, grid, block, 0, st, d, x, gh, gdst, R);
-    else if (R) hipLaunchKernelGGL(k_hist_rbf_bwd<false>, grid, block, 0, st, d, x, gh, gdst, R);
-    else if (wg) hipLaunchKernelGGL(k_hist_thr_bwd<true>, grid, block, 0, st, d, x, gh, gdst);
-    else hipLaunchKernelGGL(k_hist_thr_bwd<false>, grid, block, 0, st, d, x, gh, gdst);
-    HG_LAUNCH_CHECK();
-  } else if (pl.planes_rt) {
-    float *part = (float *)((char *)workspace + pl.gxs_bytes);
-    int r = launch_bwd_planes(d, pl, x, grad_out, hist_out, sum_out, part, gdst, st);
-    if (r) return r;
-  } else if (!generic) {
-    int r = (pl.T == 1) ? launch_bwd_t<1>(d, pl, x, grad_out, hist_out, sum_out, gdst, st)
-                        : launch_bwd_t<2>(d, pl, x, grad_out, hist_out, sum_out, gdst, st);
-    if (r) return r;
-  } else {
-    float *gh = (float *)((char *)workspace + pl.gxs_bytes);
-    const int n_per_img = d.P * d.h * d.h;
-    hipLaunchKernelGGL(k_hist_ghat, dim3(d.B), dim3(1024), 0, st, grad_out, hist_out, sum_out, gh, n_per_img);
-    HG_LAUNCH_CHECK();
-    const size_t lds = (size_t)d.h * 64 * sizeof(float);
-    if (lds > 160 * 1024) return HG_EUNSUPPORTED;  // h > 640
-    const dim3 grid((d.npix + 63) / 64, d.B), block(64);
-    switch (d.method) {
-      case HG_METHOD_THRESHOLDING:
-        if (wg) hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_THRESHOLDING, true>), grid, block, lds, st, d, x, gh, gdst);
-        else hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_THRESHOLDING>), grid, block, lds, st, d, x, gh, gdst);
-        break;
-      case HG_METHOD_RBF:
-        if (wg) hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_RBF, true>), grid, block, lds, st, d, x, gh, gdst);
-        else hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_RBF>), grid, block, lds, st, d, x, gh, gdst);
-        break;
-      default:
-        if (wg) hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_INVERSE_QUADRATIC, true>), grid, block, lds, st, d, x, gh, gdst);
-        else hipLaunchKernelGGL((k_hist_bwd_generic<HG_METHOD_INVERSE_QUADRATIC>), grid, block, lds, st, d, x, gh, gdst);
-        break;
+    case HG_ROUTE_BWD_RBF_GATHER:
+      if ((rc = ghat())) break;
+      rc = dispatch([&](auto WG) { return launch(k_hist_rbf_bwd<WG>, grid, dim3(256), 0, st, d, x, gh, gdst, rt.rbf_R); }, wg);
+      break;
+    case HG_ROUTE_BWD_THR_GATHER:
+      if ((rc = ghat())) break;
+      rc = dispatch([&](auto WG) { return launch(k_hist_thr_bwd<WG>, grid, dim3(256), 0, st, d, x, gh, gdst); }, wg);
+      break;
+    case HG_ROUTE_BWD_PLANES:
+      rc = launch_bwd_planes(d, pl, x, grad_out, hist_out, sum_out, gh, gdst, st);
+      break;
+    case HG_ROUTE_BWD_MIRRORED: {
+      // the planes' three cases -- 2: three planes with shared reciprocals (SHARE; inverse-quadratic only), 1: one plane
+      // (GREEN), 0: three planes
+      // (2 is chosen for inverse-quadratic only, the condition under which the lambda below instantiates it: keep the two together)
+      const int planes = d.green ? 1 : (d.method == HG_METHOD_INVERSE_QUADRATIC && share_rcp_ok(d)) ? 2 : 0;
+      rc = dispatch([&](auto T, auto METHOD, auto PLANES, auto W) {
+        if constexpr (PLANES == 2 && METHOD != HG_METHOD_INVERSE_QUADRATIC) return (int)HG_EINVAL;   // never picked
+        else return launch(k_hist_bwd<T, METHOD, PLANES == 1, PLANES == 2, W >= 1, W == 2>, grid, dim3(256),
+                           (size_t)3 * pl.BLK * (pl.BLK + 1) * sizeof(float), st, d, x, grad_out, hist_out, sum_out, gdst,
+                           pl.rounds);
+      }, among<1, 2>(pl.T), any_method(d.method), among<2, 1, 0>(planes), weight_case(d));
+      break;
     }
-    HG_LAUNCH_CHECK();
+    default: {   // HG_ROUTE_BWD_GENERIC
+      const size_t lds = (size_t)d.h * 64 * sizeof(float);
+      if (lds > 160 * 1024) return HG_EUNSUPPORTED;  // h > 640
+      if ((rc = ghat())) break;
+      rc = dispatch([&](auto METHOD, auto WG) {
+        return launch(k_hist_bwd_generic<METHOD, WG>, grid, dim3(64), lds, st, d, x, gh, gdst);
+      }, any_method(d.method), wg);
+    }
   }
-  if (d.mode == HG_RESIZE_BILINEAR) {
-    const long long total = (long long)d.B * d.H * d.W;
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (wg) hipLaunchKernelGGL(k_bilinear_adjoint<true>, grid, block, 0, st, d, x, gxs, grad_x, grad_weight);
-    else hipLaunchKernelGGL(k_bilinear_adjoint<false>, grid, block, 0, st, d, x, gxs, grad_x, grad_weight);
-    HG_LAUNCH_CHECK();
-  } else if (d.mode == HG_RESIZE_SAMPLING) {
-    const long long total = (long long)d.B * d.npix;
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (wg) hipLaunchKernelGGL(k_sampling_adjoint<true>, grid, block, 0, st, d, x, gxs, grad_x, grad_weight);
-    else hipLaunchKernelGGL(k_sampling_adjoint<false>, grid, block, 0, st, d, x, gxs, grad_x, grad_weight);
-    HG_LAUNCH_CHECK();
-  }
-  return HG_OK;
+  if (rc) return rc;
+  // the resize adjoints: gxs (and the map's plane behind it) -> grad_x (and grad_weight)
+  if (d.mode == HG_RESIZE_NONE) return HG_OK;
+  const long long total = (d.mode == HG_RESIZE_BILINEAR) ? (long long)d.B * d.H * d.W : (long long)d.B * d.npix;
+  const dim3 agrid((unsigned)((total + 255) / 256));
+  return dispatch([&](auto BILINEAR, auto WG) {
+    if constexpr (BILINEAR) return launch(k_bilinear_adjoint<WG>, agrid, dim3(256), 0, st, d, x, gxs, grad_x, grad_weight);
+    else return launch(k_sampling_adjoint<WG>, agrid, dim3(256), 0, st, d, x, gxs, grad_x, grad_weight);
+  }, d.mode == HG_RESIZE_BILINEAR, wg);
 }
 
 int hg_rgbuv_hist_bwd(const hg_hist_params *p, const float *x, const float *grad_out, const float *hist_out,
@@ -2681,19 +2651,10 @@ int hg_rgbuv_hist_bwd(const hg_hist_params *p, const float *x, const float *grad
   return hist_bwd_impl(p, x, grad_out, hist_out, sum_out, grad_x, nullptr, workspace, workspace_bytes, stream);
 }
 
-// a differentiable map must own every element: a zero stride (broadcast) would make the elements' gradients collide
-static int validate_wgrad(const hg_hist_params *p) {
-  const int rc = validate(p);
-  if (rc) return rc;
-  if (!p->weight) return HG_EINVAL;
-  if (p->weight_stride_b == 0 || p->weight_stride_h == 0 || p->weight_stride_w == 0) return HG_EUNSUPPORTED;
-  return HG_OK;
-}
-
 int hg_rgbuv_hist_bwd_w_workspace_bytes(const hg_hist_params *p, size_t *bytes) {
   const int rc = validate_wgrad(p);
   if (rc) return rc;
-  const Plan pl = make_plan(p);
+  const Plan pl = make_plan(p, true);
   if (bytes) *bytes = pl.gxs_bytes + pl.gh_bytes + pl.gws_bytes;
   return HG_OK;
 }

@@ -106,6 +106,42 @@ int hg_selftest_fastlog(float *out2, void *stream);
  * Negative HG_E* on bad params. */
 int hg_rgbuv_hist_uses_proj_cache(const hg_hist_params *p);
 
+/* Which kernel families a call with these params runs on (since version 106).  The library decides this once per call;
+ * the same decision sizes the workspaces and picks the launches, and this query returns it.  DESIGN.md section 4 has the
+ * table of conditions. */
+enum {
+  HG_ROUTE_FWD_DENSE = 0,       /* k_hist_fwd (MFMA, split-K over pixels) -> k_hist_finish                          */
+  HG_ROUTE_FWD_THR_SCATTER = 1, /* k_hist_thr_fwd -> k_hist_finish                                                  */
+  HG_ROUTE_FWD_THR_LEAN = 2,    /* k_thr_fwd_lean [-> k_hist_finish when fwd_slices > 1]                            */
+  HG_ROUTE_FWD_RBF_SCATTER = 3  /* k_hist_rbf_fwd (truncated at rbf_radius bins) -> k_hist_finish                   */
+};
+enum {
+  HG_ROUTE_BWD_MIRRORED = 0,    /* k_hist_bwd (MFMA, mirrored-bin merge)                                            */
+  HG_ROUTE_BWD_PLANES = 1,      /* k_hist_bwd_planes<planes_rt> (MFMA, one plane at a time)                         */
+  HG_ROUTE_BWD_GENERIC = 2,     /* k_hist_ghat -> k_hist_bwd_generic                                                */
+  HG_ROUTE_BWD_THR_GATHER = 3,  /* k_hist_ghat -> k_hist_thr_bwd                                                    */
+  HG_ROUTE_BWD_RBF_GATHER = 4,  /* k_hist_ghat -> k_hist_rbf_bwd                                                    */
+  HG_ROUTE_BWD_THR_LEAN = 5,    /* k_thr_bwd_lean                                                                   */
+  HG_ROUTE_BWD_ZERO = 6         /* no kernel: grad_x is cleared (the gradient is identically zero)                  */
+};                              /* every backward is followed by the resize adjoint when resize_mode != NONE        */
+
+typedef struct hg_hist_route {
+  int32_t struct_size;          /* in: sizeof(hg_hist_route) as the caller compiled it (ABI guard, like the params) */
+  int32_t fwd, bwd;             /* HG_ROUTE_FWD_*, HG_ROUTE_BWD_*                                                    */
+  int32_t fwd_slices;           /* split-K slices per image of the forward                                          */
+  int32_t bwd_workgroups;       /* workgroups per image of the backward kernel `bwd` names (0 for ZERO)             */
+  int32_t planes_rt;            /* PLANES: 32-bin row tiles, ceil(h / 32); else 0                                    */
+  int32_t rbf_radius;           /* RBF_SCATTER / RBF_GATHER: support radius in bins; else 0                          */
+  int32_t uses_proj_cache;      /* == (fwd == HG_ROUTE_FWD_DENSE), what hg_rgbuv_hist_uses_proj_cache returns        */
+} hg_hist_route;
+
+/* Fills *out (all fields but struct_size) for a forward / backward pair with these params.  weight_grad != 0: the
+ * backward is hg_rgbuv_hist_bwd_w, and the params are validated like that call's (p->weight == NULL: HG_EINVAL; a
+ * broadcast map: HG_EUNSUPPORTED); only `bwd` and `bwd_workgroups` can depend on it.  Launches nothing, touches no
+ * device and needs none.  out == NULL or a stale out->struct_size: HG_EINVAL.  The environment switches HG_RBF_DENSE,
+ * HG_THR_EXACT and HG_BWD_PLANES are read on every call, here as in the launching entry points. */
+int hg_rgbuv_hist_route(const hg_hist_params *p, int weight_grad, hg_hist_route *out);
+
 /* Bytes of scratch each call needs for these params (both may be queried at once). */
 int hg_rgbuv_hist_workspace_bytes(const hg_hist_params *p, size_t *fwd_bytes, size_t *bwd_bytes);
 

@@ -48,33 +48,22 @@ def _parity_record():
 
 
 def family(x, proj, kw):
-    """The kernel family hg_hist.hip dispatches (x, block) to, from the library's own answers: the projection-cache query
-    separates the dense MFMA kernels from the scatter paths; within them the rules are the dispatcher's documented ones
-    (thr_lean / rbf_radius / bwd_planes_rt).  Returns (label, forward split-K slices)."""
+    """The kernel family hg_hist.hip dispatches (x, block) to, as the library itself answers (hg_rgbuv_hist_route: the
+    decision its launches and workspace sizes are made from).  Returns (label, forward split-K slices)."""
     from histogan_amd import hist as HH
-    from histogan_amd._lib import lib
+    from histogan_amd._lib import HG_ROUTE_BWD, HG_ROUTE_FWD, hist_route, lib
     cfg = HH.HistConfig(projection=proj, **{k: (list(v) if k == 'hist_boundary' else v) for k, v in kw.items()})
     p, keep = HH._make_params(x, cfg)
-    dense = lib.hg_rgbuv_hist_uses_proj_cache(ctypes.byref(p))
-    assert dense in (0, 1)
-    fwd_b, _ = HH._ws_bytes(p)
-    planes = 1 if (cfg.green_only or proj != 'rgbuv') else 3
-    nbd = -(-cfg.h // (32 if cfg.h <= 32 else 64))
-    # forward workspace = B * S * (one fp32 slab + nbd^2 fp64 totals), each part rounded up to 256 bytes: S split-K slices
-    slices = fwd_b // (p.B * (planes * cfg.h * cfg.h * 4 + nbd * nbd * 8))
-    sym = cfg.lo == -cfg.hi
-    single = cfg.h > 1 and (cfg.hi - cfg.lo) / (cfg.h - 1) > (abs(cfg.lo) + abs(cfg.hi)) / cfg.h * (1.0 + 1e-9)
-    if dense:
-        if cfg.h > 128:
-            return 'dense fwd + k_hist_bwd_generic', slices
-        if proj == 'rgbuv' and sym and cfg.h <= 64:
-            return 'dense fwd + k_hist_bwd' + (' (green)' if cfg.green_only else ''), slices
-        return 'dense fwd + k_hist_bwd_planes', slices
-    if cfg.method == 'RBF':
-        return 'truncated RBF scatter / gather', slices
-    if proj == 'rgbuv' and not cfg.green_only and single and cfg.h <= 79:
-        return 'lean scatter', slices
-    return 'thresholding scatter / gather', slices
+    r = hist_route(p)
+    assert r.uses_proj_cache == lib.hg_rgbuv_hist_uses_proj_cache(ctypes.byref(p))
+    fwd, bwd = HG_ROUTE_FWD[r.fwd], HG_ROUTE_BWD[r.bwd]
+    if fwd == 'DENSE':
+        label = {'MIRRORED': 'dense fwd + k_hist_bwd' + (' (green)' if cfg.green_only else ''),
+                 'PLANES': 'dense fwd + k_hist_bwd_planes', 'GENERIC': 'dense fwd + k_hist_bwd_generic'}[bwd]
+    else:
+        label = {'RBF_SCATTER': 'truncated RBF scatter / gather', 'THR_LEAN': 'lean scatter',
+                 'THR_SCATTER': 'thresholding scatter / gather'}[fwd]
+    return label, r.fwd_slices
 
 
 GPU_PIN_EXTRA = [
