@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_PKG, 'libhistogan_hip' + ('_' + _TAG if _TAG else '') +
 
 HG_METHOD = {'thresholding': 0, 'RBF': 1, 'inverse-quadratic': 2}
 HG_RESIZE_NONE, HG_RESIZE_BILINEAR, HG_RESIZE_SAMPLING = 0, 1, 2
-HG_PROJ = {'rgbuv': 0, 'rgchroma': 1, 'direct': 2}
+HG_PROJ = {'rgbuv': 0, 'rgchroma': 1, 'direct': 2, 'lab': 3}
 # hg_hist_route.fwd / .bwd (the HG_ROUTE_FWD_* / HG_ROUTE_BWD_* enums of include/hg_hist.h), by value
 HG_ROUTE_FWD = ('DENSE', 'THR_SCATTER', 'THR_LEAN', 'RBF_SCATTER')
 HG_ROUTE_BWD = ('MIRRORED', 'PLANES', 'GENERIC', 'THR_GATHER', 'RBF_GATHER', 'THR_LEAN', 'ZERO')
@@ -230,6 +230,10 @@ def _load():
     lib.hg_bgu_normal.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
     lib.hg_bgu_slice.restype = ctypes.c_int
     lib.hg_bgu_slice.argtypes = [vp, i32, i32, i32, vp, i64, i64, i64, vp, i32, i32, i32, vp]
+    lib.hg_srgb_to_lab.restype = ctypes.c_int
+    lib.hg_srgb_to_lab.argtypes = [vp, i64, i64, i64, i64, vp, i32, i32, i32, vp]
+    lib.hg_lab_to_srgb.restype = ctypes.c_int
+    lib.hg_lab_to_srgb.argtypes = [vp, i64, i64, i64, i64, vp, i32, i32, i32, vp]
     return lib
 
 
@@ -253,7 +257,7 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
            'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd',
            'hg_resize_axis', 'hg_pyr_down', 'hg_pyr_up_add', 'hg_color_moments_workspace_bytes', 'hg_color_moments',
            'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc', 'hg_bgu_normal_workspace_bytes', 'hg_bgu_normal',
-           'hg_bgu_slice')
+           'hg_bgu_slice', 'hg_srgb_to_lab', 'hg_lab_to_srgb')
 
 
 class HgError(RuntimeError):

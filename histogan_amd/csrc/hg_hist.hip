@@ -28,11 +28,12 @@
 // v_mfma_f32_32x32x2_f32 is an exact fp32 fma chain (no reduced-precision path on gfx950).
 #include "hg_common.h"
 #include "../../include/hg_hist.h"
+#include "hg_lab.h"
 #include <cstdlib>
 
-#define HG_VERSION_NUM 106   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
+#define HG_VERSION_NUM 107   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
                              // 104: hg_bgu_normal, hg_bgu_slice (hg_post.h); 105: hg_rgbuv_hist_bwd_w (gradient of the weight map);
-                             // 106: hg_rgbuv_hist_route
+                             // 106: hg_rgbuv_hist_route; 107: HG_PROJ_LAB, hg_srgb_to_lab, hg_lab_to_srgb (hg_post.h)
 
 // Settled schedule constants of the dense kernels (DESIGN.md sections 4 and 11 hold the measurements).
 constexpr int kFwdMfmaGroup = 12;    // k_hist_fwd at configs[1]: groups of 1: 505 us, 3: 498, 6: 473, 12: 465
@@ -68,7 +69,7 @@ struct DevParams {
   int Hs, Ws, mode;
   const int *rows, *cols;
   int h, P, method, intensity, green;
-  int proj;                 // HG_PROJ_*: 0 RGB-uv (3 planes), 1 rg-chroma, 2 direct (Lab): one plane, run as `green`
+  int proj;                 // HG_PROJ_*: 0 RGB-uv (3 planes), 1 rg-chroma, 2 direct (Lab), 3 Lab from sRGB: one plane, run as `green`
   int pre_relu;             // the caller's F.relu in front of the block (histoGAN.py:955) folded into the clamp mask
   float4 *cache;            // optional [B][npix][2] float4: (a, b, c, Iy), (r, g, b, w) written by the forward, read by the backward
   const float *weight;      // optional per-pixel weight map (hg_hist_params.weight), element strides wsb / wsh / wsw
@@ -179,8 +180,20 @@ __device__ __forceinline__ float sample_weight(const DevParams &P, int b, int n)
 }
 
 // Stage 1 (projection), RGBuvHistBlock.py:104-115: three logs and three chroma differences.
+// LAB (compile time; HG_PROJ_LAB): sRGB -> normalised CIE Lab in fp64, rounded once (hg_lab.h), then exactly a DIRECT pixel
+// of (Ln, an, bn).  Three fp64 pow and three fp64 cbrt per pixel: a template argument and not one more run-time branch,
+// because this function is inlined into kernels that sit at their register budget -- the LAB = false instantiations are
+// the kernels as they were (profiles/lab_proj_isa.json), and LAB exists for the one-plane kernel families only.
+template <bool LAB = false>
 __device__ __forceinline__ void project(const DevParams &P, float r, float g, float b, float &a,
                                         float &bb, float &c, float &iy) {
+  if constexpr (LAB) {
+    float Ln, an, bn;
+    hg_lab::srgb_to_lab(r, g, b, Ln, an, bn);
+    a = -an; c = bn; bb = 0.f;
+    iy = P.intensity ? Ln : 1.f;
+    return;
+  }
   if (P.proj == HG_PROJ_RGCHROMA) {
     // rgChromaHistBlock.py:100-110: (u, v) = (R, G) / (R+G+B + eps), weight Iy.  The single plane runs through the
     // `green` path, which bins (-a, c): a = -u, c = v.
@@ -215,7 +228,7 @@ __device__ __forceinline__ void project(const DevParams &P, float r, float g, fl
 // WGT (compile time, k_hist_fwd / k_hist_bwd / k_hist_bwd_planes): false = there is no map and wn is the constant 1, which
 // the compiler folds away -- the unweighted instantiations are the kernels as they were before the map existed (with a
 // run-time NULL test instead, the forward + backward pair at the benchmark shape measured 0.4 % slower: DESIGN.md section 4).
-template <bool WGT>
+template <bool WGT, bool LAB = false>
 __device__ __forceinline__ void pixel_state(const DevParams &P, const float *xb, int b, int n, bool valid, float &r,
                                             float &g, float &bl, float &a, float &bb, float &c, float &iy, float &wn) {
   if (P.cache) {
@@ -223,12 +236,12 @@ __device__ __forceinline__ void pixel_state(const DevParams &P, const float *xb,
     const float4 u = cp[0], v = cp[1];
     a = u.x; bb = u.y; c = u.z; iy = u.w; r = v.x; g = v.y; bl = v.z;
     wn = WGT ? v.w : 1.f;
-    if (!valid) { r = g = bl = 0.f; project(P, r, g, bl, a, bb, c, iy); }
+    if (!valid) { r = g = bl = 0.f; project<LAB>(P, r, g, bl, a, bb, c, iy); }
     return;
   }
   r = g = bl = 0.f; wn = 1.f;
   if (valid) { sample_rgb(P, xb, n, r, g, bl); if (WGT) wn = sample_weight(P, b, n); }
-  project(P, r, g, bl, a, bb, c, iy);
+  project<LAB>(P, r, g, bl, a, bb, c, iy);
 }
 
 struct BinC { float chi, clo; double bd; };
@@ -271,7 +284,7 @@ __device__ __forceinline__ void lds_wave_sync() {
 // Each wave owns a contiguous run of `chunk` pixels and accumulates a (3 x BLK x BLK) partial
 // histogram block (BLK = 32*T) in 3*T*T MFMA accumulator tiles; the 4 waves are then summed through
 // LDS in fixed order and written as one slab  slabs[b][s][p][h][h]  (real bin order, flips undone).
-template <int T, int METHOD, bool SYM, bool DIAG, bool GREEN, bool SHARE = false, bool WGT = false>
+template <int T, int METHOD, bool SYM, bool DIAG, bool GREEN, bool SHARE = false, bool WGT = false, bool LAB = false>
 __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const float *__restrict__ x,
                                                      float *__restrict__ slabs, double *__restrict__ slab_tot,
                                                      const int chunk) {
@@ -416,7 +429,7 @@ __global__ __launch_bounds__(256, 2) void k_hist_fwd(const DevParams P, const fl
   for (int base = (int)start; base < end; base += 64) {
     HG_PROBE_T(pb0);
     float a, bb, c, iy;
-    project(P, r_, g_, b_, a, bb, c, iy);
+    project<LAB>(P, r_, g_, b_, a, bb, c, iy);
     const bool valid = base + lane < end;
     // the one place the weight map enters: the A-side weight of the contraction is w_n * Iy (one multiply per pixel, outside
     // the K loop); the cache keeps Iy and w_n apart for the backward
@@ -580,10 +593,17 @@ __device__ __forceinline__ void store_pixel_grad(const DevParams &P, const float
 }
 
 // Chain rule of the one-plane projections: dU = dL/du, dV = dL/dv, dW = dL/dweight
+// LAB: (u, v, weight) = (an, bn, Ln) of the clamped / resized sRGB pixel (r_, g_, b_): the Jacobian of hg_lab.h
+template <bool LAB = false>
 __device__ __forceinline__ void store_pixel_grad_proj(const DevParams &P, const float *xb, int b, int n, float r_,
                                                       float g_, float b_, float iy, float dU, float dV, float dW,
                                                       float *gdst) {
   float dr, dg, dbl;
+  if constexpr (LAB) {
+    hg_lab::srgb_to_lab_grad(r_, g_, b_, P.intensity ? dW : 0.f, dU, dV, dr, dg, dbl);
+    store_rgb_grad(P, xb, b, n, dr, dg, dbl, gdst);
+    return;
+  }
   if (P.proj == HG_PROJ_RGCHROMA) {
     // u = r/S, v = g/S, S = r+g+b+eps:  du/dr = 1/S - r/S^2, du/dg = du/db = -r/S^2 (same for v with g)
     const float S = ((r_ + g_) + b_) + kEps, inv = 1.f / S;
@@ -1041,7 +1061,7 @@ __global__ __launch_bounds__(256, kBwdWaves) void k_hist_bwd(const DevParams P, 
 template <int RT>
 struct POps { float Au[RT], Av[RT]; float ku, kv; };
 
-template <int RT, int METHOD, bool WGT = false, bool WG = false>
+template <int RT, int METHOD, bool WGT = false, bool WG = false, bool LAB = false>
 __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, const float *__restrict__ x,
                                                             const float *__restrict__ gout,
                                                             const float *__restrict__ hist,
@@ -1079,7 +1099,7 @@ __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, c
       const int n = (int)n0 + q;
       const bool valid = n < P.npix;
       float r_, g_, b_, a, bb, c, iy, wn;
-      pixel_state<WGT>(P, xb, b, n, valid, r_, g_, b_, a, bb, c, iy, wn);
+      pixel_state<WGT, LAB>(P, xb, b, n, valid, r_, g_, b_, a, bb, c, iy, wn);
       const float u = (p == 0) ? a : (p == 1 ? -a : -bb), v = (p == 0) ? bb : (p == 1 ? c : -c);
 
       // t_s = (u - lo - 4*half*step)/sigma - beta0(s)*step/sigma, double-single (beta0(s) < 128: beta0*ds_hi exact)
@@ -1191,9 +1211,9 @@ __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, c
         dIy += isum;
         if (pi + 1 < nplanes) {
           pb[n] = da; pb[P.npix + n] = db; pb[2LL * P.npix + n] = dc; pb[3LL * P.npix + n] = dIy;
-        } else if (P.proj != HG_PROJ_RGBUV) {
+        } else if (LAB || P.proj != HG_PROJ_RGBUV) {
           // one plane binned as (u, v) = (-a, c): dL/du = -da, dL/dv = dc
-          store_pixel_grad_proj(P, xb, b, n, r_, g_, b_, iy, -da, dc, P.intensity ? __fmul_rn(dIy, wn) : 0.f, gdst);
+          store_pixel_grad_proj<LAB>(P, xb, b, n, r_, g_, b_, iy, -da, dc, P.intensity ? __fmul_rn(dIy, wn) : 0.f, gdst);
         } else {
           store_pixel_grad(P, xb, b, n, r_, g_, b_, iy, da, db, dc, P.intensity ? __fmul_rn(dIy, wn) : 0.f, gdst);
         }
@@ -1247,7 +1267,7 @@ __device__ __forceinline__ void kern_eval_d(const DevParams &P, float u, int i, 
   }
 }
 
-template <int METHOD, bool WG = false>
+template <int METHOD, bool WG = false, bool LAB = false>
 __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, const float *__restrict__ x,
                                                          const float *__restrict__ gh, float *__restrict__ gdst) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1259,7 +1279,7 @@ __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, cons
   float r_ = 0.f, g_ = 0.f, b_ = 0.f, wn = 1.f;
   if (valid) { sample_rgb(P, xb, n, r_, g_, b_); wn = sample_weight(P, b, n); }
   float a, bb, c, iy;
-  project(P, r_, g_, b_, a, bb, c, iy);
+  project<LAB>(P, r_, g_, b_, a, bb, c, iy);
   // plane p: (u, v) = (su*U, sv*V) with U,V in {a,b,c}  (RGBuvHistBlock.py:112-115,150-153,190-193)
   const float uvals[3] = {a, -a, -bb}, vvals[3] = {bb, c, -c};
   float gu[3] = {0.f, 0.f, 0.f}, gv[3] = {0.f, 0.f, 0.f}, isum = 0.f;
@@ -1291,8 +1311,8 @@ __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, cons
   const float da = wiy * (gu[0] - gu[1]), db = wiy * (gv[0] - gu[2]), dc = wiy * (gv[1] - gv[2]);
   const float dIy = P.intensity ? __fmul_rn(isum, wn) : 0.f;
   if (valid) {
-    if (P.proj != HG_PROJ_RGBUV)   // one plane, binned as (u, v) = (-a, c): gu[1] = dL/du, gv[1] = dL/dv (before the weight)
-      store_pixel_grad_proj(P, xb, b, n, r_, g_, b_, iy, wiy * gu[1], wiy * gv[1], dIy, gdst);
+    if (LAB || P.proj != HG_PROJ_RGBUV)   // one plane, binned as (u, v) = (-a, c): gu[1] = dL/du, gv[1] = dL/dv (before the weight)
+      store_pixel_grad_proj<LAB>(P, xb, b, n, r_, g_, b_, iy, wiy * gu[1], wiy * gv[1], dIy, gdst);
     else
       store_pixel_grad(P, xb, b, n, r_, g_, b_, iy, da, db, dc, dIy, gdst);
     if (P.mode == HG_RESIZE_NONE)
@@ -1521,7 +1541,7 @@ __global__ __launch_bounds__(256) void k_selftest_fastlog(uint32_t first, uint32
 
 // ALL3: the grids of all planes are in LDS at once (3 h^2 x 8 B <= 150 KB, h <= 79): every pixel is read and projected
 // (3 fp64 logs) ONCE; otherwise plane after plane through one grid (the 2nd / 3rd read of a pixel hits L2).
-template <bool ALL3>
+template <bool ALL3, bool LAB = false>
 __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevParams P, const float *__restrict__ x,
                                                                     float *__restrict__ slabs,
                                                                     double *__restrict__ slab_tot, int per_block) {
@@ -1542,7 +1562,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevPar
     for (int n = n0 + threadIdx.x; n < n1; n += NT) {
       float r, g, bl, a, bb, c, iy;
       sample_rgb(P, xb, n, r, g, bl);
-      project(P, r, g, bl, a, bb, c, iy);
+      project<LAB>(P, r, g, bl, a, bb, c, iy);
       iy = __fmul_rn(sample_weight(P, b, n), iy);       // weight map, before the fixed-point conversion
       const unsigned long long q = (unsigned long long)((double)iy * kThrScale + 0.5);
       if (P.green) {
@@ -1567,7 +1587,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevPar
       for (int n = n0 + threadIdx.x; n < n1; n += NT) {
         float r, g, bl, a, bb, c, iy;
         sample_rgb(P, xb, n, r, g, bl);
-        project(P, r, g, bl, a, bb, c, iy);
+        project<LAB>(P, r, g, bl, a, bb, c, iy);
         iy = __fmul_rn(sample_weight(P, b, n), iy);
         const float u = p == 0 ? a : (p == 1 ? -a : -bb), v = p == 0 ? bb : (p == 1 ? c : -c);
         thr_scatter_plane(P, bins, u, v, inv_step, w, single, (unsigned long long)((double)iy * kThrScale + 0.5));
@@ -1590,7 +1610,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevPar
 // dL/dIy = sum over planes of Ghat at the pixel's bin(s) -- a gather -- and dx_c = dL/dIy * x_c / Iy (store_pixel_grad).
 // WG: the weight map's gradient is that gather times the pixel's non-map factor -- also without intensity_scale, where the
 // colour gradient is identically zero.
-template <bool WG = false>
+template <bool WG = false, bool LAB = false>
 __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const float *__restrict__ x,
                                                       const float *__restrict__ gh, float *__restrict__ gdst) {
   const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x, h = P.h;
@@ -1598,7 +1618,7 @@ __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const f
   const float *xb = x + (long long)b * P.sb;
   float r, g, bl, a, bb, c, iy;
   sample_rgb(P, xb, n, r, g, bl);
-  project(P, r, g, bl, a, bb, c, iy);
+  project<LAB>(P, r, g, bl, a, bb, c, iy);
   float dIy = 0.f;
   if (P.intensity || WG) {
     const double inv_step = P.step > 0.0 ? 1.0 / P.step : 0.0, w = P.half_eps * inv_step;
@@ -1627,7 +1647,7 @@ __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const f
     if (!P.intensity) dIy = 0.f;
   }
   dIy = __fmul_rn(dIy, sample_weight(P, b, n));       // weight map: dL/dIy = w_n dL/d(w_n Iy)
-  if (P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj(P, xb, b, n, r, g, bl, iy, 0.f, 0.f, dIy, gdst);
+  if (LAB || P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj<LAB>(P, xb, b, n, r, g, bl, iy, 0.f, 0.f, dIy, gdst);
   else store_pixel_grad(P, xb, b, n, r, g, bl, iy, 0.f, 0.f, 0.f, dIy, gdst);
   if (P.mode == HG_RESIZE_NONE)
     for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
@@ -1905,7 +1925,7 @@ __device__ __forceinline__ int rbf_center(const DevParams &P, float u, double in
   return (int)rint(t);
 }
 
-template <bool ALL3>
+template <bool ALL3, bool LAB = false>
 __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_rbf_fwd(const DevParams P, const float *__restrict__ x,
                                                                     float *__restrict__ slabs,
                                                                     double *__restrict__ slab_tot, int per_block, int R) {
@@ -1945,7 +1965,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_rbf_fwd(const DevPar
     for (int n = n0 + threadIdx.x; n < n1; n += NT) {
       float r, g, bl, a, bb, c, iy;
       sample_rgb(P, xb, n, r, g, bl);
-      project(P, r, g, bl, a, bb, c, iy);
+      project<LAB>(P, r, g, bl, a, bb, c, iy);
       iy = __fmul_rn(sample_weight(P, b, n), iy);       // weight map
       if (P.green) {
         scatter(bins, -a, c, iy);
@@ -1969,7 +1989,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_rbf_fwd(const DevPar
       for (int n = n0 + threadIdx.x; n < n1; n += NT) {
         float r, g, bl, a, bb, c, iy;
         sample_rgb(P, xb, n, r, g, bl);
-        project(P, r, g, bl, a, bb, c, iy);
+        project<LAB>(P, r, g, bl, a, bb, c, iy);
         iy = __fmul_rn(sample_weight(P, b, n), iy);
         scatter(bins, p == 0 ? a : (p == 1 ? -a : -bb), p == 0 ? bb : (p == 1 ? c : -c), iy);
       }
@@ -1989,7 +2009,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_rbf_fwd(const DevPar
 
 // Backward of the truncated RBF histogram: the generic backward's two mat-vecs per plane restricted to the (2R+1)^2
 // support (kernel value and slope in fp64, as k_hist_bwd_generic).
-template <bool WG = false>
+template <bool WG = false, bool LAB = false>
 __global__ __launch_bounds__(256) void k_hist_rbf_bwd(const DevParams P, const float *__restrict__ x,
                                                       const float *__restrict__ gh, float *__restrict__ gdst, int R) {
   const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x, h = P.h;
@@ -1997,7 +2017,7 @@ __global__ __launch_bounds__(256) void k_hist_rbf_bwd(const DevParams P, const f
   const float *xb = x + (long long)b * P.sb;
   float r, g, bl, a, bb, c, iy;
   sample_rgb(P, xb, n, r, g, bl);
-  project(P, r, g, bl, a, bb, c, iy);
+  project<LAB>(P, r, g, bl, a, bb, c, iy);
   const double inv_step = P.step > 0.0 ? 1.0 / P.step : 0.0;
   float gu[3] = {0.f, 0.f, 0.f}, gv[3] = {0.f, 0.f, 0.f}, isum = 0.f;
   for (int p = 0; p < 3; ++p) {
@@ -2038,7 +2058,7 @@ __global__ __launch_bounds__(256) void k_hist_rbf_bwd(const DevParams P, const f
   const float wn = sample_weight(P, b, n), wiy = __fmul_rn(wn, iy);   // weight map x Iy: the pixel's histogram weight
   const float da = wiy * (gu[0] - gu[1]), db = wiy * (gv[0] - gu[2]), dc = wiy * (gv[1] - gv[2]);
   const float dIy = P.intensity ? __fmul_rn(isum, wn) : 0.f;
-  if (P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj(P, xb, b, n, r, g, bl, iy, wiy * gu[1], wiy * gv[1], dIy, gdst);
+  if (LAB || P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj<LAB>(P, xb, b, n, r, g, bl, iy, wiy * gu[1], wiy * gv[1], dIy, gdst);
   else store_pixel_grad(P, xb, b, n, r, g, bl, iy, da, db, dc, dIy, gdst);
   if (P.mode == HG_RESIZE_NONE)
     for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
@@ -2172,7 +2192,7 @@ int validate(const hg_hist_params *p) {
   if (!(p->hi >= p->lo)) return HG_EINVAL;
   if (p->method != HG_METHOD_THRESHOLDING && !(p->sigma > 0.0)) return HG_EINVAL;
   if ((long long)p->Hs * p->Ws > 0x7fffffffLL) return HG_EINVAL;
-  if (p->projection < 0 || p->projection > 2) return HG_EINVAL;
+  if (p->projection < 0 || p->projection > HG_PROJ_LAB) return HG_EINVAL;
   return HG_OK;
 }
 
@@ -2416,14 +2436,17 @@ constexpr Among<HG_METHOD_THRESHOLDING, HG_METHOD_RBF, HG_METHOD_INVERSE_QUADRAT
 // one choice, not two bools: (WG without WGT) does not exist
 inline Among<2, 1, 0> weight_case(const DevParams &d) { return {d.gw ? 2 : d.weight ? 1 : 0}; }
 
+// HG_PROJ_LAB picks the LAB instantiations -- of the kernels a one-plane projection can reach, and of those only
+inline bool is_lab(const DevParams &d) { return d.proj == HG_PROJ_LAB; }
+
 int launch_bwd_planes(const DevParams &d, const Plan &pl, const float *x, const float *gout, const float *hist,
                       const float *sums, float *part, float *gdst, hipStream_t st) {
   const int rt = pl.rt.planes_rt;
   const size_t lds = (size_t)(32 * rt) * (32 * rt + 1) * sizeof(float);
-  return dispatch([&](auto RT, auto W, auto METHOD) {
-    return launch(k_hist_bwd_planes<RT, METHOD, W >= 1, W == 2>, dim3(pl.bwd_wgs, d.B), dim3(256), lds, st, d, x, gout, hist,
+  return dispatch([&](auto RT, auto W, auto METHOD, auto LAB) {
+    return launch(k_hist_bwd_planes<RT, METHOD, W >= 1, W == 2, LAB>, dim3(pl.bwd_wgs, d.B), dim3(256), lds, st, d, x, gout, hist,
                   sums, part, gdst, pl.rounds);
-  }, among<1, 2, 3, 4>(rt), weight_case(d), among<HG_METHOD_RBF, HG_METHOD_INVERSE_QUADRATIC>(d.method));
+  }, among<1, 2, 3, 4>(rt), weight_case(d), among<HG_METHOD_RBF, HG_METHOD_INVERSE_QUADRATIC>(d.method), is_lab(d));
 }
 
 }  // namespace
@@ -2513,14 +2536,14 @@ int hg_rgbuv_hist_fwd(const hg_hist_params *p, const float *x, float *hist_out, 
   int tot_per_split = 1;          // slab_tot entries every split of an image leaves
   switch (rt.fwd) {
     case HG_ROUTE_FWD_RBF_SCATTER:
-      rc = dispatch([&](auto ALL3) {
-        return launch(k_hist_rbf_fwd<ALL3>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk, rt.rbf_R);
-      }, rt.all3);
+      rc = dispatch([&](auto ALL3, auto LAB) {
+        return launch(k_hist_rbf_fwd<ALL3, LAB>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk, rt.rbf_R);
+      }, rt.all3, is_lab(d));
       break;
     case HG_ROUTE_FWD_THR_SCATTER:
-      rc = dispatch([&](auto ALL3) {
-        return launch(k_hist_thr_fwd<ALL3>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk);
-      }, rt.all3);
+      rc = dispatch([&](auto ALL3, auto LAB) {
+        return launch(k_hist_thr_fwd<ALL3, LAB>, grid, block, lds, st, d, x, slabs, slab_tot, 4 * pl.chunk);
+      }, rt.all3, is_lab(d));
       break;
     case HG_ROUTE_FWD_THR_LEAN:
       // (S > 1: k_hist_finish sums the slabs.  Round 3 tried ONE launch -- the last-arriving workgroup of an image, found
@@ -2540,12 +2563,13 @@ int hg_rgbuv_hist_fwd(const hg_hist_params *p, const float *x, float *hist_out, 
       // (`share` repeats, at run time, the condition under which the lambda below instantiates BND == 3: keep the two together)
       const int boundary = !rt.sym ? 0 : !diag ? 1 : !share ? 2 : 3;
       tot_per_split = pl.nbd * pl.nbd;
-      rc = dispatch([&](auto T, auto METHOD, auto GREEN, auto BND, auto WGT) {
+      rc = dispatch([&](auto T, auto METHOD, auto GREEN, auto BND, auto WGT, auto LAB) {
         if constexpr (BND == 3 && !(T == 2 && METHOD == HG_METHOD_INVERSE_QUADRATIC && !GREEN)) return (int)HG_EINVAL;   // never picked
-        else return launch(k_hist_fwd<T, METHOD, BND >= 1, BND >= 2, GREEN, BND == 3, WGT>, dim3(pl.S_fwd, tot_per_split, d.B),
+        else if constexpr (LAB && !GREEN) return (int)HG_EINVAL;   // never picked: make_dev runs every one-plane projection as `green`
+        else return launch(k_hist_fwd<T, METHOD, BND >= 1, BND >= 2, GREEN, BND == 3, WGT, LAB>, dim3(pl.S_fwd, tot_per_split, d.B),
                            dim3(256), 4 * kFwdStage * 16 + (size_t)3 * pl.BLK * pl.BLK * sizeof(float), st, d, x, slabs,
                            slab_tot, pl.chunk);
-      }, among<1, 2>(pl.T), any_method(d.method), d.green != 0, among<3, 2, 1, 0>(boundary), d.weight != nullptr);
+      }, among<1, 2>(pl.T), any_method(d.method), d.green != 0, among<3, 2, 1, 0>(boundary), d.weight != nullptr, is_lab(d));
     }
   }
   if (rc) return rc;
@@ -2602,11 +2626,11 @@ static int hist_bwd_impl(const hg_hist_params *p, const float *x, const float *g
     }
     case HG_ROUTE_BWD_RBF_GATHER:
       if ((rc = ghat())) break;
-      rc = dispatch([&](auto WG) { return launch(k_hist_rbf_bwd<WG>, grid, dim3(256), 0, st, d, x, gh, gdst, rt.rbf_R); }, wg);
+      rc = dispatch([&](auto WG, auto LAB) { return launch(k_hist_rbf_bwd<WG, LAB>, grid, dim3(256), 0, st, d, x, gh, gdst, rt.rbf_R); }, wg, is_lab(d));
       break;
     case HG_ROUTE_BWD_THR_GATHER:
       if ((rc = ghat())) break;
-      rc = dispatch([&](auto WG) { return launch(k_hist_thr_bwd<WG>, grid, dim3(256), 0, st, d, x, gh, gdst); }, wg);
+      rc = dispatch([&](auto WG, auto LAB) { return launch(k_hist_thr_bwd<WG, LAB>, grid, dim3(256), 0, st, d, x, gh, gdst); }, wg, is_lab(d));
       break;
     case HG_ROUTE_BWD_PLANES:
       rc = launch_bwd_planes(d, pl, x, grad_out, hist_out, sum_out, gh, gdst, st);
@@ -2628,9 +2652,9 @@ static int hist_bwd_impl(const hg_hist_params *p, const float *x, const float *g
       const size_t lds = (size_t)d.h * 64 * sizeof(float);
       if (lds > 160 * 1024) return HG_EUNSUPPORTED;  // h > 640
       if ((rc = ghat())) break;
-      rc = dispatch([&](auto METHOD, auto WG) {
-        return launch(k_hist_bwd_generic<METHOD, WG>, grid, dim3(64), lds, st, d, x, gh, gdst);
-      }, any_method(d.method), wg);
+      rc = dispatch([&](auto METHOD, auto WG, auto LAB) {
+        return launch(k_hist_bwd_generic<METHOD, WG, LAB>, grid, dim3(64), lds, st, d, x, gh, gdst);
+      }, any_method(d.method), wg, is_lab(d));
     }
   }
   if (rc) return rc;

@@ -7,6 +7,7 @@
 #include "hg_common.h"
 #include "../../include/hg_hist.h"
 #include "../../include/hg_post.h"
+#include "hg_lab.h"
 
 namespace {
 
@@ -527,6 +528,35 @@ bool grid_ok(long long gx, long long gy, long long gz) {
   return gx >= 1 && gx <= 0x7fffffffLL && gy >= 1 && gy <= 65535 && gz >= 1 && gz <= 65535;
 }
 
+// sRGB <-> normalised CIE Lab (hg_lab.h), one pixel per thread; grid = (pixel blocks, B).  x: element strides, out: planar
+// contiguous (B, 3, H, W).  TO_LAB clamps its input to [0, 1] first (stage 0 of the histogram blocks).
+template <bool TO_LAB>
+__global__ __launch_bounds__(256) void k_lab_convert(const float *__restrict__ x, long long xs_b, long long xs_c,
+                                                     long long xs_h, long long xs_w, float *__restrict__ out, int H, int W) {
+  const long long HW = (long long)H * W, n = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= HW) return;
+  const int y = (int)(n / W), xx = (int)(n - (long long)y * W);
+  const float *px = x + blockIdx.y * xs_b + y * xs_h + xx * xs_w;
+  const float c0 = px[0], c1 = px[xs_c], c2 = px[2 * xs_c];
+  float o0, o1, o2;
+  if constexpr (TO_LAB) hg_lab::srgb_to_lab(fminf(fmaxf(c0, 0.f), 1.f), fminf(fmaxf(c1, 0.f), 1.f), fminf(fmaxf(c2, 0.f), 1.f), o0, o1, o2);
+  else hg_lab::lab_to_srgb(c0, c1, c2, o0, o1, o2);
+  float *po = out + (long long)blockIdx.y * 3 * HW + n;
+  po[0] = o0; po[HW] = o1; po[2 * HW] = o2;
+}
+
+template <bool TO_LAB>
+int lab_convert(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_t xs_w, float *out, int32_t B, int32_t H,
+                int32_t W, void *stream) {
+  if (!x || !out || B <= 0 || H <= 0 || W <= 0) return HG_EINVAL;
+  const long long nb = ((long long)H * W + 255) / 256;
+  if (!grid_ok(nb, B, 1)) return HG_EINVAL;
+  hipLaunchKernelGGL(k_lab_convert<TO_LAB>, dim3((unsigned)nb, B), dim3(256), 0, (hipStream_t)stream, x, (long long)xs_b,
+                     (long long)xs_c, (long long)xs_h, (long long)xs_w, out, (int)H, (int)W);
+  HG_LAUNCH_CHECK();
+  return HG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -686,6 +716,16 @@ int hg_bgu_slice(const float *gamma, int32_t gh, int32_t gw, int32_t gd, const u
                      plan.nyv, plan.nxv);
   HG_LAUNCH_CHECK();
   return HG_OK;
+}
+
+int hg_srgb_to_lab(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_t xs_w, float *out, int32_t B,
+                   int32_t H, int32_t W, void *stream) {
+  return lab_convert<true>(x, xs_b, xs_c, xs_h, xs_w, out, B, H, W, stream);
+}
+
+int hg_lab_to_srgb(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_t xs_w, float *out, int32_t B,
+                   int32_t H, int32_t W, void *stream) {
+  return lab_convert<false>(x, xs_b, xs_c, xs_h, xs_w, out, B, H, W, stream);
 }
 
 }  // extern "C"

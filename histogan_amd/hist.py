@@ -32,8 +32,10 @@ class HistConfig:
 
     def __init__(self, h=64, insz=150, resizing='interpolation', method='inverse-quadratic', sigma=0.02,
                  intensity_scale=True, hist_boundary=None, green_only=False, projection='rgbuv'):
-        """projection: 'rgbuv' (RGBuvHistBlock, 3 planes, default boundary [-3,3]), 'rgchroma' (rgChromaHistBlock) or
-        'direct' (LabHistBlock): one plane, default boundary [0,1]."""
+        """projection: 'rgbuv' (RGBuvHistBlock, 3 planes, default boundary [-3,3]), 'rgchroma' (rgChromaHistBlock),
+        'direct' (LabHistBlock: the input already is normalised Lab) or 'lab' (LabHistBlock(from_rgb=True): the input is
+        sRGB and every clamped / resized pixel is converted to normalised CIE Lab first, include/hg_hist.h HG_PROJ_LAB):
+        one plane, default boundary [0,1]."""
         if projection not in _lib.HG_PROJ:
             raise ValueError(f'unknown projection {projection!r}')
         self.projection = projection

@@ -6,6 +6,9 @@ touch the GPU or any HIP runtime state: it imports nothing but torch and numpy (
 the measured path and NOT a fallback of it: GPU tensors never come here, CPU tensors never reach the HIP kernels
 (`hist.run_block` routes on the module's `device` argument only).
 
+`projection='lab'` (LabHistBlock(from_rgb=True)) has no reference counterpart: its definition is HG_PROJ_LAB of
+include/hg_hist.h, the sRGB -> normalised CIE Lab chain in fp64 rounded once to fp32, stated here on torch ops.
+
 Same arithmetic types as the reference chain (RGBuvHistBlock.py:75-228; rgChromaHistBlock.py:73-145; LabHistBlock.py:73-144):
 fp32 clamp / resize / projection, fp64 bin distances and kernel values, fp32 accumulation -- but one batched pass instead
 of the per-image Python loop: the projection is evaluated once per pixel (3 logarithms instead of 12), the two kernel
@@ -52,7 +55,31 @@ def _planes(I, cfg):
         return w, [(I[:, 0] / s, I[:, 1] / s)]
     if cfg.projection == 'direct':                 # Lab: channel 0 weighs, channels 1 / 2 are the coordinates
         return (I[:, 0] if cfg.intensity_scale else None), [(I[:, 1], I[:, 2])]
+    if cfg.projection == 'lab':                    # sRGB in: normalised CIE Lab first, then exactly 'direct'
+        L = _srgb_to_lab(I)
+        return (L[:, 0] if cfg.intensity_scale else None), [(L[:, 1], L[:, 2])]
     raise ValueError(f'unknown projection {cfg.projection!r}')
+
+
+_LAB_M = ((0.412453, 0.357580, 0.180423), (0.212671, 0.715160, 0.072169), (0.019334, 0.119193, 0.950227))
+
+
+def _srgb_to_lab(I):
+    """(b, 3, N) fp32 sRGB in [0, 1] -> (b, 3, N) fp32 (L/100, (a+128)/255, (b+128)/255): the HG_PROJ_LAB chain of
+    include/hg_hist.h, evaluated in fp64 and rounded once.  Differentiable; the branch a `where` does not take is fed a
+    value from its own domain, so its (discarded) slope is finite and no 0 * inf reaches the gradient."""
+    c = I.double()
+    hi = c > 0.04045
+    lin = torch.where(hi, ((torch.where(hi, c, torch.ones_like(c)) + 0.055) / 1.055) ** 2.4, c / 12.92)
+    M = torch.tensor(_LAB_M, dtype=torch.float64)
+    xyz = torch.einsum('ij,bjn->bin', M / M.sum(dim=1, keepdim=True), lin)
+    d = 6.0 / 29.0
+    up = xyz > d ** 3
+    f = torch.where(up, torch.where(up, xyz, torch.ones_like(xyz)) ** (1.0 / 3.0), xyz / (3 * d * d) + 4.0 / 29.0)
+    fx, fy, fz = f[:, 0], f[:, 1], f[:, 2]
+    lab = torch.stack([(116.0 * fy - 16.0) / 100.0, (500.0 * (fx - fy) + 128.0) / 255.0,
+                       (200.0 * (fy - fz) + 128.0) / 255.0], dim=1)
+    return lab.float()
 
 
 def _kernel(coord, bins, cfg):

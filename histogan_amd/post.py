@@ -161,6 +161,38 @@ def float_to_u8_hwc(x):
     return out
 
 
+# ---- device: sRGB <-> normalised CIE Lab ------------------------------------------------------------------------------
+def _lab_convert(x, fn, what):
+    if torch.is_tensor(x) and x.requires_grad:      # before any HIP call
+        raise ValueError(f'{what} is not differentiable (a data-side tool): the input requires grad.  For a Lab histogram of '
+                         f'an sRGB image with a gradient use histogram_classes.LabHistBlock(from_rgb=True)')
+    need_gpu(x, what, _FOUND)
+    if x.dim() not in (3, 4) or x.shape[-3] != 3 or not x.is_floating_point():
+        raise ValueError(f'{what}: expected a float (B, 3, H, W) or (3, H, W) tensor, got {x.dtype} {tuple(x.shape)}')
+    x4 = x if x.dim() == 4 else x.unsqueeze(0)
+    if x4.dtype != torch.float32:
+        x4 = x4.float()
+    B, _, H, W = x4.shape
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
+    with on_device(x.device):
+        check(fn(x4.data_ptr(), *x4.stride(), out.data_ptr(), B, H, W, raw_stream(x.device)), what)
+    return out if x.dim() == 4 else out[0]
+
+
+def srgb_to_lab(x):
+    """sRGB float (B, 3, H, W) or (3, H, W), any strides -> fp32 contiguous normalised CIE Lab (L/100, (a+128)/255,
+    (b+128)/255): what LabHistBlock() bins and what LabHistBlock(from_rgb=True) computes per pixel (include/hg_post.h,
+    hg_srgb_to_lab: the input is clamped to [0, 1]; fp64, rounded once).  Not differentiable: a tensor that requires grad
+    raises ValueError."""
+    return _lab_convert(x, lib.hg_srgb_to_lab, 'srgb_to_lab')
+
+
+def lab_to_srgb(x):
+    """The exact inverse of srgb_to_lab, clipped to [0, 1] (hg_lab_to_srgb): normalised Lab -> sRGB, e.g. to save what a
+    network trained on Lab images generates.  Not differentiable."""
+    return _lab_convert(x, lib.hg_lab_to_srgb, 'lab_to_srgb')
+
+
 # ---- device: pyramids -------------------------------------------------------------------------------------------------
 def pyr_down(x):
     """OpenCV pyrDown of fp32 (C, H, W): (C, (H+1)//2, (W+1)//2)."""

@@ -37,6 +37,7 @@ extern "C" {
 #define HG_PROJ_RGBUV 0
 #define HG_PROJ_RGCHROMA 1
 #define HG_PROJ_DIRECT 2
+#define HG_PROJ_LAB 3        /* since version 107 */
 
 /* stage-0 resize, RGBuvHistBlock.py:77-95 */
 #define HG_RESIZE_NONE 0      /* H<=insz and W<=insz: pixels used as they are            */
@@ -67,7 +68,13 @@ typedef struct hg_hist_params {
   /* 2-D projection of a pixel (HG_PROJ_*).  0: RGB-uv log-chroma, 3 planes.  The two one-plane variants of the
    * reference's other histogram blocks share everything else (clamp, resize, kernels, normalisation):
    * 1: rg-chroma (u,v) = (R,G)/(R+G+B+1e-6), weight Iy   (histogram_classes/rgChromaHistBlock.py:100-141)
-   * 2: direct     (u,v) = channels (1,2), weight = channel 0  (histogram_classes/LabHistBlock.py:102-140) */
+   * 2: direct     (u,v) = channels (1,2), weight = channel 0  (histogram_classes/LabHistBlock.py:102-140)
+   * 3: Lab        the input is sRGB; the clamped / resized pixel is converted to normalised CIE Lab (Ln, an, bn) =
+   *               (L/100, (a+128)/255, (b+128)/255) -- sRGB transfer curve, the D65 matrix of hg_srgb_to_lab (hg_post.h)
+   *               with every row divided by its sum, f(t) = cbrt(t) above (6/29)^3 and t/(3 (6/29)^2) + 4/29 below --
+   *               evaluated in fp64 and rounded ONCE to fp32; from there on it is a `direct` pixel: (u,v) = (an, bn),
+   *               weight = Ln.  The backward goes through the 3x3 Jacobian of that chain at the pixel.  Routes,
+   *               workspaces and cache use are those of 2. */
   int32_t projection;
   /* 1: the F.relu the train step puts in front of the block (histoGAN/histoGAN.py:955) is part of the call -- identical
    * forward (clamp(relu(x)) == clamp(x)); the backward masks x <= 0 instead of x < 0.  Saves that aten launch and node. */
@@ -82,7 +89,7 @@ typedef struct hg_hist_params {
    * + x*weight_stride_w], element strides, any layout; a stride of 0 broadcasts the map over that axis (one map for the
    * whole batch: weight_stride_b = 0).  Values are taken as clamp(w, 0, 1).  Stage 0 resizes the map exactly like a
    * colour channel (same bilinear taps / same row_idx, col_idx gather); histogram pixel n then enters with the weight
-   * w_n * Iy_n (w_n * 1 without intensity_scale, w_n * channel 0 for HG_PROJ_DIRECT).  grad_x is the gradient with w fixed
+   * w_n * Iy_n (w_n * 1 without intensity_scale, w_n * channel 0 for HG_PROJ_DIRECT, w_n * Ln for HG_PROJ_LAB).  grad_x is the gradient with w fixed
    * (exactly 0 where w_n == 0); hg_rgbuv_hist_bwd treats the map as a constant, hg_rgbuv_hist_bwd_w (since version 105)
    * also produces its gradient.  Either backward call must be given the same map as the forward.  Every kernel path
    * honours it. */
@@ -160,7 +167,7 @@ int hg_rgbuv_hist_bwd(const hg_hist_params *p, const float *x, const float *grad
 /* Backward with the gradient of the weight map (since version 105): hg_rgbuv_hist_bwd, same grad_x bit for bit, plus
  * grad_weight (B, H, W) contiguous, fully written: dL/dw at the INPUT resolution of the map -- per histogram pixel
  * m_n * sum_p k(u_p)^T Ghat_p k(v_p) with m_n the pixel's non-map factor (Iy, 1 without intensity_scale, channel 0 for
- * HG_PROJ_DIRECT), taken through the adjoint of the resize and masked by the map's clamp (passes where 0 <= w <= 1, both
+ * HG_PROJ_DIRECT, Ln for HG_PROJ_LAB), taken through the adjoint of the resize and masked by the map's clamp (passes where 0 <= w <= 1, both
  * ends inclusive; exactly 0 elsewhere).  Thresholding included (a gather of Ghat at the pixel's bins), also without
  * intensity_scale, where grad_x is identically zero.  p->weight == NULL or grad_weight == NULL: HG_EINVAL; a map with a
  * zero stride (broadcast): HG_EUNSUPPORTED -- expand it into memory first and reduce the gradient afterwards.

@@ -12,6 +12,8 @@
  *                             the caller's np.uint8(result*255))
  *   hg_u8_hwc_to_f32          uint8 HWC -> fp32 planar, x/255 (torchvision ToTensor)
  *   hg_f32_to_u8_hwc          fp32 planar -> uint8 HWC, clamp(x*255 + 0.5, 0, 255) truncated (torchvision save_image)
+ *   hg_srgb_to_lab            sRGB -> normalised CIE Lab (L/100, (a+128)/255, (b+128)/255): what LabHistBlock bins, for the
+ *   hg_lab_to_srgb            reference README's "convert loaded images into the CIE LAB space", and its exact inverse
  *
  * Conventions as in hg_hist.h: return 0 / negative HG_E* / positive hipError_t; device pointers unless stated; fp32;
  * enqueue on `stream`; never allocate or synchronise; nothing is launched for invalid arguments.  Planar images are
@@ -101,6 +103,19 @@ int hg_bgu_normal(const float *in_ds, const float *out_ds, const float *weight, 
  * LDS. */
 int hg_bgu_slice(const float *gamma, int32_t gh, int32_t gw, int32_t gd, const uint8_t *photo, int64_t xs_h,
                  int64_t xs_w, int64_t xs_c, void *out, int32_t out_u8, int32_t H, int32_t W, void *stream);
+
+/* sRGB <-> normalised CIE Lab (since version 107), the conversion HG_PROJ_LAB of hg_hist.h applies per pixel.  x: fp32
+ * (B, 3, H, W) with element strides xs_*; out: fp32 (B, 3, H, W) contiguous.  Evaluated in fp64, rounded once to fp32.
+ *   hg_srgb_to_lab: c = clamp(x, 0, 1); c_lin = c / 12.92 (c <= 0.04045) else ((c + 0.055) / 1.055)^2.4;
+ *     (X, Y, Z) = M c_lin with M = [[0.412453 0.357580 0.180423] [0.212671 0.715160 0.072169] [0.019334 0.119193 0.950227]],
+ *     every row divided by its own sum (D65 white = (1, 1, 1)); f(t) = cbrt(t) (t > (6/29)^3) else t / (3 (6/29)^2) + 4/29;
+ *     L = 116 f(Y) - 16, a = 500 (f(X) - f(Y)), b = 200 (f(Y) - f(Z));  out = (L / 100, (a + 128) / 255, (b + 128) / 255).
+ *   hg_lab_to_srgb: the exact inverse -- f^-1(s) = s^3 (s > 6/29) else 3 (6/29)^2 (s - 4/29), the inverse of the normalised
+ *     matrix, c = 12.92 l (l <= 0.04045 / 12.92) else 1.055 l^(1/2.4) - 0.055 -- ending with a clip to [0, 1]. */
+int hg_srgb_to_lab(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_t xs_w, float *out, int32_t B,
+                   int32_t H, int32_t W, void *stream);
+int hg_lab_to_srgb(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_t xs_w, float *out, int32_t B,
+                   int32_t H, int32_t W, void *stream);
 
 #ifdef __cplusplus
 }
