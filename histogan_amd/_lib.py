@@ -17,6 +17,9 @@ HG_RESIZE_NONE, HG_RESIZE_BILINEAR, HG_RESIZE_SAMPLING = 0, 1, 2
 HG_PROJ = {'rgbuv': 0, 'rgchroma': 1, 'direct': 2, 'lab': 3}
 # hg_hist_route.fwd / .bwd (the HG_ROUTE_FWD_* / HG_ROUTE_BWD_* enums of include/hg_hist.h), by value
 HG_ROUTE_FWD = ('DENSE', 'THR_SCATTER', 'THR_LEAN', 'RBF_SCATTER')
+# hg_conv_route.kind / .tile (the HG_CONV_* enums of include/hg_conv.h), by value
+HG_CONV_KIND = ('SINGLE', 'PARITY4', 'PER_CLASS')
+HG_CONV_TILE = ('16x256', '32x256', '64x256', '128x128', '128x128_SM', '64x64')
 HG_ROUTE_BWD = ('MIRRORED', 'PLANES', 'GENERIC', 'THR_GATHER', 'RBF_GATHER', 'THR_LEAN', 'ZERO')
 
 
@@ -48,6 +51,18 @@ class HgHistRoute(ctypes.Structure):
     """struct hg_hist_route (include/hg_hist.h): what hg_rgbuv_hist_route fills in."""
     _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'fwd', 'bwd', 'fwd_slices', 'bwd_workgroups', 'planes_rt',
                                               'rbf_radius', 'uses_proj_cache')]
+
+
+class HgConvQuery(ctypes.Structure):
+    """struct hg_conv_query (include/hg_conv.h): the call hg_conv2d_route is asked about."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'dgrad', 'B', 'K', 'N', 'Hi', 'Wi', 'ksize', 'stride', 'fe',
+                                              'have_workspace')] + [('workspace_bytes', ctypes.c_size_t)]
+
+
+class HgConvRoute(ctypes.Structure):
+    """struct hg_conv_route (include/hg_conv.h): what hg_conv2d_route fills in."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'kind', 'tile', 'kchunk', 'ksplit', 'reduce', 'cus')] + \
+               [('blocks', ctypes.c_int64), ('slab_bytes', ctypes.c_size_t)]
 
 
 class GlinLayer(ctypes.Structure):
@@ -149,6 +164,8 @@ def _load():
     lib.hg_conv_pack_weights_multi.argtypes = [vp, i32, i32, vp]
     lib.hg_conv2d_plan.restype = ctypes.c_int
     lib.hg_conv2d_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
+    lib.hg_conv2d_route.restype = ctypes.c_int
+    lib.hg_conv2d_route.argtypes = [ctypes.POINTER(HgConvQuery), ctypes.POINTER(HgConvRoute)]
     lib.hg_conv2d_dgrad.restype = ctypes.c_int
     lib.hg_conv2d_dgrad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
     lib.hg_conv2d_wgrad_workspace_bytes.restype = sz
@@ -245,7 +262,7 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
            'hg_rgbuv_hist_bwd', 'hg_rgbuv_hist_bwd_w_workspace_bytes', 'hg_rgbuv_hist_bwd_w', 'hg_hellinger_workspace_bytes', 'hg_hellinger_fwd_bwd', 'hg_selftest_fastlog',
            'hg_modulate_fwd', 'hg_modulate_bwd', 'hg_demod_noise_lrelu_fwd', 'hg_demod_noise_lrelu_bwd',
            'hg_diffgrad_step', 'hg_diffgrad_step_size', 'hg_diffgrad_step_dev', 'hg_ema_update', 'hg_nets_workspace_bytes', 'hg_channel_sum', 'hg_lrelu_bwd_channel_sum', 'hg_demod_weight_term', 'hg_demod_style_grad', 'hg_demod_style_grad_workspace_bytes',
-           'hg_conv_packed_elems', 'hg_conv_pack_weights', 'hg_conv_pack_weights_both', 'hg_conv_pack_blocks', 'hg_conv_pack_weights_multi', 'hg_conv2d_fwd', 'hg_conv2d_fwd_add', 'hg_modconv2d_fwd', 'hg_conv2d_workspace_bytes', 'hg_conv2d_plan', 'hg_conv2d_dgrad',
+           'hg_conv_packed_elems', 'hg_conv_pack_weights', 'hg_conv_pack_weights_both', 'hg_conv_pack_blocks', 'hg_conv_pack_weights_multi', 'hg_conv2d_fwd', 'hg_conv2d_fwd_add', 'hg_modconv2d_fwd', 'hg_conv2d_workspace_bytes', 'hg_conv2d_plan', 'hg_conv2d_route', 'hg_conv2d_dgrad',
            'hg_conv2d_wgrad_workspace_bytes',
            'hg_conv2d_wgrad',
            'hg_instnorm_workspace_bytes', 'hg_instnorm_lrelu_fwd', 'hg_instnorm_lrelu_bwd', 'hg_stencil3',
@@ -268,6 +285,17 @@ def hist_route(p, weight_grad=False):
     """hg_rgbuv_hist_route for the HgHistParams `p`: the filled HgHistRoute (host only, no launch)."""
     r = HgHistRoute(struct_size=ctypes.sizeof(HgHistRoute))
     check(lib.hg_rgbuv_hist_route(ctypes.byref(p), int(weight_grad), ctypes.byref(r)), 'hg_rgbuv_hist_route')
+    return r
+
+
+def conv_route(B, K, N, Hi, Wi, ksize, stride=1, dgrad=False, fe=False, workspace_bytes=None):
+    """hg_conv2d_route: the filled HgConvRoute (host only, no launch).  workspace_bytes None: as the workspace query plans
+    (a workspace of any size); 0: no workspace."""
+    unlimited = ctypes.c_size_t(-1).value
+    q = HgConvQuery(ctypes.sizeof(HgConvQuery), int(dgrad), B, K, N, Hi, Wi, ksize, stride, int(fe),
+                    int(workspace_bytes is None or workspace_bytes > 0), unlimited if workspace_bytes is None else workspace_bytes)
+    r = HgConvRoute(struct_size=ctypes.sizeof(HgConvRoute))
+    check(lib.hg_conv2d_route(ctypes.byref(q), ctypes.byref(r)), 'hg_conv2d_route')
     return r
 
 

@@ -12,8 +12,8 @@
 //            Output rows (channels) x columns (pixels): a lane owns one pixel, 32 consecutive lanes
 //            write 32 consecutive pixels of one channel (128 B segments).
 //            The same kernel computes the data gradient: stride 1 = the forward kernel on transposed +
-//            flipped weights; stride 2 = four launches, one per output parity class, each with the
-//            1/2/2/4 taps that reach that class (no multiplications by inserted zeros).
+//            flipped weights; stride 2 = the four output parity classes, each with the 1/2/2/4 taps
+//            that reach it (no multiplications by inserted zeros), in one launch or one each.
 //   k_wgrad  dW[tap][n][k] = sum_pixels gout[n][pixel] * X[k][pixel*IS + tap]   (K-dim = pixels, split-K
 //            over pixel chunks into slabs, then k_wgrad_reduce sums the slabs in fixed order and
 //            writes the (N,K,kh,kw) layout).
@@ -21,11 +21,9 @@
 //
 // Pixel tiles are NI images x TH rows x TW columns (all powers of two, chosen on the host per layer:
 // 32-wide rows for big maps, several whole images per tile for 4x4 / 8x8 maps).
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
-#include "hg_common.h"
-#include "../../include/hg_hist.h"
+#include "hg_host.h"
 #include "../../include/hg_conv.h"
 
 // Settled tuning constants (DESIGN.md sections 8 and 11 hold the measurements).
@@ -925,12 +923,9 @@ __global__ __launch_bounds__(256) void k_pack_multi(const hg_pack_item *__restri
 }
 
 // ------------------------------------------------------------------------------------------------
-inline int ceil_log2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
-}
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+// Host side.  Every entry point decides its launches ONCE, as a ConvRoute (make_conv_route) or a WgradPlan
+// (make_wgrad_plan): the workspace queries, the launches and the public queries hg_conv2d_plan / hg_conv2d_route all read
+// that one value.  Each kernel has one launch site; runtime values become template arguments through dispatch() (hg_host.h).
 
 // log2 of the pixel tile (width, height, images) for MB compute-grid pixels per block over an Hc x Wc grid
 inline void tile_shape(int MB, int Hc, int Wc, int min_t, int &lTW, int &lTH, int &lNI) {
@@ -942,17 +937,9 @@ inline void tile_shape(int MB, int Hc, int Wc, int min_t, int &lTW, int &lTH, in
   if (lTH > lMB - lTW) lTH = lMB - lTW;
   lNI = lMB - lTW - lTH;
 }
-// pixel tiles (grid x extent) of a launch with MB pixels per block
-inline long long pixel_tiles(int MB, int B, int Hc, int Wc, int min_t) {
-  int lTW, lTH, lNI;
-  tile_shape(MB, Hc, Wc, min_t, lTW, lTH, lNI);
-  const int TW = 1 << lTW, TH = 1 << lTH, NI = 1 << lNI;
-  return (long long)((Wc + TW - 1) / TW) * ((Hc + TH - 1) / TH) * ((B + NI - 1) / NI);
-}
 
 // pixel-tile geometry for MB compute-grid pixels per block over an Hc x Wc grid; taps span [lo, hi] in y and x
-Geom make_geom(int MB, int B, int Hc, int Wc, int IS, int lo_y, int hi_y, int lo_x, int hi_x, bool odd_chs,
-               int min_t = 4) {
+Geom make_geom(int MB, int B, int Hc, int Wc, int IS, int lo_y, int hi_y, int lo_x, int hi_x, int min_t) {
   Geom g;
   int lTW, lTH, lNI;
   tile_shape(MB, Hc, Wc, min_t, lTW, lTH, lNI);
@@ -961,7 +948,7 @@ Geom make_geom(int MB, int B, int Hc, int Wc, int IS, int lo_y, int hi_y, int lo
   g.TWp = (TW - 1) * IS + 1 + (hi_x - lo_x);
   g.IMS = ((TH - 1) * IS + 1 + (hi_y - lo_y)) * g.TWp;
   g.HALO = NI * g.IMS;
-  g.CHS = odd_chs ? (g.HALO | 1) : g.HALO;
+  g.CHS = g.HALO;
   g.inv_TWp = 1.0f / (float)g.TWp;
   g.inv_IMS = 1.0f / (float)g.IMS;
   g.inv_HALO = 1.0f / (float)g.HALO;
@@ -974,11 +961,64 @@ Geom make_geom(int MB, int B, int Hc, int Wc, int IS, int lo_y, int hi_y, int lo
 
 // tap list of one launch: offsets (dy, dx) in input coordinates relative to pixel*IS, and the packed-weight tap
 struct Taps {
-  int n, ntx, dy[9], dx[9], w[9];   // ntx = taps per row of the (rows x ntx) tap grid
+  int ntx, dy[9], dx[9], w[9];   // ntx = taps per row of the (rows x ntx) tap grid
 };
+// the ksize x ksize taps of an output or stride-1 data-gradient launch
+inline Taps square_taps(int ksize) {
+  Taps t;
+  t.ntx = ksize;
+  for (int i = 0; i < ksize * ksize; ++i) { t.dy[i] = i / ksize - ksize / 2; t.dx[i] = i % ksize - ksize / 2; t.w[i] = i; }
+  return t;
+}
+// the (1 + pY) x (1 + pX) taps that reach parity class (pY, pX) of a stride-2 data gradient:
+//   gin[2y+pY, 2x+pX] = sum over the taps (dy,dx) with dy == pY+1, dx == pX+1 (mod 2) of
+//                       gout[y + (pY+1-dy)/2, x + (pX+1-dx)/2] * W[.,.,dy,dx];  the dgrad packing stores W[dy,dx] at tap 8-(3dy+dx)
+inline Taps parity_taps(int pY, int pX) {
+  Taps t;
+  int n = 0;
+  t.ntx = 1 + pX;
+  for (int dy = 0; dy < 3; ++dy)
+    for (int dx = 0; dx < 3; ++dx)
+      if (((pY + 1 - dy) & 1) == 0 && ((pX + 1 - dx) & 1) == 0) {
+        t.dy[n] = (pY + 1 - dy) / 2; t.dx[n] = (pX + 1 - dx) / 2; t.w[n] = 8 - (3 * dy + dx);
+        ++n;
+      }
+  return t;
+}
+
+// The tile shapes of k_conv: waves along channels / pixels (WC, WP), MFMA tiles per wave (TC, TP), the MFMA tile (MT) and the
+// small-map halo bound (SM).  A block computes NB channels x MB pixels.  The values of ConvTile are part of the C ABI
+// (hg_conv2d_plan out[0], hg_conv_route.tile).
+enum ConvTile { TILE_16x256, TILE_32x256, TILE_64x256, TILE_128x128, TILE_128x128_SM, TILE_64x64 };
+struct TileShape {
+  int WC, WP, TC, TP, MT;
+  bool SM;
+  constexpr int NB() const { return WC * TC * MT; }
+  constexpr int MB() const { return WP * TP * MT; }
+};
+constexpr TileShape kTiles[6] = {
+    {1, 4, 1, 4, 16, false},   // TILE_16x256 on the 16x16x4 MFMA
+    {1, 4, 1, 2, 32, false},   // TILE_32x256
+    {1, 4, 2, 2, 32, false},   // TILE_64x256
+    {2, 2, 2, 2, 32, false},   // TILE_128x128
+    {2, 2, 2, 2, 32, true},    // TILE_128x128_SM: 4x4 maps, 8 images per pixel tile
+    {2, 2, 1, 1, 32, true}};   // TILE_64x64
+// input channels per K chunk of a tile (the stride-2 kernels stage 4 whatever kConvKC is; the 64x64 tile takes twice as many)
+constexpr int tile_kc(ConvTile t, int IS) { return t == TILE_16x256 ? 4 : (IS == 2 ? 4 : kConvKC) * (t == TILE_64x64 ? 2 : 1); }
+// 3x3 stride-1 launches of these tiles also exist with 2-channel K chunks: 16 fewer staging registers = one more block per
+// CU (4 instead of 3).  See short_k_chunks for when they are taken.
+constexpr bool has_short_chunks(ConvTile t, int TAPS, int IS) {
+  return TAPS == 9 && IS == 1 && kConvKC == 4 && (t == TILE_32x256 || t == TILE_64x256 || t == TILE_128x128);
+}
+// output blocks of a tile over B x Hc x Wc compute pixels as the planner counts them (before the K split)
+inline long long plan_blocks(ConvTile t, int B, int N, int Hc, int Wc) {
+  const long long px = (long long)B * Hc * Wc;
+  return ((N + kTiles[t].NB() - 1) / kTiles[t].NB()) * ((px + kTiles[t].MB() - 1) / kTiles[t].MB());
+}
+
+inline int out_size(int in, int stride) { return (in - 1) / stride + 1; }  // k = 3, pad 1 (or k = 1, pad 0, stride 1)
 
 // tile shape + K split of one k_conv launch
-enum ConvTile { TILE_16x256, TILE_32x256, TILE_64x256, TILE_128x128, TILE_128x128_SM, TILE_64x64 };
 struct ConvPlan {
   ConvTile tile;
   int ksplit;
@@ -989,24 +1029,6 @@ struct ConvPlan {
 // for 1 / 2 / 3 blocks of the 128x128 tile), and a launch whose block count is not a multiple of (CUs x c) ends in a
 // round at low occupancy that the dispatcher also balances badly (1024 blocks at c = 3: 104 TFLOP/s, at c = 2: 134).
 constexpr size_t kLdsPerCu = 160 * 1024;
-// per-process caches are keyed by the CURRENT device (a process that launches on a second GPU must not plan with the first
-// one's CU count, nor skip the dynamic-LDS attribute there)
-constexpr int kMaxDev = 16;
-inline int cur_dev() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-  return dev;
-}
-inline int num_cus() {
-  static int n[kMaxDev] = {0};
-  const int dev = cur_dev();
-  if (!n[dev]) {
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, dev) == hipSuccess) n[dev] = pr.multiProcessorCount;
-    if (n[dev] <= 0) n[dev] = 256;
-  }
-  return n[dev];
-}
 // *t_out: modelled duration of the launch in units of (one block alone on a CU at the full matrix rate)
 inline int pick_blocks_per_cu(long long nwg, int cmax, double *t_out = nullptr) {
   static const double e[9] = {0, 0.71, 0.85, 0.90, 0.92, 0.93, 0.93, 0.93, 0.93};
@@ -1051,15 +1073,14 @@ inline int pick_ksplit_128(long long nb, int nch, double flops, double out_bytes
 // output tiles (few pixels, many channels: the 2x2 ... 8x8 maps) split the reduction over K into slabs.
 ConvPlan plan_conv(int B, int K, int N, int Hc, int Wc, int IS, int os, bool have_ws, bool big_split = true, int taps = 9) {
   const long long pix = (long long)B * Hc * Wc;
-  auto blocks = [&](int nb, int mb) { return ((N + nb - 1) / nb) * ((pix + mb - 1) / mb); };
   const bool wide256 = Wc > 8 && Hc > 8, wide128 = Wc > 4 && Hc > 4;
   ConvPlan p;
   p.ksplit = 1;
   if (N <= 16 && wide256) { p.tile = TILE_16x256; return p; }
   if (N <= 32 && wide256) { p.tile = TILE_32x256; return p; }
-  if (N <= 64 && wide256 && blocks(64, 256) >= 384) { p.tile = TILE_64x256; return p; }
+  if (N <= 64 && wide256 && plan_blocks(TILE_64x256, B, N, Hc, Wc) >= 384) { p.tile = TILE_64x256; return p; }
   if (N > 64 && wide128) {
-    const long long nb = blocks(128, 128);
+    const long long nb = plan_blocks(TILE_128x128, B, N, Hc, Wc);
     const int nch = (K + kConvKC - 1) / kConvKC;
     const bool may_split = big_split && have_ws && os == 1 && IS == 1;
     if (nb >= 256 || (may_split && nb >= 32 && nch >= 32)) {
@@ -1071,7 +1092,7 @@ ConvPlan plan_conv(int B, int K, int N, int Hc, int Wc, int IS, int os, bool hav
   }
   // 4x4 maps (8 images per 128-pixel tile): the small-map instantiation of the 128x128 tile (larger halo bound)
   if (N > 64 && Wc == 4 && Hc == 4 && big_split && have_ws && os == 1 && IS == 1) {
-    const long long nb = blocks(128, 128);
+    const long long nb = plan_blocks(TILE_128x128_SM, B, N, Hc, Wc);
     const int nch = (K + kConvKC - 1) / kConvKC;
     if (nb >= 32 && nch >= 32) {
       int ks = (int)((512 + nb - 1) / nb);
@@ -1088,7 +1109,7 @@ ConvPlan plan_conv(int B, int K, int N, int Hc, int Wc, int IS, int os, bool hav
   if (th > 64 / tw) th = 64 / tw;
   const int ni = 64 / (tw * th);
   const long long nblk = (long long)((Wc + tw - 1) / tw) * ((Hc + th - 1) / th) * ((B + ni - 1) / ni) * ((N + 63) / 64);
-  const int kc = IS == 2 ? 8 : 2 * kConvKC, nchunks = (K + kc - 1) / kc;
+  const int kc = tile_kc(TILE_64x64, IS), nchunks = (K + kc - 1) / kc;
   // blocks to aim for: 1024 for the stride-1 launches (2x2 maps, 2048 channels: 103 -> 113 TFLOP/s; the kernel is small enough
   // for 4+ blocks per CU), 512 for the stride-2 forward and the four parity-class launches of the stride-2 data gradient
   // (measured slower with more, shorter blocks)
@@ -1102,43 +1123,111 @@ ConvPlan plan_conv(int B, int K, int N, int Hc, int Wc, int IS, int os, bool hav
   return p;
 }
 
-inline int launch_splitk_reduce(const ConvArgs &a, int ksplit, hipStream_t st);
-
-// a launch tag: unique per call within the process, never 0
-inline unsigned long long next_conv_tag() {
-  static std::atomic<unsigned long long> ctr{0x9E3779B97F4A7C15ull ^ ((unsigned long long)(uintptr_t)&ctr << 17)};
-  return ctr.fetch_add(2, std::memory_order_relaxed) | 1ull;
-}
-
-// output blocks of a plan over B x Hc x Wc compute pixels (before the K split)
-inline long long plan_blocks(const ConvPlan &p, int B, int N, int Hc, int Wc) {
-  const long long px = (long long)B * Hc * Wc;
-  const int nbt = p.tile == TILE_16x256 ? 16 : p.tile == TILE_32x256 ? 32 : (p.tile == TILE_64x256 || p.tile == TILE_64x64) ? 64 : 128;
-  const int mbt = (p.tile == TILE_128x128 || p.tile == TILE_128x128_SM) ? 128 : p.tile == TILE_64x64 ? 64 : 256;
-  return ((N + nbt - 1) / nbt) * ((px + mbt - 1) / mbt);
-}
-// 3x3 stride-1 launches: the 2-channel K-chunk kernels instead of the 4-channel ones?  (see dispatch_conv)
-inline bool short_k_chunks(const ConvPlan &p, int B, int N, int Hc, int Wc) {
+// 3x3 stride-1 launches: the 2-channel K-chunk kernels instead of the 4-channel ones?  Taken when that makes the launch whole
+// rounds of 4 blocks per CU (1024 / 2048 blocks: 134 -> 139 TFLOP/s) and for the 32-channel tile (+2..5 %); deep-K layers
+// lose 3 % to the doubled barrier count and keep the 4-channel chunks.  The fused-extras instantiations of the two larger
+// tiles fit 3 blocks per CU at either chunk size -- their epilogue is the register peak -- so they keep the 4-channel chunks.
+inline bool short_k_chunks(const ConvPlan &p, int B, int N, int Hc, int Wc, bool fe) {
   if (p.tile == TILE_32x256) return true;
-  if (p.tile == TILE_64x256 || (p.tile == TILE_128x128 && p.ksplit == 1)) {
-    const long long nwg = plan_blocks(p, B, N, Hc, Wc), cus = num_cus();
+  if (!fe && (p.tile == TILE_64x256 || (p.tile == TILE_128x128 && p.ksplit == 1))) {
+    const long long nwg = plan_blocks(p.tile, B, N, Hc, Wc), cus = num_cus();
     return nwg % (4 * cus) == 0 && nwg % (3 * cus) != 0 && nwg <= 32 * cus;
   }
   return false;
 }
 
+// ---- the route of one output / data-gradient call ----------------------------------------------------------------------
+enum ConvKind {
+  CONV_SINGLE,      // one k_conv launch
+  CONV_PARITY4,     // stride-2 data gradient: the four parity classes of the output pixels in one k_conv_parity4 launch
+  CONV_PER_CLASS    // stride-2 data gradient: one k_conv launch per (non-empty) parity class
+};
+struct ConvRoute {
+  ConvKind kind;
+  ConvTile tile;            // CONV_PER_CLASS: of the largest class; every class plans its own launch (class_tile)
+  ConvTile class_tile[4];   // CONV_PER_CLASS only
+  int kc;                   // input channels per K chunk (of `tile`)
+  int ksplit;               // K split as launched (gridDim.z)
+  size_t slab_bytes;        // workspace the route needs (the small-map CONV_PARITY4 asks for twice what it then uses)
+  long long blocks;         // blocks as the planner counts them (plan_blocks of every launch x ksplit)
+  bool reduce;              // k_splitk_reduce follows
+};
+
+// one k_conv launch over the compute grid Hc x Wc (os == 1: that is the output; os == 2: one parity class of it)
+ConvRoute route_single(int B, int K, int N, int Hc, int Wc, int taps, int IS, int os, bool have_ws, size_t ws_bytes, bool fe) {
+  ConvPlan p = plan_conv(B, K, N, Hc, Wc, IS, os, have_ws, true, taps);
+  ConvRoute r{};
+  r.kind = CONV_SINGLE;
+  r.slab_bytes = p.ksplit > 1 ? (size_t)p.ksplit * B * N * Hc * Wc * sizeof(float) : 0;   // ksplit slabs in `out` layout
+  if (r.slab_bytes > ws_bytes) { p.ksplit = 1; r.slab_bytes = 0; }   // too little scratch: no K split
+  r.tile = p.tile;
+  r.ksplit = p.ksplit;
+  r.kc = has_short_chunks(p.tile, taps, IS) && short_k_chunks(p, B, N, Hc, Wc, fe) ? 2 : tile_kc(p.tile, IS);
+  r.blocks = plan_blocks(p.tile, B, N, Hc, Wc) * p.ksplit;
+  r.reduce = p.ksplit > 1;
+  return r;
+}
+
+// have_ws / ws_bytes: the caller's workspace (the workspace queries plan with "present, unlimited"); fe: the launch carries
+// fused extras (input / output scale, noise, LeakyReLU).  Hi x Wi: the convolution's input.
+ConvRoute make_conv_route(bool dgrad, int B, int K, int N, int Hi, int Wi, int ksize, int stride, bool have_ws, size_t ws_bytes,
+                          bool fe) {
+  if (!dgrad) return route_single(B, K, N, out_size(Hi, stride), out_size(Wi, stride), ksize * ksize, stride, 1, have_ws, ws_bytes, fe);
+  if (stride == 1) return route_single(B, K, N, Hi, Wi, ksize * ksize, 1, 1, have_ws, ws_bytes, fe);
+  // stride 2: the four parity classes (pY, pX) of the output pixels, class c = 2 pY + pX of (Hi - pY + 1) / 2 x (Wi - pX + 1) / 2
+  ConvRoute r{};
+  r.ksplit = 1;
+  if (Hi > 1 && Wi > 1) {
+    // small maps (the 64x64 tile): one launch, K split decided once for the four classes (they fill disjoint pixels of the
+    // same slabs).  One launch has the blocks of all four classes: half the K split planned per class fills the chip as
+    // well, with half the slab traffic (measured best of 1 / 2 / 4) -- the workspace asked for stays the per-class plan's.
+    const ConvPlan p = plan_conv(B, K, N, (Hi + 1) / 2, (Wi + 1) / 2, 1, 1, have_ws, false);
+    if (p.tile == TILE_64x64) {
+      r.kind = CONV_PARITY4;
+      r.tile = TILE_64x64;
+      r.slab_bytes = p.ksplit > 1 ? (size_t)p.ksplit * B * N * Hi * Wi * sizeof(float) : 0;
+      if (r.slab_bytes > ws_bytes) r.slab_bytes = 0;   // too little scratch: no K split
+      if (r.slab_bytes && p.ksplit / 2 > 1) r.ksplit = p.ksplit / 2;
+    } else if (!fe) {
+      // large maps: one launch as well, for the cache-line pairing of k_conv_parity4's block order (planned on the smallest
+      // class; instantiated without the fused extras, and not for the 64x64 tile)
+      const ConvPlan pl = plan_conv(B, K, N, Hi / 2, Wi / 2, 1, 2, false, false, 4);
+      if (pl.tile != TILE_64x64) { r.kind = CONV_PARITY4; r.tile = pl.tile; }
+    }
+  }
+  if (r.kind == CONV_PARITY4) {
+    for (int c = 0; c < 4; ++c) r.blocks += plan_blocks(r.tile, B, N, (Hi - c / 2 + 1) / 2, (Wi - c % 2 + 1) / 2) * r.ksplit;
+  } else {
+    // (a 1-pixel-wide image has empty parity classes, whose slab pixels would never be written: no split, no one-launch form)
+    r.kind = CONV_PER_CLASS;
+    for (int c = 3; c >= 0; --c) {
+      const int Hc = (Hi - c / 2 + 1) / 2, Wc = (Wi - c % 2 + 1) / 2;
+      if (Hc <= 0 || Wc <= 0) continue;
+      const ConvRoute rc = route_single(B, K, N, Hc, Wc, (1 + c / 2) * (1 + c % 2), 1, 2, have_ws, ws_bytes, fe);
+      r.tile = r.class_tile[c] = rc.tile;
+      r.blocks += rc.blocks;
+    }
+  }
+  r.kc = tile_kc(r.tile, 1);
+  r.reduce = r.ksplit > 1;
+  return r;
+}
+
+inline bool has_extras(const ConvArgs &a) { return a.iscale || a.oscale || a.noise_img || a.slope > 0.f; }
+
+// ---- launches -----------------------------------------------------------------------------------------------------------
 // geometry / tap tables of one launch into `a`; returns the dynamic LDS bytes (0: not addressable, see below)
-template <int WC, int WP, int TC, int TP, int TAPS, int KC, int IS, bool SM, int MT>
+template <ConvTile TILE, int TAPS, int KC, int IS>
 size_t prep_conv(ConvArgs &a, const Taps &tp, int ksplit) {
-  constexpr int NB = WC * TC * MT, MB = WP * TP * MT;
+  constexpr TileShape T = kTiles[TILE];
   int lo_y = 0, hi_y = 0, lo_x = 0, hi_x = 0;
   for (int t = 0; t < TAPS; ++t) {
     lo_y = tp.dy[t] < lo_y ? tp.dy[t] : lo_y; hi_y = tp.dy[t] > hi_y ? tp.dy[t] : hi_y;
     lo_x = tp.dx[t] < lo_x ? tp.dx[t] : lo_x; hi_x = tp.dx[t] > hi_x ? tp.dx[t] : hi_x;
   }
-  a.g = make_geom(MB, a.B, a.Hc, a.Wc, IS, lo_y, hi_y, lo_x, hi_x, false, SM ? 2 : 4);
+  a.g = make_geom(T.MB(), a.B, a.Hc, a.Wc, IS, lo_y, hi_y, lo_x, hi_x, T.SM ? 2 : 4);
   for (int t = 0; t < TAPS; ++t) a.toff[t] = (tp.dy[t] - lo_y) * a.g.TWp + (tp.dx[t] - lo_x);
-  // the tap lists built below are (rows x ntx) grids, so the packed-weight tap index is affine in (t / ntx, t % ntx)
+  // the tap lists are (rows x ntx) grids, so the packed-weight tap index is affine in (t / ntx, t % ntx)
   a.ntx = tp.ntx;
   a.wrow0 = tp.w[0] * a.Kp;
   a.wrow_dx = tp.ntx > 1 ? (tp.w[1] - tp.w[0]) * a.Kp : 0;
@@ -1147,16 +1236,21 @@ size_t prep_conv(ConvArgs &a, const Taps &tp, int ksplit) {
   // the halo loads address one block's images with 32-bit byte offsets
   if ((long long)(1 << a.g.lNI) * a.K * a.Hi * a.Wi >= (1LL << 30)) return 0;
   // + dump rows for the spare staging lanes: 64 floats (halo) and, 16-byte aligned behind them, 64 float4 (weights)
-  return ((size_t)TAPS * KC * NB + (size_t)KC * a.g.CHS + 64 + 8 + 256) * sizeof(float);
+  return ((size_t)TAPS * KC * T.NB() + (size_t)KC * a.g.CHS + 64 + 8 + 256) * sizeof(float);
 }
 
-// blocks per CU for a launch of `nwg` blocks of `kern` (see pick_blocks_per_cu): fewer than the registers allow when that
-// makes the block count a whole number of rounds; enforced by asking for more LDS than 1/(c+1) of a CU's.  `state`: the
-// kernel's cached {register-limited blocks per CU, "large dynamic LDS allowed" flag}.
-inline int fit_blocks_per_cu(const void *kern, int threads, long long nwg, size_t &lds, int state[2], const char *what) {
+// The launch of a k_conv / k_conv_parity4 instantiation with `nwg` working blocks, at the blocks per CU pick_blocks_per_cu
+// chooses: fewer than the registers allow when that makes the block count a whole number of rounds; enforced by asking for
+// more LDS than 1/(c+1) of a CU's.  `fit`: the kernel's cached {register-limited blocks per CU, "large dynamic LDS allowed"
+// flag} on every device.
+typedef int KernelFit[kMaxDev][2];
+template <class Args>
+int launch_fitted(void (*kern)(Args), KernelFit &fit, dim3 grid, int threads, long long nwg, size_t lds, const char *what,
+                  hipStream_t st, const Args &a) {
+  int *state = fit[cur_dev()];
   if (!state[0]) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, threads, lds) != hipSuccess || n < 1) n = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)kern, threads, lds) != hipSuccess || n < 1) n = 1;
     state[0] = n;
   }
   const int by_lds = (int)(kLdsPerCu / lds), cm = by_lds < state[0] ? (by_lds > 1 ? by_lds : 1) : state[0];
@@ -1167,145 +1261,104 @@ inline int fit_blocks_per_cu(const void *kern, int threads, long long nwg, size_
   }
   static const bool dbg = getenv("HG_CONV_DEBUG") != nullptr;
   if (dbg) fprintf(stderr, "%s: %lld blocks, max %d (registers %d) -> %d per CU, lds %zu\n", what, nwg, cm, state[0], c, lds);
-  if (lds > 48 * 1024 && !state[1]) {   // dynamic LDS above 48 KB has to be allowed once per kernel
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
+  if (lds > 48 * 1024 && !state[1]) {   // dynamic LDS above 48 KB has to be allowed once per kernel and device
+    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
     if (e != hipSuccess) return (int)e;
     state[1] = 1;
   }
-  return 0;
+  return launch_allowed(kern, grid, dim3(threads), lds, st, a);
 }
 
-// ws_bytes: size of the scratch behind a.slab (0: unknown -> no in-kernel combination)
-template <int WC, int WP, int TC, int TP, int TAPS, int KC, int IS, bool SM = false, int MT = 32>
-int launch_conv(ConvArgs a, const Taps &tp, int ksplit, bool reduce, hipStream_t st, size_t ws_bytes = 0) {
-  constexpr int NB = WC * TC * MT, NT = WC * WP * 64;
-  size_t lds = prep_conv<WC, WP, TC, TP, TAPS, KC, IS, SM, MT>(a, tp, ksplit);
+template <ConvTile TILE, int TAPS, int KC, int IS>
+int launch_conv(ConvArgs a, const Taps &tp, int ksplit, hipStream_t st) {
+  constexpr TileShape T = kTiles[TILE];
+  size_t lds = prep_conv<TILE, TAPS, KC, IS>(a, tp, ksplit);
   if (!lds) return HG_EUNSUPPORTED;
-  bool inkernel_combine = false;
-  (void)ws_bytes;
-  const bool fe = a.iscale || a.oscale || a.noise_img || a.slope > 0.f;
-  auto kern = fe ? k_conv<WC, WP, TC, TP, TAPS, KC, IS, SM, MT, true> : k_conv<WC, WP, TC, TP, TAPS, KC, IS, SM, MT, false>;
-  static int state[2][2] = {{0, 0}, {0, 0}};
-  const long long nwg = (long long)a.g.tiles_x * a.g.tiles_y * a.g.groups * ((a.N + NB - 1) / NB) * ksplit;
+  const bool fe = has_extras(a);
+  auto kern = fe ? k_conv<T.WC, T.WP, T.TC, T.TP, TAPS, KC, IS, T.SM, T.MT, true> : k_conv<T.WC, T.WP, T.TC, T.TP, TAPS, KC, IS, T.SM, T.MT, false>;
+  static KernelFit fit[2] = {};
+  const dim3 grid((unsigned)(a.g.tiles_x * a.g.tiles_y * a.g.groups), (unsigned)((a.N + T.NB() - 1) / T.NB()), (unsigned)ksplit);
   char what[96];
-  snprintf(what, sizeof what, "k_conv<%d,%d,%d,%d,taps %d,kc %d,is %d,mt %d,fe %d>", WC, WP, TC, TP, TAPS, KC, IS, MT, (int)fe);
-  if (int rc = fit_blocks_per_cu((const void *)kern, NT, nwg, lds, state[fe], what)) return rc;
-  unsigned gx = (unsigned)(a.g.tiles_x * a.g.tiles_y * a.g.groups);
-  if (inkernel_combine) {
-    // the splits of a tile (blockIdx.z) share an XCD when gridDim.x * gridDim.y is a multiple of 8 (linear id mod 8).  Pad x
-    // only as far as that needs: padding 4 pixel tiles x 16 channel blocks to 8 x 16 left the real blocks on XCDs 0-3 (2x time)
-    const unsigned ny = (unsigned)((a.N + NB - 1) / NB);
-    unsigned m = 8;
-    for (unsigned d = 2; d <= 8; d *= 2) if (ny % d == 0) m = 8 / d;
-    gx = (gx + m - 1) / m * m;
-  }
-  dim3 grid(gx, (unsigned)((a.N + NB - 1) / NB), (unsigned)ksplit);
-  hipLaunchKernelGGL(kern, grid, dim3(NT), lds, st, a);
-  HG_LAUNCH_CHECK();
-  if (ksplit > 1 && reduce && !inkernel_combine) return launch_splitk_reduce(a, ksplit, st);
-  return HG_OK;
+  snprintf(what, sizeof what, "k_conv<%d,%d,%d,%d,taps %d,kc %d,is %d,mt %d,fe %d>", T.WC, T.WP, T.TC, T.TP, TAPS, KC, IS, T.MT, (int)fe);
+  return launch_fitted(kern, fit[fe], grid, T.WC * T.WP * 64, (long long)grid.x * grid.y * grid.z, lds, what, st, a);
 }
 
-// the four parity-class launches of a stride-2 data gradient as one (k_conv_parity4); the caller reduces the K-split slabs
-template <int WC, int WP, int TC, int TP, int KC, bool SM = false, int MT = 32, bool WITH_FE = true>
+// one k_conv launch on a route's tile and K-chunk size
+template <int TAPS, int IS>
+int launch_conv_tile(const ConvArgs &a, const Taps &tp, ConvTile tile, int kc, int ksplit, hipStream_t st) {
+  return dispatch([&](auto TILE) {
+    constexpr ConvTile T = (ConvTile)decltype(TILE)::value;
+    if constexpr (T == TILE_128x128_SM && IS != 1) return (int)HG_EUNSUPPORTED;   // (planned for stride 1 only)
+    else {
+      if constexpr (has_short_chunks(T, TAPS, IS)) {
+        if (kc == 2) return launch_conv<T, TAPS, 2, IS>(a, tp, ksplit, st);
+      }
+      return launch_conv<T, TAPS, tile_kc(T, IS), IS>(a, tp, ksplit, st);
+    }
+  }, among<TILE_16x256, TILE_32x256, TILE_64x256, TILE_128x128, TILE_128x128_SM, TILE_64x64>(tile));
+}
+
+// the four parity classes of a stride-2 data gradient as one launch (k_conv_parity4); the fused extras are instantiated
+// for the 64x64 tile only (the route takes this form only for images at least 2 x 2: no class is empty)
+template <ConvTile TILE>
 int launch_conv_parity4(const ConvArgs (&base)[4], const Taps (&tp)[4], int ksplit, hipStream_t st) {
-  constexpr int NB = WC * TC * MT, NT = WC * WP * 64;
+  constexpr TileShape T = kTiles[TILE];
+  constexpr int KC = tile_kc(TILE, 1);
   ConvArgs4 a4;
   size_t lds = 0;
   long long tiles_sum = 0;
   int tiles_max = 0;
   for (int c = 0; c < 4; ++c) {
     a4.c[c] = base[c];
-    a4.tiles[c] = 0;
-    if (base[c].Hc <= 0 || base[c].Wc <= 0) continue;   // empty class (1-pixel-wide image)
-    size_t l = c == 0 ? prep_conv<WC, WP, TC, TP, 1, KC, 1, SM, MT>(a4.c[c], tp[c], ksplit)
-               : c == 3 ? prep_conv<WC, WP, TC, TP, 4, KC, 1, SM, MT>(a4.c[c], tp[c], ksplit)
-                        : prep_conv<WC, WP, TC, TP, 2, KC, 1, SM, MT>(a4.c[c], tp[c], ksplit);
+    size_t l = c == 0 ? prep_conv<TILE, 1, KC, 1>(a4.c[c], tp[c], ksplit)
+               : c == 3 ? prep_conv<TILE, 4, KC, 1>(a4.c[c], tp[c], ksplit)
+                        : prep_conv<TILE, 2, KC, 1>(a4.c[c], tp[c], ksplit);
     if (!l) return HG_EUNSUPPORTED;
     lds = l > lds ? l : lds;
     a4.tiles[c] = a4.c[c].g.tiles_x * a4.c[c].g.tiles_y * a4.c[c].g.groups;
     tiles_sum += a4.tiles[c];
     tiles_max = a4.tiles[c] > tiles_max ? a4.tiles[c] : tiles_max;
   }
-  if (!tiles_max) return HG_OK;
-  const ConvArgs &a = base[0];
-  const bool fe = a.iscale || a.oscale || a.noise_img || a.slope > 0.f;
+  constexpr bool WITH_FE = TILE == TILE_64x64;
+  const bool fe = has_extras(base[0]);
   if (fe && !WITH_FE) return HG_EUNSUPPORTED;
-  auto kern = k_conv_parity4<WC, WP, TC, TP, KC, SM, MT, false>;
-  if constexpr (WITH_FE) { if (fe) kern = k_conv_parity4<WC, WP, TC, TP, KC, SM, MT, true>; }
-  static int state[2][2] = {{0, 0}, {0, 0}};
-  const int ny = (a.N + NB - 1) / NB;
-  if (int rc = fit_blocks_per_cu((const void *)kern, NT, tiles_sum * ny * ksplit, lds, state[fe], "k_conv_parity4")) return rc;
+  auto kern = k_conv_parity4<T.WC, T.WP, T.TC, T.TP, KC, T.SM, T.MT, false>;
+  if constexpr (WITH_FE) { if (fe) kern = k_conv_parity4<T.WC, T.WP, T.TC, T.TP, KC, T.SM, T.MT, true>; }
+  static KernelFit fit[2] = {};
+  const int ny = (base[0].N + T.NB() - 1) / T.NB();
   // (only where the tiles alone cover the XCDs: 4 tiles x 16 channel blocks of a 4x4 map would use 4 of the 8 -- 94 -> 163 us)
   const bool xcd_map = tiles_max >= 64;
   a4.xcd_map = xcd_map;
   const unsigned gx = xcd_map ? (unsigned)((tiles_max + 7) / 8 * 32) : (unsigned)(4 * tiles_max);
-  hipLaunchKernelGGL(kern, dim3(gx, (unsigned)ny, (unsigned)ksplit), dim3(NT), lds, st, a4);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch_fitted(kern, fit[fe], dim3(gx, (unsigned)ny, (unsigned)ksplit), T.WC * T.WP * 64, tiles_sum * ny * ksplit, lds,
+                       "k_conv_parity4", st, a4);
 }
 
-// K-split scratch: ksplit slabs in `out` layout, then (256-byte aligned) one 64-bit flag per (output tile, split) for the
-// in-kernel combination.  Hc x Wc: the compute grid of the launch (== Ho x Wo for stride-1 / forward launches).
-inline size_t conv_slab_bytes(const ConvPlan &p, int B, int N, int Ho, int Wo) {
-  return p.ksplit > 1 ? (size_t)p.ksplit * B * N * Ho * Wo * sizeof(float) : 0;
-}
-inline size_t conv_ws_bytes(const ConvPlan &p, int B, int N, int Ho, int Wo) { return conv_slab_bytes(p, B, N, Ho, Wo); }
-
-
+// the K-split slabs of a route (behind a.slab, `out` layout) summed in fixed order, with the epilogue
 inline int launch_splitk_reduce(const ConvArgs &a, int ksplit, hipStream_t st) {
   const long long total = (long long)a.B * a.N * a.Ho * a.Wo;
   long long nb = (total + 255) / 256;
   if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)nb), dim3(256), 0, st, a.slab, a.out, a.oscale, a.bias, a.noise_w,
-                     a.noise_img, a.addend, a.noise_S, a.slope, total, a.Ho * a.Wo, a.Wo, a.N, ksplit);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_splitk_reduce, dim3((unsigned)nb), dim3(256), 0, st, a.slab, a.out, a.oscale, a.bias, a.noise_w, a.noise_img,
+                a.addend, a.noise_S, a.slope, total, a.Ho * a.Wo, a.Wo, a.N, ksplit);
 }
 
-// force_ksplit > 0: the caller fixed the K split (and reduces the slabs itself); the 64x64 tile is used
+// a CONV_SINGLE route: the launch and its reduce
 template <int TAPS, int IS>
-int dispatch_conv(ConvArgs a, const Taps &tp, void *ws, size_t ws_bytes, hipStream_t st, int force_ksplit = 0) {
-  constexpr int KC = IS == 2 ? 4 : kConvKC;
-  a.slab = (float *)ws;
-  if (force_ksplit > 0) return launch_conv<2, 2, 1, 1, TAPS, 2 * KC, IS, true>(a, tp, force_ksplit, false, st);
-  ConvPlan p = plan_conv(a.B, a.K, a.N, a.Hc, a.Wc, IS, a.os, ws != nullptr, true, TAPS);
-  if (conv_slab_bytes(p, a.B, a.N, a.Ho, a.Wo) > ws_bytes) p.ksplit = 1;   // too little scratch: no K split
-  // 3x3 stride-1 launches also exist with 2-channel K chunks: 16 fewer staging registers = one more block per CU (4
-  // instead of 3).  Taken when that makes the launch whole rounds (1024 / 2048 blocks: 134 -> 139 TFLOP/s) and for the
-  // 32-channel tile (+2..5 %); deep-K layers lose 3 % to the doubled barrier count and keep the 4-channel chunks.
-  if constexpr (TAPS == 9 && IS == 1 && KC == 4) {
-    // (the fused-extras instantiations of the two larger tiles fit 3 blocks per CU at either chunk size -- their epilogue
-    // is the register peak -- so they keep the 4-channel chunks)
-    const bool fe = a.iscale || a.oscale || a.noise_img || a.slope > 0.f;
-    if (short_k_chunks(p, a.B, a.N, a.Hc, a.Wc) && (!fe || p.tile == TILE_32x256)) {
-      if (p.tile == TILE_32x256) return launch_conv<1, 4, 1, 2, TAPS, 2, IS>(a, tp, 1, true, st);
-      if (p.tile == TILE_64x256) return launch_conv<1, 4, 2, 2, TAPS, 2, IS>(a, tp, 1, true, st);
-      return launch_conv<2, 2, 2, 2, TAPS, 2, IS>(a, tp, 1, true, st);
-    }
-  }
-  switch (p.tile) {
-    case TILE_16x256:   // 16 ch x 256 px on the 16x16x4 MFMA
-      return launch_conv<1, 4, 1, 4, TAPS, 4, IS, false, 16>(a, tp, 1, true, st);
-    case TILE_32x256: return launch_conv<1, 4, 1, 2, TAPS, KC, IS>(a, tp, 1, true, st);
-    case TILE_64x256: return launch_conv<1, 4, 2, 2, TAPS, KC, IS>(a, tp, 1, true, st);
-    case TILE_128x128: return launch_conv<2, 2, 2, 2, TAPS, KC, IS>(a, tp, p.ksplit, true, st, ws_bytes);
-    case TILE_128x128_SM:
-      if constexpr (IS == 1) return launch_conv<2, 2, 2, 2, TAPS, KC, IS, true>(a, tp, p.ksplit, true, st, ws_bytes);
-      else return HG_EUNSUPPORTED;
-    default: return launch_conv<2, 2, 1, 1, TAPS, 2 * KC, IS, true>(a, tp, p.ksplit, true, st, ws_bytes);
-  }
+int run_conv(const ConvArgs &a, const Taps &tp, const ConvRoute &r, hipStream_t st) {
+  if (int rc = launch_conv_tile<TAPS, IS>(a, tp, r.tile, r.kc, r.ksplit, st)) return rc;
+  return r.reduce ? launch_splitk_reduce(a, r.ksplit, st) : HG_OK;
 }
 
+// ---- weight gradient ------------------------------------------------------------------------------------------------------
 struct WgradPlan {
   int PC, lTW, tiles_x, tiles_y, groups;
   int MT;          // MFMA tile: 16 when both channel counts are <= 16, else 32
   int WN, WK, WS;  // waves per block along n / k / pixel split
+  int TS;          // 3: the rows of the 3x3 kernel are split over waves as well (12-wave blocks); else 1
   int nchunks, splits, ktiles, ntiles, Kp32, Np32;
   size_t slab_bytes;
 };
-
-inline int out_size(int in, int stride) { return (in - 1) / stride + 1; }  // k = 3, pad 1 (or k = 1, pad 0, stride 1)
 
 // pixels per chunk of k_wgrad.  128 where the per-chunk overhead (staging pass, barrier) has the least MFMA work to hide
 // behind: the 16x16 tile (4x less work per pixel) and the pixel-split 32-channel tiles of the 3x3 kernel (each of the WS
@@ -1322,8 +1375,6 @@ WgradPlan make_wgrad_plan(int B, int K, int N, int Hi, int Wi, int ksize, int st
   if (p.MT == 16 && lTW < 2) lTW = 2;   // 4 pixels per 16x16x4 MFMA must share a row
   if (lTW > 5) lTW = 5;
   p.lTW = lTW;
-  // pixels per chunk: the 16x16 tile does 4x less MFMA work per pixel, so it takes 128-pixel chunks where the halo of
-  // 128 pixels still fits one staging pass (rows >= 8 wide)
   if (p.MT == 16) {
     p.WN = p.WK = 1;
   } else if (stride == 2) {  // only two shapes are instantiated for stride 2
@@ -1348,13 +1399,16 @@ WgradPlan make_wgrad_plan(int B, int K, int N, int Hi, int Wi, int ksize, int st
   if (s > p.nchunks) s = p.nchunks;
   if (s < 1) s = 1;
   p.splits = s;
+  // the 3x3 kernel on the 32x32 MFMA splits its rows over waves: always on the 2 x 2-wave tile, on the others where the
+  // slabs go through k_wgrad_reduce (splits == 1 stores gw directly, through an LDS transpose of the whole tile)
+  p.TS = (ksize == 3 && p.MT == 32 && ((p.WN == 2 && p.WK == 2) || s > 1)) ? 3 : 1;
   p.Kp32 = p.ktiles * p.WK * p.MT;
   p.Np32 = p.ntiles * p.WN * p.MT;
   p.slab_bytes = (size_t)s * ksize * ksize * p.Kp32 * p.Np32 * sizeof(float);   // one slab per block (WS waves combined in LDS)
   return p;
 }
 
-template <int WN, int WK, int WS, int TAPS, int LTW, int IS, int MT = 32, int TS = 1>
+template <int WN, int WK, int WS, int TAPS, int LTW, int IS, int MT, int TS>
 int launch_wgrad_k(const WgradArgs &a, const WgradPlan &p, hipStream_t st) {
   constexpr int PC = wgrad_chunk_pixels(IS, MT, LTW, WS, TAPS);
   using G = CGeom<PC, LTW, TAPS == 9 ? 1 : 0, IS>;
@@ -1370,41 +1424,15 @@ int launch_wgrad_k(const WgradArgs &a, const WgradPlan &p, hipStream_t st) {
   }
   const bool sc = a.iscale != nullptr || a.gscale != nullptr;
   auto kern = sc ? k_wgrad<WN, WK, WS, TAPS, PC, LTW, IS, MT, TS, true> : k_wgrad<WN, WK, WS, TAPS, PC, LTW, IS, MT, TS, false>;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.ktiles * p.ntiles), (unsigned)p.splits), dim3(WN * WK * WS * TS * 64), lds, st, a);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(kern, dim3((unsigned)(p.ktiles * p.ntiles), (unsigned)p.splits), dim3(WN * WK * WS * TS * 64), lds, st, a);
 }
 
-template <int TAPS, int LTW, int IS>
-int launch_wgrad_g(const WgradArgs &a, const WgradPlan &p, hipStream_t st) {
-  if constexpr (LTW >= 2) {
-    if (p.MT == 16) return launch_wgrad_k<1, 1, 4, TAPS, LTW, IS, 16>(a, p, st);
-  }
-  if (p.WN == 2 && p.WK == 2) {
-    if constexpr (TAPS == 9) {
-      return launch_wgrad_k<2, 2, 1, TAPS, LTW, IS, 32, 3>(a, p, st);   // kernel rows split over waves
-    }
-    return launch_wgrad_k<2, 2, 1, TAPS, LTW, IS>(a, p, st);
-  }
-  if constexpr (IS == 1) {
-    if constexpr (TAPS == 9) {
-      if (a.gw == nullptr) {
-        if (p.WN == 2) return launch_wgrad_k<2, 1, 2, TAPS, LTW, IS, 32, 3>(a, p, st);
-        if (p.WK == 2) return launch_wgrad_k<1, 2, 2, TAPS, LTW, IS, 32, 3>(a, p, st);
-        return launch_wgrad_k<1, 1, 4, TAPS, LTW, IS, 32, 3>(a, p, st);
-      }
-    }
-    if (p.WN == 2) return launch_wgrad_k<2, 1, 2, TAPS, LTW, IS>(a, p, st);
-    if (p.WK == 2) return launch_wgrad_k<1, 2, 2, TAPS, LTW, IS>(a, p, st);
-  }
-  if constexpr (TAPS == 9 && IS == 2) {
-    if (a.gw == nullptr) return launch_wgrad_k<1, 1, 4, TAPS, LTW, IS, 32, 3>(a, p, st);
-  }
-  return launch_wgrad_k<1, 1, 4, TAPS, LTW, IS>(a, p, st);
+// which k_wgrad shapes are compiled: the 16x16 tile one wave set on rows of >= 4 pixels; stride 2 only the square wave
+// layouts; the row split for the 3x3 kernel only.  (The 3x3 2 x 2-wave tile is only ever planned WITH the row split; its
+// unsplit form has always been compiled too and stays, so that the library's kernel set does not change.)
+constexpr bool wgrad_exists(int WN, int WK, int TAPS, int LTW, int IS, int MT, int TS) {
+  if (MT == 16) return LTW >= 2 && WN == 1 && WK == 1 && TS == 1;
+  return (TS == 1 || TAPS == 9) && (IS == 1 || WN == WK);
 }
 
 template <int TAPS, int IS>
@@ -1412,19 +1440,14 @@ int launch_wgrad(WgradArgs a, const WgradPlan &p, float *gw, hipStream_t st) {
   a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y;
   a.nchunks = p.nchunks; a.splits = p.splits; a.ktiles = p.ktiles; a.Kp32 = p.Kp32; a.Np32 = p.Np32;
   a.gw = (p.splits == 1) ? gw : nullptr;
-  int rc;
-  switch (p.lTW) {
-    case 1: rc = launch_wgrad_g<TAPS, 1, IS>(a, p, st); break;
-    case 2: rc = launch_wgrad_g<TAPS, 2, IS>(a, p, st); break;
-    case 3: rc = launch_wgrad_g<TAPS, 3, IS>(a, p, st); break;
-    case 4: rc = launch_wgrad_g<TAPS, 4, IS>(a, p, st); break;
-    default: rc = launch_wgrad_g<TAPS, 5, IS>(a, p, st); break;
-  }
+  const int rc = dispatch([&](auto LTW, auto MT16, auto WN2, auto WK2, auto TS3) {
+    constexpr int MT = MT16 ? 16 : 32, WN = WN2 ? 2 : 1, WK = WK2 ? 2 : 1, TS = TS3 ? 3 : 1;
+    if constexpr (wgrad_exists(WN, WK, TAPS, LTW, IS, MT, TS)) return launch_wgrad_k<WN, WK, 4 / (WN * WK), TAPS, LTW, IS, MT, TS>(a, p, st);
+    else return (int)HG_EUNSUPPORTED;   // (make_wgrad_plan plans none of these)
+  }, among<1, 2, 3, 4, 5>(p.lTW), p.MT == 16, p.WN == 2, p.WK == 2, p.TS == 3);
   if (rc || a.gw) return rc;
-  hipLaunchKernelGGL(k_wgrad_reduce<TAPS>, dim3((unsigned)((a.K + 31) / 32), (unsigned)TAPS, (unsigned)a.N), dim3(256), 0, st,
-                     a.slab, gw, a.N, a.K, p.Np32, p.Kp32, p.splits);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_wgrad_reduce<TAPS>, dim3((unsigned)((a.K + 31) / 32), (unsigned)TAPS, (unsigned)a.N), dim3(256), 0, st, a.slab, gw,
+                a.N, a.K, p.Np32, p.Kp32, p.splits);
 }
 
 inline bool conv_args_ok(int B, int K, int N, int H, int W, int ksize, int stride) {
@@ -1437,6 +1460,7 @@ inline bool fits_i32(int B, int K, int N, int H, int W) {
   const long long lim = 0x7fffffffLL;
   return (long long)B * K * H * W < lim && (long long)B * N * H * W < lim;
 }
+constexpr Among<9, 1> pack_taps(int ksize) { return {ksize * ksize}; }
 
 }  // namespace
 
@@ -1456,28 +1480,14 @@ int hg_conv_pack_weights(const float *w, float *wt, int32_t Co, int32_t Ci, int3
   // the grid covers the padded extent so that the padding is written (as zeros)
   const int CiP = mode == HG_CONV_PACK_FWD ? Kp : Np, CoP = mode == HG_CONV_PACK_FWD ? Np : Kp;
   const dim3 grid((unsigned)((CiP + 31) / 32), (unsigned)((CoP + 31) / 32));
-  hipStream_t st = (hipStream_t)stream;
-  if (ksize == 3)
-    hipLaunchKernelGGL(k_pack<9>, grid, dim3(256), 0, st, w, wt, Co, Ci, Kp, Np, mode);
-  else
-    hipLaunchKernelGGL(k_pack<1>, grid, dim3(256), 0, st, w, wt, Co, Ci, Kp, Np, mode);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return dispatch([&](auto TAPS) { return launch(k_pack<TAPS>, grid, dim3(256), 0, (hipStream_t)stream, w, wt, Co, Ci, Kp, Np, mode); },
+                  pack_taps(ksize));
 }
 
 size_t hg_conv2d_workspace_bytes(int32_t B, int32_t K, int32_t N, int32_t Hi, int32_t Wi, int32_t ksize, int32_t stride,
                                  int32_t dgrad) {
   if (!conv_args_ok(B, K, N, Hi, Wi, ksize, stride)) return 0;
-  if (dgrad) {
-    if (stride != 1) {
-      if (Hi == 1 || Wi == 1) return 0;
-      const ConvPlan p = plan_conv(B, K, N, (Hi + 1) / 2, (Wi + 1) / 2, 1, 1, true, false);
-      return p.tile == TILE_64x64 && p.ksplit > 1 ? (size_t)p.ksplit * B * N * Hi * Wi * sizeof(float) : 0;
-    }
-    return conv_ws_bytes(plan_conv(B, K, N, Hi, Wi, 1, 1, true, true, ksize * ksize), B, N, Hi, Wi);
-  }
-  const int Ho = out_size(Hi, stride), Wo = out_size(Wi, stride);
-  return conv_ws_bytes(plan_conv(B, K, N, Ho, Wo, stride, 1, true, true, ksize * ksize), B, N, Ho, Wo);
+  return make_conv_route(dgrad != 0, B, K, N, Hi, Wi, ksize, stride, true, SIZE_MAX, false).slab_bytes;
 }
 
 int32_t hg_conv_pack_blocks(int32_t Co, int32_t Ci) {
@@ -1487,24 +1497,35 @@ int32_t hg_conv_pack_blocks(int32_t Co, int32_t Ci) {
 
 int hg_conv_pack_weights_multi(const hg_pack_item *items_dev, int32_t n_items, int32_t total_blocks, void *stream) {
   if (!items_dev || n_items <= 0 || total_blocks <= 0) return HG_EINVAL;
-  hipLaunchKernelGGL(k_pack_multi, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, items_dev, n_items);
-  HG_LAUNCH_CHECK();
+  return launch(k_pack_multi, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, items_dev, n_items);
+}
+
+int hg_conv2d_route(const hg_conv_query *q, hg_conv_route *out) {
+  if (!q || q->struct_size != (int32_t)sizeof(hg_conv_query) || !out || out->struct_size != (int32_t)sizeof(hg_conv_route)) return HG_EINVAL;
+  if (!conv_args_ok(q->B, q->K, q->N, q->Hi, q->Wi, q->ksize, q->stride)) return HG_EINVAL;
+  if (!fits_i32(q->B, q->K, q->N, q->Hi, q->Wi)) return HG_EUNSUPPORTED;
+  const ConvRoute r = make_conv_route(q->dgrad != 0, q->B, q->K, q->N, q->Hi, q->Wi, q->ksize, q->stride, q->have_workspace != 0,
+                                      q->workspace_bytes, q->fe != 0);
+  out->kind = (int32_t)r.kind;
+  out->tile = (int32_t)r.tile;
+  out->kchunk = r.kc;
+  out->ksplit = r.ksplit;
+  out->reduce = r.reduce;
+  out->cus = num_cus();
+  out->blocks = r.blocks;
+  out->slab_bytes = r.slab_bytes;
   return HG_OK;
 }
 
 int hg_conv2d_plan(int32_t B, int32_t K, int32_t N, int32_t Hi, int32_t Wi, int32_t ksize, int32_t stride, int32_t dgrad,
                    int32_t out[5]) {
   if (!out || !conv_args_ok(B, K, N, Hi, Wi, ksize, stride)) return HG_EINVAL;
-  if (dgrad && stride != 1) return HG_EUNSUPPORTED;   // four parity-class launches: no single plan
-  const int Hc = dgrad ? Hi : out_size(Hi, stride), Wc = dgrad ? Wi : out_size(Wi, stride);
-  const ConvPlan p = plan_conv(B, K, N, Hc, Wc, dgrad ? 1 : stride, 1, true, true, ksize * ksize);
-  const bool k2 = ksize == 3 && stride == 1 && short_k_chunks(p, B, N, Hc, Wc);
-  const int base_kc = (dgrad ? 1 : stride) == 2 ? 4 : kConvKC;
-  out[0] = (int32_t)p.tile;
-  out[1] = p.ksplit;
-  out[2] = p.tile == TILE_16x256 ? 4 : (p.tile == TILE_64x64 ? 2 * base_kc : (k2 ? 2 : base_kc));
-  const long long nb = plan_blocks(p, B, N, Hc, Wc) * p.ksplit;
-  out[3] = nb > 0x7fffffffLL ? 0x7fffffff : (int32_t)nb;
+  if (dgrad && stride != 1) return HG_EUNSUPPORTED;   // not one k_conv launch: hg_conv2d_route answers
+  const ConvRoute r = make_conv_route(dgrad != 0, B, K, N, Hi, Wi, ksize, stride, true, SIZE_MAX, false);
+  out[0] = (int32_t)r.tile;
+  out[1] = r.ksplit;
+  out[2] = r.kc;
+  out[3] = r.blocks > 0x7fffffffLL ? 0x7fffffff : (int32_t)r.blocks;
   out[4] = num_cus();
   return HG_OK;
 }
@@ -1515,13 +1536,9 @@ int hg_conv_pack_weights_both(const float *w, float *wt_fwd, float *wt_dgrad, in
   const int Kpf = round_up(Ci, 16), Npf = round_up(Co, 128), Kpd = round_up(Co, 16), Npd = round_up(Ci, 128);
   // the grid covers both padded extents so that all padding is written
   const dim3 grid((unsigned)(round_up(Ci, 128) / 32), (unsigned)(round_up(Co, 128) / 32));
-  hipStream_t st = (hipStream_t)stream;
-  if (ksize == 3)
-    hipLaunchKernelGGL(k_pack_both<9>, grid, dim3(256), 0, st, w, wt_fwd, wt_dgrad, Co, Ci, Kpf, Npf, Kpd, Npd);
-  else
-    hipLaunchKernelGGL(k_pack_both<1>, grid, dim3(256), 0, st, w, wt_fwd, wt_dgrad, Co, Ci, Kpf, Npf, Kpd, Npd);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return dispatch([&](auto TAPS) {
+    return launch(k_pack_both<TAPS>, grid, dim3(256), 0, (hipStream_t)stream, w, wt_fwd, wt_dgrad, Co, Ci, Kpf, Npf, Kpd, Npd);
+  }, pack_taps(ksize));
 }
 
 static int conv2d_fwd_impl(const float *in, const float *wt, float *out, const float *iscale, const float *oscale,
@@ -1541,16 +1558,12 @@ static int conv2d_fwd_impl(const float *in, const float *wt, float *out, const f
   a.Ho = a.Hc = out_size(Hi, stride); a.Wo = a.Wc = out_size(Wi, stride);
   a.os = 1; a.oy = a.ox = 0;
   a.Kp = round_up(K, 16); a.Np = round_up(N, 128);
-  Taps tp;
+  a.slab = (float *)workspace;
+  const ConvRoute r = make_conv_route(false, B, K, N, Hi, Wi, ksize, stride, workspace != nullptr, workspace_bytes, has_extras(a));
+  const Taps tp = square_taps(ksize);
   hipStream_t st = (hipStream_t)stream;
-  if (ksize == 1) {
-    tp.n = 1; tp.ntx = 1; tp.dy[0] = tp.dx[0] = 0; tp.w[0] = 0;
-    return dispatch_conv<1, 1>(a, tp, workspace, workspace_bytes, st);
-  }
-  tp.n = 9; tp.ntx = 3;
-  for (int t = 0; t < 9; ++t) { tp.dy[t] = t / 3 - 1; tp.dx[t] = t % 3 - 1; tp.w[t] = t; }
-  return stride == 1 ? dispatch_conv<9, 1>(a, tp, workspace, workspace_bytes, st)
-                     : dispatch_conv<9, 2>(a, tp, workspace, workspace_bytes, st);
+  if (ksize == 1) return run_conv<1, 1>(a, tp, r, st);
+  return stride == 1 ? run_conv<9, 1>(a, tp, r, st) : run_conv<9, 2>(a, tp, r, st);
 }
 
 int hg_conv2d_fwd(const float *in, const float *wt, float *out, const float *iscale, const float *oscale,
@@ -1589,82 +1602,38 @@ int hg_conv2d_dgrad(const float *gout, const float *wt, float *gin, const float 
   a.Hi = out_size(Hi, stride); a.Wi = out_size(Wi, stride);  // the kernel's input is grad_out
   a.Ho = Hi; a.Wo = Wi;
   a.Kp = round_up(K, 16); a.Np = round_up(N, 128);
-  Taps tp;
+  a.slab = (float *)workspace;
+  const ConvRoute r = make_conv_route(true, B, K, N, Hi, Wi, ksize, stride, workspace != nullptr, workspace_bytes, has_extras(a));
   if (stride == 1) {
     a.Hc = Hi; a.Wc = Wi; a.os = 1; a.oy = a.ox = 0;
-    if (ksize == 1) {
-      tp.n = 1; tp.ntx = 1; tp.dy[0] = tp.dx[0] = 0; tp.w[0] = 0;
-      return dispatch_conv<1, 1>(a, tp, workspace, workspace_bytes, st);
-    }
-    tp.n = 9; tp.ntx = 3;
-    for (int t = 0; t < 9; ++t) { tp.dy[t] = t / 3 - 1; tp.dx[t] = t % 3 - 1; tp.w[t] = t; }
-    return dispatch_conv<9, 1>(a, tp, workspace, workspace_bytes, st);
+    const Taps tp = square_taps(ksize);
+    return ksize == 1 ? run_conv<1, 1>(a, tp, r, st) : run_conv<9, 1>(a, tp, r, st);
   }
-  // stride 2: gin[2y+pY, 2x+pX] = sum over the taps (dy,dx) with dy == pY+1, dx == pX+1 (mod 2) of
-  //           gout[y + (pY+1-dy)/2, x + (pX+1-dx)/2] * W[.,.,dy,dx];  the dgrad packing stores W[dy,dx] at tap 8-(3dy+dx)
   a.os = 2;
-  // K split decided once for the four parity launches (they fill disjoint pixels of the same slabs)
-  int ksplit = 0;
-  bool plan64 = false;
-  {
-    ConvPlan p = plan_conv(B, K, N, (Hi + 1) / 2, (Wi + 1) / 2, 1, 1, workspace != nullptr, false);
-    plan64 = p.tile == TILE_64x64 && Hi > 1 && Wi > 1;
-    // (a 1-pixel-wide image has empty parity classes, whose slab pixels would never be written: no split then)
-    if (Hi > 1 && Wi > 1 && p.tile == TILE_64x64 && p.ksplit > 1 &&
-        (size_t)p.ksplit * B * N * Hi * Wi * sizeof(float) <= workspace_bytes)
-      ksplit = p.ksplit;
-  }
   ConvArgs ca[4];
   Taps tps[4];
-  for (int pY = 0; pY < 2; ++pY)
-    for (int pX = 0; pX < 2; ++pX) {
-      ConvArgs &c = ca[pY * 2 + pX];
-      Taps &t = tps[pY * 2 + pX];
-      c = a;
-      c.Hc = (Hi - pY + 1) / 2; c.Wc = (Wi - pX + 1) / 2;
-      c.oy = pY; c.ox = pX;
-      t.n = 0; t.ntx = pX ? 2 : 1;
-      for (int dy = 0; dy < 3; ++dy)
-        for (int dx = 0; dx < 3; ++dx)
-          if (((pY + 1 - dy) & 1) == 0 && ((pX + 1 - dx) & 1) == 0) {
-            t.dy[t.n] = (pY + 1 - dy) / 2; t.dx[t.n] = (pX + 1 - dx) / 2; t.w[t.n] = 8 - (3 * dy + dx);
-            ++t.n;
-          }
-    }
-  if (!plan64 && Hi > 1 && Wi > 1) {
-    // large maps: the four classes in one launch as well, for the cache-line pairing of k_conv_parity4's block order
-    const ConvPlan p = plan_conv(B, K, N, Hi / 2, Wi / 2, 1, 2, false, false, 4);   // (the smallest class)
-    int rc = HG_EUNSUPPORTED;
-    switch (p.tile) {
-      case TILE_16x256: rc = launch_conv_parity4<1, 4, 1, 4, 4, false, 16, false>(ca, tps, 1, st); break;
-      case TILE_32x256: rc = launch_conv_parity4<1, 4, 1, 2, kConvKC, false, 32, false>(ca, tps, 1, st); break;
-      case TILE_64x256: rc = launch_conv_parity4<1, 4, 2, 2, kConvKC, false, 32, false>(ca, tps, 1, st); break;
-      case TILE_128x128: rc = launch_conv_parity4<2, 2, 2, 2, kConvKC, false, 32, false>(ca, tps, 1, st); break;
-      default: break;
-    }
-    if (rc != HG_EUNSUPPORTED) return rc;
+  for (int c = 0; c < 4; ++c) {
+    const int pY = c / 2, pX = c % 2;
+    ca[c] = a;
+    ca[c].Hc = (Hi - pY + 1) / 2; ca[c].Wc = (Wi - pX + 1) / 2;
+    ca[c].oy = pY; ca[c].ox = pX;
+    tps[c] = parity_taps(pY, pX);
   }
-  if (plan64) {
-    // small maps (the 64x64 tile): the four classes in one launch
-    // (one launch has the blocks of all four classes: half the K split planned per class fills the chip as well, with
-    // half the slab traffic -- measured best of 1 / 2 / 4)
-    if (ksplit > 1) ksplit = ksplit / 2 > 1 ? ksplit / 2 : 1;
-    for (int c = 0; c < 4; ++c) ca[c].slab = (float *)workspace;
-    const int rc = launch_conv_parity4<2, 2, 1, 1, 2 * kConvKC, true>(ca, tps, ksplit > 1 ? ksplit : 1, st);
+  if (r.kind == CONV_PARITY4) {
+    const int rc = dispatch([&](auto TILE) {
+      if constexpr (TILE == TILE_128x128_SM) return (int)HG_EUNSUPPORTED;   // (never planned for a parity class)
+      else return launch_conv_parity4<(ConvTile)decltype(TILE)::value>(ca, tps, r.ksplit, st);
+    }, among<TILE_16x256, TILE_32x256, TILE_64x256, TILE_128x128, TILE_128x128_SM, TILE_64x64>(r.tile));
     if (rc) return rc;
-  } else {
-    for (int c = 0; c < 4; ++c) {
-      if (ca[c].Hc <= 0 || ca[c].Wc <= 0) continue;
-      int rc;
-      if (tps[c].n == 1) rc = dispatch_conv<1, 1>(ca[c], tps[c], workspace, workspace_bytes, st, ksplit);
-      else if (tps[c].n == 2) rc = dispatch_conv<2, 1>(ca[c], tps[c], workspace, workspace_bytes, st, ksplit);
-      else rc = dispatch_conv<4, 1>(ca[c], tps[c], workspace, workspace_bytes, st, ksplit);
-      if (rc) return rc;
-    }
+    return r.reduce ? launch_splitk_reduce(a, r.ksplit, st) : HG_OK;
   }
-  if (ksplit > 1) {
-    a.slab = (float *)workspace;
-    return launch_splitk_reduce(a, ksplit, st);
+  for (int c = 0; c < 4; ++c) {
+    if (ca[c].Hc <= 0 || ca[c].Wc <= 0) continue;
+    const ConvTile t = r.class_tile[c];
+    const int rc = c == 0 ? launch_conv_tile<1, 1>(ca[c], tps[c], t, tile_kc(t, 1), 1, st)
+                   : c == 3 ? launch_conv_tile<4, 1>(ca[c], tps[c], t, tile_kc(t, 1), 1, st)
+                            : launch_conv_tile<2, 1>(ca[c], tps[c], t, tile_kc(t, 1), 1, st);
+    if (rc) return rc;
   }
   return HG_OK;
 }

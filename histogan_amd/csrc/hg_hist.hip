@@ -26,14 +26,13 @@
 // (c_hi,c_lo) a double-single split of -b_i/sigma, which keeps t to ~1e-7 relative without fp64;
 // thresholding compares in fp64 so its 0/1 weights are bit-identical to the reference's.
 // v_mfma_f32_32x32x2_f32 is an exact fp32 fma chain (no reduced-precision path on gfx950).
-#include "hg_common.h"
-#include "../../include/hg_hist.h"
+#include "hg_host.h"
 #include "hg_lab.h"
 #include <cstdlib>
 
-#define HG_VERSION_NUM 107   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
+#define HG_VERSION_NUM 108   // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
                              // 104: hg_bgu_normal, hg_bgu_slice (hg_post.h); 105: hg_rgbuv_hist_bwd_w (gradient of the weight map);
-                             // 106: hg_rgbuv_hist_route; 107: HG_PROJ_LAB, hg_srgb_to_lab, hg_lab_to_srgb (hg_post.h)
+                             // 106: hg_rgbuv_hist_route; 107: HG_PROJ_LAB, hg_srgb_to_lab, hg_lab_to_srgb (hg_post.h); 108: hg_conv2d_route (hg_conv.h)
 
 // Settled schedule constants of the dense kernels (DESIGN.md sections 4 and 11 hold the measurements).
 constexpr int kFwdMfmaGroup = 12;    // k_hist_fwd at configs[1]: groups of 1: 505 us, 3: 498, 6: 473, 12: 465
@@ -2398,38 +2397,7 @@ bool share_rcp_ok(const DevParams &d) {
   return den * den * den * den < 1e30;
 }
 
-// ---- runtime values -> template arguments ---------------------------------------------------------------------------
-// dispatch(f, picks...) calls the generic lambda f with one compile-time constant per pick: a bool becomes a
-// std::bool_constant, among<V0, V1, ...>(v) the std::integral_constant<int, Vi> with Vi == v (the last one when none is).
-template <int... Vs> struct Among { int v; };
-template <int... Vs> Among<Vs...> among(int v) { return {v}; }
-
-template <class F> int dispatch(F &&f) { return f(); }
-template <class F, int V0, int... Vs, class... Rest> int dispatch(F &&f, Among<V0, Vs...> a, Rest... rest);
-
-template <class F, class... Rest> int dispatch(F &&f, bool b, Rest... rest) {
-  auto with = [&](auto c) { return dispatch([&](auto... cs) { return f(c, cs...); }, rest...); };
-  return b ? with(std::true_type{}) : with(std::false_type{});
-}
-
-template <class F, int V0, int... Vs, class... Rest> int dispatch(F &&f, Among<V0, Vs...> a, Rest... rest) {
-  auto head = [&] { return dispatch([&](auto... cs) { return f(std::integral_constant<int, V0>{}, cs...); }, rest...); };
-  if constexpr (sizeof...(Vs) == 0) return head();
-  else return a.v == V0 ? head() : dispatch(f, Among<Vs...>{a.v}, rest...);
-}
-
-// the one launch: dynamic LDS above 48 KB is asked for on the kernel that is launched
-template <class... KArgs>
-int launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, std::decay_t<KArgs>... args) {
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
-}
-
+// (dispatch / among / launch: hg_host.h)
 constexpr Among<HG_METHOD_THRESHOLDING, HG_METHOD_RBF, HG_METHOD_INVERSE_QUADRATIC> any_method(int m) { return {m}; }
 
 // the weight map's three cases of the MFMA backwards: 0 none, 1 a constant map (WGT), 2 its gradient too (WGT, WG) --

@@ -18,9 +18,7 @@
 //     each thread applies A^T . A to (channel, tile) pairs, the fused epilogue of hg_modconv2d_fwd, and stores 2x2 pixels.
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
-#include "hg_common.h"
-#include "../../include/hg_hist.h"
+#include "hg_host.h"
 #include "../../include/hg_conv.h"
 #include "../../include/hg_wino.h"
 
@@ -825,30 +823,6 @@ __global__ __launch_bounds__(256) void k_wino_wgrad_reduce(const float *__restri
     for (int g = 0; g < SG; ++g) v += part[g][kl >> 2][(kl & 3) * 9 + rc];
     gw[((size_t)n * K + kb) * 9 + q] = v;
   }
-}
-
-inline int ceil_log2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
-}
-// per-process caches are keyed by the CURRENT device (a process that launches on a second GPU must not plan with the first
-// one's CU count, nor skip the dynamic-LDS attribute there)
-constexpr int kMaxDev = 16;
-inline int cur_dev() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-  return dev;
-}
-inline int num_cus() {
-  static int n[kMaxDev] = {0};
-  const int dev = cur_dev();
-  if (!n[dev]) {
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, dev) == hipSuccess) n[dev] = pr.multiProcessorCount;
-    if (n[dev] <= 0) n[dev] = 256;
-  }
-  return n[dev];
 }
 
 // the variant serving N output channels: 0 = 64 ch x 64 tiles (KC 8), 1 = 32 ch x 128 tiles (KC 4)

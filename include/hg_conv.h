@@ -88,19 +88,70 @@ typedef struct hg_pack_item {
 int32_t hg_conv_pack_blocks(int32_t Co, int32_t Ci);
 int hg_conv_pack_weights_multi(const hg_pack_item *items_dev, int32_t n_items, int32_t total_blocks, void *stream);
 
-/* The launch plan hg_conv2d_fwd (dgrad = 0) / the stride-1 hg_conv2d_dgrad (dgrad = 1) take for these arguments (host logic
- * only, no device work; with no GPU present 256 CUs are assumed):
+/* Which launches a call takes (since version 108).  The library decides this once per call, as one route: the same
+ * decision sizes the workspace (hg_conv2d_workspace_bytes), picks the launches of hg_conv2d_fwd / _fwd_add /
+ * hg_modconv2d_fwd / hg_conv2d_dgrad, and is what the two queries below return.  DESIGN.md section 8 has the rules. */
+enum {
+  HG_CONV_SINGLE = 0,    /* one k_conv launch [-> k_splitk_reduce when reduce]: every output, the stride-1 data gradient     */
+  HG_CONV_PARITY4 = 1,   /* stride-2 data gradient: the four parity classes of the output pixels in ONE k_conv_parity4
+                            launch [-> k_splitk_reduce]: images of at least 2 x 2 whose classes take the 64 x 64 tile, and
+                            larger ones without input / output scales                                                       */
+  HG_CONV_PER_CLASS = 2  /* stride-2 data gradient: one k_conv launch per non-empty parity class (1 x N images; large maps
+                            with scales; maps between the two one-launch forms)                                             */
+};
+enum {                   /* channels x pixels of a block's output tile                                                        */
+  HG_CONV_TILE_16x256 = 0, HG_CONV_TILE_32x256 = 1, HG_CONV_TILE_64x256 = 2, HG_CONV_TILE_128x128 = 3,
+  HG_CONV_TILE_128x128_SM = 4,   /* 128 x 128 on 4 x 4 maps (8 images per pixel tile)                                         */
+  HG_CONV_TILE_64x64 = 5
+};
+
+typedef struct hg_conv_query {
+  int32_t struct_size;          /* sizeof(hg_conv_query) as the caller compiled it (ABI guard)                              */
+  int32_t dgrad;                /* 0: hg_conv2d_fwd / _fwd_add / hg_modconv2d_fwd, 1: hg_conv2d_dgrad                        */
+  int32_t B, K, N, Hi, Wi, ksize, stride;   /* as passed to that call                                                        */
+  int32_t fe;                   /* != 0: the launch carries fused extras (any of iscale, oscale, noise, lrelu_slope > 0)     */
+  int32_t have_workspace;       /* 0: the call's workspace is NULL                                                           */
+  size_t workspace_bytes;       /* the call's workspace_bytes (SIZE_MAX: as the workspace query plans, "unlimited")          */
+} hg_conv_query;
+
+typedef struct hg_conv_route {
+  int32_t struct_size;          /* in: sizeof(hg_conv_route) as the caller compiled it (ABI guard)                           */
+  int32_t kind;                 /* HG_CONV_SINGLE / _PARITY4 / _PER_CLASS                                                    */
+  int32_t tile;                 /* HG_CONV_TILE_*; PER_CLASS: of the largest class (the smaller ones plan their own)         */
+  int32_t kchunk;               /* input channels staged per K chunk: 4, 8 on the 64 x 64 tile, 2 on the 3x3 stride-1
+                                   launches that gain a fourth block per CU from it (never with fe on the 64 x 256 and
+                                   128 x 128 tiles)                                                                          */
+  int32_t ksplit;               /* K split as launched (gridDim.z): after "too little workspace: no split" and after the
+                                   one-launch stride-2 data gradient has halved the split planned per class                  */
+  int32_t reduce;               /* 1: k_splitk_reduce follows (== ksplit > 1)                                                */
+  int32_t cus;                  /* compute units planned for (256 when no GPU is present)                                    */
+  int64_t blocks;               /* blocks of all launches as the planner counts them: ceil(N / tile channels) x
+                                   ceil(pixels / tile pixels) x ksplit, summed over the parity classes -- the number the K
+                                   split and the chunk size are chosen by: whole rounds of (CUs x blocks per CU)             */
+  size_t slab_bytes;            /* workspace the route uses, == hg_conv2d_workspace_bytes for an unlimited workspace:
+                                   ksplit x B x N x Ho x Wo x 4, except that the small-map PARITY4 form asks for the split
+                                   planned per class (twice what it launches, or more); 0 without a split                    */
+} hg_conv_route;
+
+/* Fills *out (all fields but struct_size) for the call `q` describes.  Host logic only: launches nothing, touches no
+ * device and needs none.  NULL pointers, a stale struct_size or arguments the call itself refuses: HG_EINVAL; tensors
+ * beyond 2^31 elements: HG_EUNSUPPORTED, as from the call. */
+int hg_conv2d_route(const hg_conv_query *q, hg_conv_route *out);
+
+/* The same route for a plain launch (fe = 0, unlimited workspace) of hg_conv2d_fwd (dgrad = 0) / the stride-1
+ * hg_conv2d_dgrad (dgrad = 1), as five ints (host logic only, no device work; with no GPU present 256 CUs are assumed):
  *   out[0] tile (0: 16 ch x 256 px, 1: 32 x 256, 2: 64 x 256, 3: 128 x 128, 4: 128 x 128 small-map, 5: 64 x 64),
  *   out[1] K split, out[2] input channels per K chunk, out[3] blocks of the launch, out[4] CUs planned for.
  * The block count decides the K split and the chunk size: a launch should be a whole number of rounds of
- * (CUs x blocks per CU) -- DESIGN.md section 8. */
+ * (CUs x blocks per CU) -- DESIGN.md section 8.  The stride-2 data gradient is not one launch: HG_EUNSUPPORTED here,
+ * hg_conv2d_route answers. */
 int hg_conv2d_plan(int32_t B, int32_t K, int32_t N, int32_t Hi, int32_t Wi, int32_t ksize, int32_t stride, int32_t dgrad,
                    int32_t out[5]);
 
 /* Data gradient of that convolution:  gin (B,N,Hi,Wi) <- gout (B,K,Ho,Wo), K = the convolution's OUTPUT
  * channels, N = its INPUT channels, (Hi,Wi) = the size of the convolution's input; wt packed with
  * HG_CONV_PACK_DGRAD.   gin[b,n] = oscale[b,n] * sum_k dgrad(iscale[b,k] * gout[b,k]).
- * Stride 2 runs as four launches (one per parity class of the output pixel). */
+ * Stride 2 runs per parity class of the output pixel: all four in one launch, or one launch each (hg_conv2d_route). */
 int hg_conv2d_dgrad(const float *gout, const float *wt, float *gin, const float *iscale, const float *oscale,
                     int32_t B, int32_t K, int32_t N, int32_t Hi, int32_t Wi, int32_t ksize, int32_t stride,
                     void *workspace, size_t workspace_bytes, void *stream);
