@@ -127,6 +127,8 @@ def _load():
     lib.hg_demod_noise_lrelu_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.hg_demod_noise_lrelu_bwd.restype = ctypes.c_int
     lib.hg_demod_noise_lrelu_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]
+    lib.hg_noise_grad.restype = ctypes.c_int
+    lib.hg_noise_grad.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.hg_lrelu_bwd_channel_sum.restype = ctypes.c_int
     lib.hg_lrelu_bwd_channel_sum.argtypes = [vp, vp, f32, vp, vp, i32, i32, i32, vp, sz, vp]
     lib.hg_demod_style_grad_workspace_bytes.restype = ctypes.c_size_t
@@ -271,7 +273,7 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
            'hg_grouped_linear_bwd_input', 'hg_grouped_linear_bwd_params',
            'hg_wino_supported', 'hg_wino_packed_elems', 'hg_wino_pack_weights', 'hg_wino_pack_blocks', 'hg_wino_pack_weights_multi', 'hg_wino_workspace_bytes', 'hg_wino_conv2d',
            'hg_wino_wgrad_supported', 'hg_wino_wgrad_workspace_bytes', 'hg_wino_wgrad',
-           'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd',
+           'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd', 'hg_noise_grad',
            'hg_resize_axis', 'hg_pyr_down', 'hg_pyr_up_add', 'hg_color_moments_workspace_bytes', 'hg_color_moments',
            'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc', 'hg_bgu_normal_workspace_bytes', 'hg_bgu_normal',
            'hg_bgu_slice', 'hg_srgb_to_lab', 'hg_lab_to_srgb')

@@ -334,6 +334,65 @@ __global__ __launch_bounds__(256) void k_dnl_bwd_finish(const float *__restrict_
   gb[p] = v2;
 }
 
+// The noise image's gradient of one stage: gnzt[b,i,j] (+)= sum_o (wn[o] / d[b,o]) gconv[b,o,i,j] -- the reduction over
+// CHANNELS per pixel that none of the kernels above does (they reduce over pixels per channel).  A workgroup owns PT units
+// of VEC consecutive pixels of one sample (PT a power of two <= 64, chosen by the host) and splits the channels over its
+// CS = 256 / PT thread rows: row r takes channels r, r + CS, ... in increasing order.  The 64 / PT rows of a wave are
+// folded with xor shuffles (strides 32 ... PT), the 4 waves meet in LDS and are added as (0 + 1) + (2 + 3) by the ONE
+// thread that owns the output element: no atomics, the same bits on every run.  Small maps get PT = 1 ... 8: the 2048-term
+// sums of the 4 x 4 stage run 256 wide over 4 workgroups instead of serially; at PT = 64 (large maps) a wave reads 1 KiB
+// of one channel per pass and the scale wn / d is wave-uniform.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_noise_grad(const float *__restrict__ gconv, const float *__restrict__ d,
+                                                    const float *__restrict__ wn, float *__restrict__ gnzt, int O, int H,
+                                                    int S, int PT, int nblk, int accumulate) {
+  __shared__ float sm[4 * 64 * VEC];
+  const int CS = 256 / PT;
+  const int px = threadIdx.x & (PT - 1), cs = threadIdx.x / PT;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.x / nblk, blk = blockIdx.x - b * nblk;
+  const int HW = H * H, NU = HW / VEC;
+  const int u = blk * PT + px;
+  float acc[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+  if (u < NU) {
+    const float *gp = gconv + (size_t)b * O * HW + (size_t)u * VEC;
+    const float *dp = d ? d + (size_t)b * O : nullptr;
+#pragma unroll 4
+    for (int o = cs; o < O; o += CS) {
+      const float sc = dp ? wn[o] / dp[o] : wn[o];
+      if constexpr (VEC == 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(gp + (size_t)o * HW);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = fmaf(sc, v[k], acc[k]);
+      } else {
+        acc[0] = fmaf(sc, gp[(size_t)o * HW], acc[0]);
+      }
+    }
+  }
+  for (int off = 32; off >= PT; off >>= 1) {       // (block-uniform bounds: every lane shuffles)
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] += __shfl_xor(acc[k], off, 64);
+  }
+  if (lane < PT) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) sm[(wave * PT + lane) * VEC + k] = acc[k];
+  }
+  __syncthreads();
+  const int f = threadIdx.x;                  // element f of the block's PT * VEC consecutive pixels
+  const int n = PT * VEC;
+  if (f < n) {
+    const int p = blk * n + f;
+    if (p < HW) {
+      const float r = (sm[f] + sm[n + f]) + (sm[2 * n + f] + sm[3 * n + f]);
+      const int i = p / H, j = p - i * H;
+      float *q = gnzt + (size_t)b * S * S + (size_t)i * S + j;
+      *q = accumulate ? *q + r : r;
+    }
+  }
+}
+
 // sum over (b, h, w) of a (B, C, HW) tensor -> out[C]  (bias gradient); grid = (chunks, C), partials + finish
 __global__ __launch_bounds__(256) void k_channel_sum(const float *__restrict__ g, float *__restrict__ part, int B, int C,
                                                      int HW) {
@@ -643,6 +702,28 @@ int hg_demod_noise_lrelu_bwd(const float *gout, const float *out, const float *c
   HG_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_dnl_bwd_finish, dim3((planes + 255) / 256), dim3(256), 0, st, part, gd, gwn_part, gbn_part,
                      (!conv && d) ? d : nullptr, planes, chunks);
+  HG_LAUNCH_CHECK();
+  return HG_OK;
+}
+
+int hg_noise_grad(const float *gconv, const float *d, const float *wn, float *gnzt, int32_t B, int32_t O, int32_t H,
+                  int32_t S, int32_t accumulate, void *stream) {
+  // (the same H, S guard as hg_demod_noise_lrelu_fwd: any window that fits the noise image)
+  if (!gconv || !wn || !gnzt || B <= 0 || O <= 0 || H <= 0 || S < H) return HG_EINVAL;
+  const bool vec = (H & 3) == 0 && ((uintptr_t)gconv & 15) == 0;      // 16-byte loads: 4 pixels of one row
+  const long long units = (long long)H * H / (vec ? 4 : 1);
+  // pixel units per workgroup: 64, halved until the launch has >= 512 workgroups (two per CU) or one unit each
+  int pt = 64;
+  while (pt > 1 && (long long)B * ((units + pt - 1) / pt) < 512) pt >>= 1;
+  const long long nblk = (units + pt - 1) / pt;
+  if (H > 32768 || nblk * B >= (1ll << 31)) return HG_EUNSUPPORTED;      // 32-bit pixel index / grid size
+  hipStream_t st = (hipStream_t)stream;
+  if (vec)
+    hipLaunchKernelGGL((k_noise_grad<4>), dim3((unsigned)(nblk * B)), dim3(256), 0, st, gconv, d, wn, gnzt, O, H, S, pt,
+                       (int)nblk, accumulate != 0);
+  else
+    hipLaunchKernelGGL((k_noise_grad<1>), dim3((unsigned)(nblk * B)), dim3(256), 0, st, gconv, d, wn, gnzt, O, H, S, pt,
+                       (int)nblk, accumulate != 0);
   HG_LAUNCH_CHECK();
   return HG_OK;
 }

@@ -19,7 +19,7 @@ import torch
 
 from . import conv as C
 from ._lib import f32c
-from .launch import gstage_bwd, modulate_bwd, modulate_fwd, torgb_fits, torgb_fwd
+from .launch import gstage_bwd, modulate_bwd, modulate_fwd, noise_grad, torgb_fits, torgb_fwd
 from .ops import demod_bwd, demod_fwd
 
 GFUSED = os.environ.get('HG_GFUSED', '1') != '0'
@@ -92,6 +92,15 @@ class _GeneratorTrain(torch.autograd.Function):
         per = 17
         blk = lambda i: sv[2 + per * i:2 + per * (i + 1)]
         grads = [None] * (PER_BLOCK * L)
+        # What autograd asks for, per argument (x0, nzt, then PER_BLOCK per block).  Training asks for every parameter and
+        # not for the noise; a projection (project.py) asks for the styles and the noise against frozen weights: then no
+        # weight-gradient convolution runs and no flat gradient slot is touched.
+        need = ctx.needs_input_grad
+        need_params = need[0] or any(need[2 + PER_BLOCK * i + k] for i in range(L) for k in range(3, PER_BLOCK))
+        # The noise image's gradient: one (B, S, S) buffer that the 2 L stages add their windows to (hg_noise_grad), each
+        # right behind the stage kernel that wrote its gconv, on the main stream: the read-modify-write of the buffer has
+        # to be ordered anyway, and 14 launches of microseconds are not worth a cross-stream event pair each.
+        gnz = torch.zeros_like(nzt) if need[1] else None
         from . import nets as _N
         if _N.PHASE_HOOK is not None:
             _N.PHASE_HOOK('gb_generator_node_entered', True)
@@ -106,7 +115,7 @@ class _GeneratorTrain(torch.autograd.Function):
         wterm = {}
 
         def demod(idx, gd, d, s1p, wsq, wp):
-            gy, wterm[idx] = demod_bwd(gd, d, s1p, wsq, wp)
+            gy, wterm[idx] = demod_bwd(gd, d, s1p, wsq, wp, True, need[2 + idx])
             return gy
         for i in range(L - 1, -1, -1):
             xm1, out1, xm2, out2, s1, s2, srgb, d1, d2, wn1, bn1, wn2, bn2, s1p, s2p, wsq1, wsq2 = blk(i)
@@ -116,7 +125,8 @@ class _GeneratorTrain(torch.autograd.Function):
             base = PER_BLOCK * i
             # ---- at out2: next block's first convolution (behind the bilinear x2) + this block's to-RGB -> conv2's upstream gradient
             # (the to-RGB weight gradient straight into its flat slot when that slot has no writer yet this step)
-            slot = C.grad_slot(wrgbp) if wrgbp.is_contiguous() else None
+            nd = need[2 + base:2 + base + PER_BLOCK]
+            slot = C.grad_slot(wrgbp) if nd[5] and wrgbp.is_contiguous() else None
             if slot is not None and slot[0].data_ptr() in slot[1].direct_written:
                 slot = None
             gconv2, gs_a, gs_rgb, gw_rgb, gd2, gwn2, gbn2 = gstage_bwd(out2, ga, sa, ga is not None, g_rgb, wrgb.reshape(Cr, -1),
@@ -124,24 +134,36 @@ class _GeneratorTrain(torch.autograd.Function):
                                                                        None if slot is None else slot[0].view(Cr, -1))
             if ga is not None:
                 pend.append((base + PER_BLOCK + 0, gs_a, gy_next))   # style of the next block's conv1: modulation + demodulation parts
+            if gnz is not None:
+                noise_grad(gconv2, d2, wn2, gnz, True)
             grads[base + 2] = gs_rgb
-            if slot is None:
-                grads[base + 5] = gw_rgb.reshape(wrgbp.shape)
-            else:
+            if slot is not None:
                 slot[1].direct_written.add(slot[0].data_ptr())
-            grads[base + 8], grads[base + 9] = gwn2.reshape(-1, 1), gbn2
+            elif nd[5]:
+                grads[base + 5] = gw_rgb.reshape(wrgbp.shape)
+            if nd[8]:
+                grads[base + 8] = gwn2.reshape(-1, 1)
+            if nd[9]:
+                grads[base + 9] = gbn2
             g_xm2 = C.conv_dgrad_packed(gconv2, C.pack_weights(w2, C.PACK_DGRAD), w2.shape[1], xm2.shape[2], xm2.shape[3], 3)
-            grads[base + 4] = _wgrad(w2p, xm2, gconv2)
+            if nd[4]:
+                grads[base + 4] = _wgrad(w2p, xm2, gconv2)
             gy2 = demod(base + 4, gd2, d2, s2p, wsq2, w2p)
             if i > 0:                                            # rgb_i = to_rgb(out2) + up2(rgb_{i-1})
                 g_rgb_prev, _ = modulate_bwd(g_rgb, torch.empty((g_rgb.shape[0], Cr, g_rgb.shape[2] // 2, g_rgb.shape[3] // 2),
                                                                  dtype=torch.float32, device=g_rgb.device), None, True)
             # ---- at out1: conv2 (same resolution) -> conv1's upstream gradient
             gconv1, gs2, _, _, gd1, gwn1, gbn1 = gstage_bwd(out1, g_xm2, s2, False, None, None, None, d1, nzt, wn1, bn1)
+            if gnz is not None:
+                noise_grad(gconv1, d1, wn1, gnz, True)
             pend.append((base + 1, gs2, gy2))
-            grads[base + 6], grads[base + 7] = gwn1.reshape(-1, 1), gbn1
+            if nd[6]:
+                grads[base + 6] = gwn1.reshape(-1, 1)
+            if nd[7]:
+                grads[base + 7] = gbn1
             ga = C.conv_dgrad_packed(gconv1, C.pack_weights(w1, C.PACK_DGRAD), w1.shape[1], xm1.shape[2], xm1.shape[3], 3)
-            grads[base + 3] = _wgrad(w1p, xm1, gconv1)
+            if nd[3]:
+                grads[base + 3] = _wgrad(w1p, xm1, gconv1)
             gy_next = demod(base + 3, gd1, d1, s1p, wsq1, w1p)
             sa = s1
             if i > 0:
@@ -149,7 +171,7 @@ class _GeneratorTrain(torch.autograd.Function):
         # block 0's first convolution reads the learned constant directly (no upsample)
         gx0e, gs1_0 = modulate_bwd(ga, x0e, sa, False)
         pend.append((0, gs1_0, gy_next))
-        g_x0 = gx0e.sum(0)
+        g_x0 = gx0e.sum(0) if need[0] else None
         torch._foreach_add_([a for _, a, _ in pend], [b for _, _, b in pend])
         for idx, a, _ in pend:
             grads[idx] = a
@@ -157,9 +179,9 @@ class _GeneratorTrain(torch.autograd.Function):
             grads[idx] = _add(grads[idx], gwd)
         if _N.PHASE_HOOK is not None:
             _N.PHASE_HOOK('gb_generator_blocks_done', True)
-        if AFTER_BLOCKS is not None:
+        if AFTER_BLOCKS is not None and need_params:
             AFTER_BLOCKS()
-        return (g_x0, None, *grads)
+        return (g_x0, gnz, *grads)
 
 
 def generator_infer(gen, styles_t, nzt):
@@ -240,7 +262,8 @@ def supported(gen, styles_t, nzt, train=True):
 
 def generator_train(gen, styles_t, nzt):
     """rgb = Generator(...) given the 3 L projected styles `styles_t` ([to_style1, to_style2, to_rgb.to_style] per block) and the
-    transposed noise image; differentiable (first order) w.r.t. the styles and every generator parameter."""
+    transposed noise image; differentiable (first order) w.r.t. the styles, the noise image and every generator parameter
+    (each gradient is computed only where autograd asks for it: frozen weights cost no weight-gradient launch)."""
     args = []
     for i, b in enumerate(gen.blocks):
         s1, s2, srgb = styles_t[3 * i], styles_t[3 * i + 1], styles_t[3 * i + 2]

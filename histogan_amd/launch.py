@@ -81,6 +81,16 @@ def dnl_bwd(g, out, conv, d, nzt, wn, bn):
     return gconv, gd, gw_p, gb_p
 
 
+def noise_grad(gconv, d, wn, gnzt, accumulate):
+    """hg_noise_grad: gnzt[b, i, j] (+)= sum_o (wn[o] / d[b, o]) gconv[b, o, i, j] on the H x H window of the (B, S, S) buffer
+    gnzt, in place (accumulate False: the window is overwritten); d None: no demodulation.  Returns gnzt."""
+    B, O, H, _ = gconv.shape
+    with on_device(gconv.device):
+        check(lib.hg_noise_grad(gconv.data_ptr(), ptr(d), wn.data_ptr(), gnzt.data_ptr(), B, O, H, gnzt.shape[-1],
+                                int(bool(accumulate)), stream_of(gconv)), 'hg_noise_grad')
+    return gnzt
+
+
 def torgb_fwd(x, s, w, prev):
     """conv1x1(x * (s + 1), w) [+ prev] as one stream over x; w (C, O) or (C, O, 1, 1), torgb_fits(C, O)."""
     B, O, H, W = x.shape

@@ -36,14 +36,23 @@ class Flatten(nn.Module):
 
 
 def _noise_t(inoise):
-    """(B,S,S,1) noise image -> (B,S,S) transposed copy, cached on the tensor for the G forward."""
-    nzt = getattr(inoise, '_hg_nzt', None)
-    if nzt is None:
-        nzt = inoise[..., 0].transpose(1, 2).contiguous()
-        try:
-            inoise._hg_nzt = nzt
-        except Exception:
-            pass
+    """(B,S,S,1) noise image -> (B,S,S) transposed copy.  A noise image that requires grad (projection: the optimiser's
+    variable) is transposed inside the autograd graph, which transposes its gradient back, and is not cached.  Any other
+    is cached on the tensor for the G forward, keyed on the tensor's version counter: an in-place update invalidates it."""
+    if inoise.requires_grad:
+        return inoise[..., 0].transpose(1, 2).contiguous()
+    try:
+        version = inoise._version
+    except Exception:                     # (inference tensors keep no version counter: nothing to key a cache on)
+        return inoise[..., 0].transpose(1, 2).contiguous()
+    ent = getattr(inoise, '_hg_nzt', None)
+    if ent is not None and ent[0] == version:
+        return ent[1]
+    nzt = inoise[..., 0].transpose(1, 2).contiguous()
+    try:
+        inoise._hg_nzt = (version, nzt)
+    except Exception:
+        pass
     return nzt
 
 
@@ -206,7 +215,6 @@ class Generator(nn.Module):
         batch_size = styles.shape[0]
         x = self.initial_block.expand(batch_size, -1, -1, -1)
         styles = torch.cat((styles.transpose(0, 1), hists.transpose(0, 1)), dim=0)
-        _noise_t(input_noise)
         rgb = None
         layers = [m for block in self.blocks for m in (block.to_style1, block.to_style2, block.to_rgb.to_style)]
         if (styles.dtype == torch.float32 and styles.shape[0] >= len(self.blocks)     # (fewer style rows than blocks: the zip below)

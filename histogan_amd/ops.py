@@ -59,17 +59,27 @@ class _DemodNoiseLrelu(torch.autograd.Function):
         d = None if d is None else f32c(d)
         nzt = f32c(nzt)
         _square(conv)
-        out = launch.dnl_fwd(conv, d, nzt, f32c(wn.detach().reshape(-1)), f32c(bn))
+        wn_ = f32c(wn.detach().reshape(-1))
+        out = launch.dnl_fwd(conv, d, nzt, wn_, f32c(bn))
         # The convolution output is kept for the backward (no recovery rounding); recovering conv*d from `out` there instead
         # was measured at C3 within noise: 45.86 against 45.99 ms per plain step.
-        ctx.save_for_backward(conv, d, nzt, out)
+        ctx.save_for_backward(conv, d, nzt, out, wn_)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        conv, d, nzt, out = ctx.saved_tensors
+        conv, d, nzt, out, wn_ = ctx.saved_tensors
         gconv, gd, gw_p, gb_p = launch.dnl_bwd(f32c(g), out, conv, d, nzt, None, None)
-        return gconv, gd, None, gw_p.sum(0).reshape(-1, 1), gb_p.sum(0)
+        return gconv, gd, _noise_grad(ctx, 2, gconv, d, wn_, nzt), gw_p.sum(0).reshape(-1, 1), gb_p.sum(0)
+
+
+def _noise_grad(ctx, arg, gconv, d, wn, nzt):
+    """The gradient of a stage with respect to its transposed noise image nzt (the Function's argument number `arg`) from the
+    stage's gconv -- one launch (hg_noise_grad), and only when autograd asks for it (projection: the noise image is
+    optimised; training draws a fresh one that needs no gradient: no launch, no allocation)."""
+    if not ctx.needs_input_grad[arg]:
+        return None
+    return launch.noise_grad(gconv, d, wn, torch.zeros_like(nzt), False)
 
 
 def demod_noise_lrelu(conv, d, nzt, wn, bn):
@@ -142,7 +152,7 @@ class _ConvDnl(torch.autograd.Function):
             gx = C.conv_dgrad_packed(gconv, C.pack_weights(f32c(w), C.PACK_DGRAD), K, xm.shape[2], xm.shape[3], k)
         if ctx.needs_input_grad[1] and not C._skip_wgrad and not C._direct_wgrad(w, xm, gconv, 1):
             gw = C.conv_wgrad(f32c(xm), gconv, k)
-        return gx, gw, gd, None, gw_p.sum(0).reshape(-1, 1), gb_p.sum(0)
+        return gx, gw, gd, _noise_grad(ctx, 3, gconv, d, wn_, nzt_), gw_p.sum(0).reshape(-1, 1), gb_p.sum(0)
 
 
 def conv_dnl(xm, w, d, nzt, wn, bn):
@@ -195,10 +205,11 @@ class _ModConvStage(torch.autograd.Function):
         if xin is None:
             xin = x
         Hi, Wi = xin.shape[2], xin.shape[3]
-        gwn = gbn = gd = None
+        gwn = gbn = gd = gnzt = None
         if act:
             gconv, gd, gw_p, gb_p = launch.dnl_bwd(g, out, None, d, nzt_, wn_, bn_)
             gwn, gbn = gw_p.sum(0).reshape(-1, 1), gb_p.sum(0)
+            gnzt = _noise_grad(ctx, 3, gconv, d, wn_, nzt_)
         else:
             if d is not None:
                 raise RuntimeError('modconv_stage: demodulation without activation is not implemented')
@@ -212,7 +223,7 @@ class _ModConvStage(torch.autograd.Function):
             gq = gd * (-0.5) * d * d * d
             gs = gs + 2.0 * s1 * torch.mm(gq, wsq)
             gw = gw + 2.0 * w * torch.mm(gq.t(), s1 * s1)[:, :, None, None]
-        return gx, gs, gw, None, gwn, gbn, None, None, None
+        return gx, gs, gw, gnzt, gwn, gbn, None, None, None
 
 
 def modconv_stage(x, style, weight, nzt=None, wn=None, bn=None, demod=True, upsample=False, act=True):

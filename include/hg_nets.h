@@ -88,6 +88,17 @@ int hg_demod_noise_lrelu_bwd(const float *gout, const float *out, const float *c
                              float *gwn_part, float *gbn_part, int32_t B, int32_t O, int32_t H, int32_t S,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* The gradient of a stage with respect to the (transposed) noise image, from the gconv that hg_demod_noise_lrelu_bwd /
+ * hg_gstage_bwd wrote (gconv = m d, m = gout lrelu'(out), so d out / d nzt = wn[o] m = (wn[o] / d[b,o]) gconv):
+ *   gnzt[b,i,j] (+)= sum_o (wn[o] / d[b,o]) gconv[b,o,i,j]        for i, j < H      (d NULL: the scale is wn[o])
+ * gconv (B,O,H,H); d (B,O) or NULL; wn (O); gnzt (B,S,S) in the nzt layout, S >= H.  accumulate = 0 overwrites the H x H
+ * window of every sample, accumulate != 0 adds to it; elements outside the window are never touched.  Any H <= S as
+ * hg_demod_noise_lrelu_fwd (16-byte loads where H % 4 == 0).  No workspace, no atomics: every output element has one
+ * owner thread that adds the channel partials in a fixed order, so two runs give the same bits; launches of successive
+ * stages on ONE stream serialise the read-modify-write of gnzt. */
+int hg_noise_grad(const float *gconv, const float *d, const float *wn, float *gnzt, int32_t B, int32_t O, int32_t H,
+                  int32_t S, int32_t accumulate, void *stream);
+
 /* out[c] = sum_{b,p} g[b,c,p]: the bias gradient of a convolution (nn.Conv2d bias, histoGAN/histoGAN.py:510-518). */
 int hg_channel_sum(const float *g, float *out, int32_t B, int32_t C, int32_t HW, void *workspace,
                    size_t workspace_bytes, void *stream);
