@@ -1,5 +1,6 @@
 """DiffAugment kernels (include/hg_augment.h) against the outputs of the reference's
-utils/diff_augment.py (recorded draws replayed), their adjoints, and the augmented train step."""
+utils/diff_augment.py (recorded draws replayed), their adjoints, and the augmented train step.
+Shapes beyond one workgroup, up to 256 x 256, against the fp64 oracle: tests/test_augment_shapes_gpu.py."""
 import os
 
 import numpy as np
