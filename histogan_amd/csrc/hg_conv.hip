@@ -113,13 +113,30 @@ struct MfmaTile<16> {
   static __device__ __forceinline__ int row(int r, int lk) { return 4 * lk + r; }
 };
 
+template <int V>
+struct IntC { static constexpr int value = V; };   // a compile-time int as a function argument
+
+// The packed-weight tap (row block of the data-gradient packing) with which parity class (pY, pX) of a stride-2 data gradient
+// reads gout at offset (oy, ox) from its pixel, -1: that class has no such tap.  Per class, the offsets in the order (1,1),
+// (1,0), (0,1), (0,0) are that class's taps in parity_taps order (checked at compile time next to parity_taps).
+constexpr int parity_row(int pY, int pX, int oy, int ox) {
+  const int dy = pY + 1 - 2 * oy, dx = pX + 1 - 2 * ox;
+  return (dy < 0 || dy > 2 || dx < 0 || dx > 2) ? -1 : 8 - (3 * dy + dx);
+}
+
 // FE (fused extras) = input scale / output scale / noise / LeakyReLU support; the plain instantiation (bias only)
 // keeps ~90 fewer registers and is what the training hot path runs.
-template <int WC, int WP, int TC, int TP, int TAPS, int KC, int IS, bool SM, int MT, bool FE>
+//
+// NC = classes per block.  1: one accumulator set, the taps of ConvArgs.  4: the stride-2 data gradient's four output-parity
+// classes from ONE staged tile -- the block's pixels live on the grid of the largest class (0, 0), the halo tile is the gout
+// tile with one extra row and column, the staged weights are all nine packed rows (TAPS == 9, in packed order), and each of
+// the four read offsets (oy, ox) of the tile feeds the accumulator sets of the classes it reaches (parity_row).
+template <int WC, int WP, int TC, int TP, int TAPS, int KC, int IS, bool SM, int MT, bool FE, int NC = 1>
 __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, const int bidy, const int bidz) {
   typedef MfmaTile<MT> M;
   constexpr int KS = M::KS;         // channels per MFMA
   static_assert(KC % KS == 0, "chunk must hold whole MFMA k-steps");
+  static_assert(NC == 1 || (NC == 4 && TAPS == 9 && IS == 1 && !FE), "all-class blocks: plain epilogue, nine packed rows");
   constexpr int NT = WC * WP * 64;
   constexpr int NB = WC * TC * MT;  // channels per block
   constexpr int MB = WP * TP * MT;  // pixels per block
@@ -200,13 +217,15 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, con
   }
   const int aoff = lk * NB + wc * TC * MT + lm;
 
-  typename M::acc_t acc[TC][TP];
+  typename M::acc_t acc[NC][TC][TP];
 #pragma unroll
-  for (int i = 0; i < TC; ++i)
+  for (int c = 0; c < NC; ++c)
 #pragma unroll
-    for (int j = 0; j < TP; ++j)
+    for (int i = 0; i < TC; ++i)
 #pragma unroll
-      for (int r = 0; r < M::NR; ++r) acc[i][j][r] = 0.f;
+      for (int j = 0; j < TP; ++j)
+#pragma unroll
+        for (int r = 0; r < M::NR; ++r) acc[c][i][j][r] = 0.f;
 
   float xr[NH];
   float xs[FE ? NH : 1];     // modulation scale of each staged element (only live when iscale is given)
@@ -273,44 +292,99 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, con
     if (c + 1 < nchunks) prefetch(c + 1);
     if (c < c_begin) continue;
 
-    // operand reads one MFMA step ahead (explicit two-slot pipeline): the ds_reads of step s+1 are issued before the
-    // MFMAs of step s, so a wave never waits a full LDS latency between two MFMA groups
-    constexpr int NS = TAPS * (KC / KS);
-    float av[2][TC], bv[2][TP];
-    auto ldop = [&](int s_, int slot) __attribute__((always_inline)) {
-      const int t = s_ / (KC / KS), kk = s_ % (KC / KS);
+    if constexpr (NC == 1) {
+      // operand reads one MFMA step ahead (explicit two-slot pipeline): the ds_reads of step s+1 are issued before the
+      // MFMAs of step s, so a wave never waits a full LDS latency between two MFMA groups
+      constexpr int NS = TAPS * (KC / KS);
+      float av[2][TC], bv[2][TP];
+      auto ldop = [&](int s_, int slot) __attribute__((always_inline)) {
+        const int t = s_ / (KC / KS), kk = s_ % (KC / KS);
 #pragma unroll
-      for (int i = 0; i < TC; ++i) av[slot][i] = Ws[(t * KC + kk * KS) * NB + aoff + i * MT];
-      if constexpr (TAPS == 9) {
-        // the 3x3 tap grid: the three taps of a kernel row are consecutive floats of the halo row -- one address per
-        // (pixel tile, kernel row, k step) with the column as the instruction's immediate offset (a third of the address
-        // registers of the general form below)
-        const int roff = a.toff[(t / 3) * 3];
+        for (int i = 0; i < TC; ++i) av[slot][i] = Ws[(t * KC + kk * KS) * NB + aoff + i * MT];
+        if constexpr (TAPS == 9) {
+          // the 3x3 tap grid: the three taps of a kernel row are consecutive floats of the halo row -- one address per
+          // (pixel tile, kernel row, k step) with the column as the instruction's immediate offset (a third of the address
+          // registers of the general form below)
+          const int roff = a.toff[(t / 3) * 3];
 #pragma unroll
-        for (int j = 0; j < TP; ++j) bv[slot][j] = (Xs + pixoff[j] + roff + kk * KS * g.CHS)[t % 3];
-      } else {
-        const int toff = a.toff[t];
+          for (int j = 0; j < TP; ++j) bv[slot][j] = (Xs + pixoff[j] + roff + kk * KS * g.CHS)[t % 3];
+        } else {
+          const int toff = a.toff[t];
+#pragma unroll
+          for (int j = 0; j < TP; ++j) bv[slot][j] = Xs[pixoff[j] + toff + kk * KS * g.CHS];
+        }
+      };
+      ldop(0, 0);
+      // pin the schedule: [operand reads of step s+1] [MFMAs of step s] (the compiler otherwise batches the pixel-operand
+      // reads of several steps and issues the weight reads just in time, behind an s_waitcnt lgkmcnt(0) per step)
+      constexpr int DSN = (MT == 32 ? (TC + 1) / 2 : TC) + TP;
+      __builtin_amdgcn_sched_group_barrier(0x100, DSN, 0);
+#pragma unroll
+      for (int s_ = 0; s_ < NS; ++s_) {
+        if (s_ + 1 < NS) ldop(s_ + 1, (s_ + 1) & 1);
+#pragma unroll
+        for (int i = 0; i < TC; ++i)
+#pragma unroll
+          for (int j = 0; j < TP; ++j) acc[0][i][j] = M::mma(av[s_ & 1][i], bv[s_ & 1][j], acc[0][i][j]);
+        if (s_ + 1 < NS) {
+          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);     // address of the next weight read
+          __builtin_amdgcn_sched_group_barrier(0x100, DSN, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, TC * TP, 0);
+      }
+    } else {
+      // all four classes: a step is (read offset o, k step) -- one pixel operand per pixel tile, one weight operand per class the
+      // offset reaches (1 / 2 / 2 / 4 of them), and that many MFMA groups.  Offsets outermost in the order (1,1), (1,0), (0,1),
+      // (0,0), k steps inside: every accumulator sees its class's taps in parity_taps order with the k steps innermost, i.e. the
+      // summation order of the per-class kernel.  Same two-slot operand pipeline as above.
+      constexpr int KSTEPS = KC / KS;
+      float av[2][4][TC], bv[2][TP];
+      auto ldop = [&](int s_, int slot) __attribute__((always_inline)) {
+        const int o = s_ / KSTEPS, kk = s_ % KSTEPS, oy = o < 2 ? 1 : 0, ox = (o & 1) ? 0 : 1;
+#pragma unroll
+        for (int cl = 0; cl < 4; ++cl) {
+          const int w = parity_row(cl >> 1, cl & 1, oy, ox);
+          if (w >= 0) {
+#pragma unroll
+            for (int i = 0; i < TC; ++i) av[slot][cl][i] = Ws[(w * KC + kk * KS) * NB + aoff + i * MT];
+          }
+        }
+        const int toff = oy * g.TWp + ox;
 #pragma unroll
         for (int j = 0; j < TP; ++j) bv[slot][j] = Xs[pixoff[j] + toff + kk * KS * g.CHS];
-      }
-    };
-    ldop(0, 0);
-    // pin the schedule: [operand reads of step s+1] [MFMAs of step s] (the compiler otherwise batches the pixel-operand
-    // reads of several steps and issues the weight reads just in time, behind an s_waitcnt lgkmcnt(0) per step)
-    constexpr int DSN = (MT == 32 ? (TC + 1) / 2 : TC) + TP;
-    __builtin_amdgcn_sched_group_barrier(0x100, DSN, 0);
+      };
+      // one step: [operand reads of the next step (of offset O1, 4 = there is none)] [MFMAs of this one (offset O)]
+      auto step = [&](auto O_, auto O1_, int kk) __attribute__((always_inline)) {
+        constexpr int o = decltype(O_)::value, o1 = decltype(O1_)::value, oy = o < 2 ? 1 : 0, ox = (o & 1) ? 0 : 1;
+        constexpr int ncl = (2 - oy) * (2 - ox), ncl1 = (o1 < 2 ? 1 : 2) * ((o1 & 1) ? 2 : 1);   // classes an offset reaches
+        const int s_ = o * KSTEPS + kk;
+        if constexpr (o1 < 4) ldop(s_ + 1, (s_ + 1) & 1);
 #pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_) {
-      if (s_ + 1 < NS) ldop(s_ + 1, (s_ + 1) & 1);
+        for (int cl = 0; cl < 4; ++cl) {
+          if (parity_row(cl >> 1, cl & 1, oy, ox) >= 0) {
 #pragma unroll
-      for (int i = 0; i < TC; ++i)
+            for (int i = 0; i < TC; ++i)
 #pragma unroll
-        for (int j = 0; j < TP; ++j) acc[i][j] = M::mma(av[s_ & 1][i], bv[s_ & 1][j], acc[i][j]);
-      if (s_ + 1 < NS) {
-        __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);     // address of the next weight read
-        __builtin_amdgcn_sched_group_barrier(0x100, DSN, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, TC * TP, 0);
+              for (int j = 0; j < TP; ++j) acc[cl][i][j] = M::mma(av[s_ & 1][cl][i], bv[s_ & 1][j], acc[cl][i][j]);
+          }
+        }
+        if constexpr (o1 < 4) {
+          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, ncl1 * TC + TP, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, ncl * TC * TP, 0);
+      };
+      auto steps = [&](auto O_, auto ONext_) __attribute__((always_inline)) {
+#pragma unroll
+        for (int kk = 0; kk + 1 < KSTEPS; ++kk) step(O_, O_, kk);
+        step(O_, ONext_, KSTEPS - 1);
+      };
+      ldop(0, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, TC + TP, 0);
+      steps(IntC<0>{}, IntC<1>{});
+      steps(IntC<1>{}, IntC<2>{});
+      steps(IntC<2>{}, IntC<3>{});
+      steps(IntC<3>{}, IntC<4>{});
     }
   }
 
@@ -319,7 +393,52 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, con
   const int HWo = a.Ho * a.Wo;
   // fin: the finished sums (bias / scales / noise / activation applied, written to `out`); else raw partial sums to slab[z]
   auto epilogue = [&](const bool fin) __attribute__((always_inline)) {
-  if constexpr (!FE) {
+  if constexpr (NC == 4) {
+    // a lane that owns class pixel (cy, cx) owns the outputs (2 cy + {0, 1}, 2 cx + {0, 1}) = classes {0, 1} / {2, 3}: the two
+    // x parities of a row leave as one 8-byte store (a wave writes whole lines) where every such address is 8-byte aligned,
+    // i.e. an even Wo on an aligned base; the last row / column of an odd Ho / Wo belongs to class (0, .) / (., 0) only
+    float *const obase = fin ? a.out : a.slab + (size_t)bidz * a.B * N * HWo;
+    const bool pair = (a.Wo & 1) == 0 && ((size_t)obase & 7) == 0;
+#pragma unroll
+    for (int j = 0; j < TP; ++j) {
+      const int p = (wp * TP + j) * MT + lm;
+      const int px = p & TWm, py = (p >> g.lTW) & THm, pi = p >> (g.lTW + g.lTH);
+      const int cx = x0 + px, cy = y0 + py, b = b0 + pi;
+      if (b >= a.B || cy >= a.Hc || cx >= a.Wc) continue;
+      const bool row1 = 2 * cy + 1 < a.Ho, col1 = 2 * cx + 1 < a.Wo;
+      const size_t pofs = ((size_t)b * N) * HWo + (size_t)(2 * cy) * a.Wo + 2 * cx;
+#pragma unroll
+      for (int i = 0; i < TC; ++i) {
+#pragma unroll
+        for (int r = 0; r < M::NR; ++r) {
+          const int ch = n0 + (wc * TC + i) * MT + M::row(r, lk);
+          if (ch < N) {
+            const size_t o = pofs + (size_t)ch * HWo;
+            float v[4] = {acc[0][i][j][r], acc[1][i][j][r], acc[2][i][j][r], acc[3][i][j][r]};
+            if (fin && a.bias) {
+              const float bs = a.bias[ch];
+              v[0] += bs; v[1] += bs; v[2] += bs; v[3] += bs;
+            }
+            if (fin && a.addend) {
+              v[0] += a.addend[o];
+              if (col1) v[1] += a.addend[o + 1];
+              if (row1) v[2] += a.addend[o + a.Wo];
+              if (row1 && col1) v[3] += a.addend[o + a.Wo + 1];
+            }
+            if (pair) {
+              *reinterpret_cast<f32x2 *>(obase + o) = f32x2{v[0], v[1]};
+              if (row1) *reinterpret_cast<f32x2 *>(obase + o + a.Wo) = f32x2{v[2], v[3]};
+            } else {
+              obase[o] = v[0];
+              if (col1) obase[o + 1] = v[1];
+              if (row1) obase[o + a.Wo] = v[2];
+              if (row1 && col1) obase[o + a.Wo + 1] = v[3];
+            }
+          }
+        }
+      }
+    }
+  } else if constexpr (!FE) {
 #pragma unroll
     for (int j = 0; j < TP; ++j) {
       const int p = (wp * TP + j) * MT + lm;
@@ -334,7 +453,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, con
         for (int r = 0; r < M::NR; ++r) {
           const int ch = n0 + (wc * TC + i) * MT + M::row(r, lk);
           if (ch < N) {
-            float v = acc[i][j][r];
+            float v = acc[0][i][j][r];
             if (fin && a.bias) v += a.bias[ch];
             if (fin && a.addend) v += a.addend[pofs + (size_t)ch * HWo];
             ob[(size_t)ch * HWo] = v;
@@ -378,7 +497,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bidx, con
         for (int r = 0; r < M::NR; ++r) {
           const int ch = n0 + (wc * TC + i) * MT + M::row(r, lk);
           if (ch < N) {
-            float v = fmaf(acc[i][j][r], posc[r], fmaf(pnw[r], nz, pbias[r]));
+            float v = fmaf(acc[0][i][j][r], posc[r], fmaf(pnw[r], nz, pbias[r]));
             if (fin && a.slope > 0.f) v = v > 0.f ? v : a.slope * v;
             ob[(size_t)ch * HWo] = v;
           }
@@ -421,6 +540,14 @@ __global__ __launch_bounds__(WC *WP * 64, kConvMinWaves) void k_conv_parity4(con
   else if (cls == 1) conv_body<WC, WP, TC, TP, 2, KC, 1, SM, MT, FE>(a.c[1], t, blockIdx.y, blockIdx.z);
   else if (cls == 2) conv_body<WC, WP, TC, TP, 2, KC, 1, SM, MT, FE>(a.c[2], t, blockIdx.y, blockIdx.z);
   else conv_body<WC, WP, TC, TP, 4, KC, 1, SM, MT, FE>(a.c[3], t, blockIdx.y, blockIdx.z);
+}
+
+// The same four classes from ONE staged tile per block (conv_body, NC = 4): block t is pixel tile t of the largest class and
+// computes the 2 x 2 outputs of each of its pixels.  gout is fetched once instead of four times, a staging pass feeds nine
+// taps' MFMAs instead of 1 / 2 / 2 / 4, and the stores are whole lines (no block order needed to pair them in an L2).
+template <int WC, int WP, int TC, int TP, int KC, bool SM, int MT>
+__global__ __launch_bounds__(WC *WP * 64, kConvMinWaves) void k_conv_allclass(const ConvArgs a) {
+  conv_body<WC, WP, TC, TP, 9, KC, 1, SM, MT, false, 4>(a, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // out[b][n][p] = epilogue( sum_z slab[z][b][n][p] )   (fixed order: deterministic); epilogue as in k_conv
@@ -973,8 +1100,8 @@ inline Taps square_taps(int ksize) {
 // the (1 + pY) x (1 + pX) taps that reach parity class (pY, pX) of a stride-2 data gradient:
 //   gin[2y+pY, 2x+pX] = sum over the taps (dy,dx) with dy == pY+1, dx == pX+1 (mod 2) of
 //                       gout[y + (pY+1-dy)/2, x + (pX+1-dx)/2] * W[.,.,dy,dx];  the dgrad packing stores W[dy,dx] at tap 8-(3dy+dx)
-inline Taps parity_taps(int pY, int pX) {
-  Taps t;
+constexpr Taps parity_taps(int pY, int pX) {
+  Taps t{};
   int n = 0;
   t.ntx = 1 + pX;
   for (int dy = 0; dy < 3; ++dy)
@@ -985,6 +1112,23 @@ inline Taps parity_taps(int pY, int pX) {
       }
   return t;
 }
+
+// parity_row (the all-class blocks' compile-time tap table) lists every class's taps as parity_taps does, in its order
+constexpr bool parity_row_is_parity_taps() {
+  for (int c = 0; c < 4; ++c) {
+    const Taps t = parity_taps(c / 2, c % 2);
+    int n = 0;
+    for (int o = 0; o < 4; ++o) {
+      const int oy = o < 2 ? 1 : 0, ox = (o & 1) ? 0 : 1, w = parity_row(c / 2, c % 2, oy, ox);
+      if (w < 0) continue;
+      if (t.dy[n] != oy || t.dx[n] != ox || t.w[n] != w) return false;
+      ++n;
+    }
+    if (n != (1 + c / 2) * (1 + c % 2)) return false;
+  }
+  return true;
+}
+static_assert(parity_row_is_parity_taps(), "tap table of the all-class stride-2 data gradient");
 
 // The tile shapes of k_conv: waves along channels / pixels (WC, WP), MFMA tiles per wave (TC, TP), the MFMA tile (MT) and the
 // small-map halo bound (SM).  A block computes NB channels x MB pixels.  The values of ConvTile are part of the C ABI
@@ -1168,6 +1312,11 @@ ConvRoute route_single(int B, int K, int N, int Hc, int Wc, int taps, int IS, in
   return r;
 }
 
+// CONV_PARITY4 launches whose blocks compute all four classes from one staged tile (k_conv_allclass): the tiles with room for
+// four accumulator sets (the 64x256 and 128x128 tiles would need 256 accumulator registers), without the fused extras.  The
+// others keep one class per block (k_conv_parity4).
+constexpr bool allclass_serves(ConvTile t, bool fe) { return !fe && (t == TILE_16x256 || t == TILE_32x256 || t == TILE_64x64); }
+
 // have_ws / ws_bytes: the caller's workspace (the workspace queries plan with "present, unlimited"); fe: the launch carries
 // fused extras (input / output scale, noise, LeakyReLU).  Hi x Wi: the convolution's input.
 ConvRoute make_conv_route(bool dgrad, int B, int K, int N, int Hi, int Wi, int ksize, int stride, bool have_ws, size_t ws_bytes,
@@ -1196,7 +1345,9 @@ ConvRoute make_conv_route(bool dgrad, int B, int K, int N, int Hi, int Wi, int k
     }
   }
   if (r.kind == CONV_PARITY4) {
-    for (int c = 0; c < 4; ++c) r.blocks += plan_blocks(r.tile, B, N, (Hi - c / 2 + 1) / 2, (Wi - c % 2 + 1) / 2) * r.ksplit;
+    // all-class blocks: the tiles of the largest class; per-class blocks: of the four
+    for (int c = 0; c < (allclass_serves(r.tile, fe) ? 1 : 4); ++c)
+      r.blocks += plan_blocks(r.tile, B, N, (Hi - c / 2 + 1) / 2, (Wi - c % 2 + 1) / 2) * r.ksplit;
   } else {
     // (a 1-pixel-wide image has empty parity classes, whose slab pixels would never be written: no split, no one-launch form)
     r.kind = CONV_PER_CLASS;
@@ -1332,6 +1483,24 @@ int launch_conv_parity4(const ConvArgs (&base)[4], const Taps (&tp)[4], int kspl
   const unsigned gx = xcd_map ? (unsigned)((tiles_max + 7) / 8 * 32) : (unsigned)(4 * tiles_max);
   return launch_fitted(kern, fit[fe], dim3(gx, (unsigned)ny, (unsigned)ksplit), T.WC * T.WP * 64, tiles_sum * ny * ksplit, lds,
                        "k_conv_parity4", st, a4);
+}
+
+// ... as one launch of all-class blocks; `a` is the launch of class (0, 0): compute grid = the largest class, os = 2
+template <ConvTile TILE>
+int launch_conv_allclass(ConvArgs a, int ksplit, hipStream_t st) {
+  constexpr TileShape T = kTiles[TILE];
+  constexpr int KC = tile_kc(TILE, 1);
+  // halo: the gout tile and one more row and column (read offsets 0 / 1); weights: the nine packed taps in packed order
+  a.g = make_geom(T.MB(), a.B, a.Hc, a.Wc, 1, 0, 1, 0, 1, T.SM ? 2 : 4);
+  for (int t = 0; t < 9; ++t) a.toff[t] = 0;
+  a.ntx = 9; a.wrow0 = 0; a.wrow_dx = a.Kp; a.wrow_dy = 0;
+  a.ksplit = ksplit;
+  if ((long long)(1 << a.g.lNI) * a.K * a.Hi * a.Wi >= (1LL << 30)) return HG_EUNSUPPORTED;   // (as prep_conv)
+  const size_t lds = ((size_t)9 * KC * T.NB() + (size_t)KC * a.g.CHS + 64 + 8 + 256) * sizeof(float);
+  static KernelFit fit = {};
+  const dim3 grid((unsigned)(a.g.tiles_x * a.g.tiles_y * a.g.groups), (unsigned)((a.N + T.NB() - 1) / T.NB()), (unsigned)ksplit);
+  return launch_fitted(k_conv_allclass<T.WC, T.WP, T.TC, T.TP, KC, T.SM, T.MT>, fit, grid, T.WC * T.WP * 64,
+                       (long long)grid.x * grid.y * grid.z, lds, "k_conv_allclass", st, a);
 }
 
 // the K-split slabs of a route (behind a.slab, `out` layout) summed in fixed order, with the epilogue
@@ -1620,9 +1789,16 @@ int hg_conv2d_dgrad(const float *gout, const float *wt, float *gin, const float 
     tps[c] = parity_taps(pY, pX);
   }
   if (r.kind == CONV_PARITY4) {
+    const bool fe = has_extras(a);
     const int rc = dispatch([&](auto TILE) {
-      if constexpr (TILE == TILE_128x128_SM) return (int)HG_EUNSUPPORTED;   // (never planned for a parity class)
-      else return launch_conv_parity4<(ConvTile)decltype(TILE)::value>(ca, tps, r.ksplit, st);
+      constexpr ConvTile T = (ConvTile)decltype(TILE)::value;
+      if constexpr (T == TILE_128x128_SM) return (int)HG_EUNSUPPORTED;   // (never planned for a parity class)
+      else {
+        if constexpr (allclass_serves(T, false)) {
+          if (allclass_serves(T, fe)) return launch_conv_allclass<T>(ca[0], r.ksplit, st);
+        }
+        return launch_conv_parity4<T>(ca, tps, r.ksplit, st);
+      }
     }, among<TILE_16x256, TILE_32x256, TILE_64x256, TILE_128x128, TILE_128x128_SM, TILE_64x64>(r.tile));
     if (rc) return rc;
     return r.reduce ? launch_splitk_reduce(a, r.ksplit, st) : HG_OK;

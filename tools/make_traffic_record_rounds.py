@@ -12,7 +12,10 @@ is tallied as 64 B, whatever the lane width (the guide states the factor for 16 
 "as reported", which under-stated the direct kernels' reads by half).  WRITE_SIZE as reported (k_wino's 67 108 864-byte output reads
 65 536.0 KB).  Infinity-Cache hits are counted: this is fabric traffic, an upper bound on HBM traffic.
 
-    python tools/make_traffic_record_rounds.py <wino txt> <conv txt> <thr txt> <commit> [round]"""
+  * tools/s2_dgrad_traffic.sh <out>/traffic.txt              (optional, 6th argument) the stride-2 data gradient of D0.down at batch 64
+A text given as `-` keeps the entries it would fill as the record has them (they stay valid or stale by their own digest).
+
+    python tools/make_traffic_record_rounds.py <wino txt> <conv txt> <thr txt> <commit> [round [s2 dgrad txt]]"""
 import hashlib
 import json
 import os
@@ -58,28 +61,36 @@ def entry(d, sub, src, commit):
                 source=src, source_sha16=digest(src), commit=commit)
 
 
-wino, conv, thr, commit = parse(sys.argv[1]), parse(sys.argv[2]), parse(sys.argv[3]), sys.argv[4]
-bench = {
-    'k_wino_fwd_256_128_64_b32': entry(wino, 'k_wino<2, 2, 8, false>', 'hg_wino.hip', commit),
-    'k_wino_wgrad_256_128_64_b32': entry(wino, 'k_wino_wgrad(', 'hg_wino.hip', commit),
-    'k_conv_fwd_256_128_64_b32': entry(conv, 'k_conv<', 'hg_conv.hip', commit),
-    'k_wgrad_256_128_64_b32': entry(conv, 'k_wgrad<', 'hg_conv.hip', commit),
-    'k_hist_bwd_c2': entry(conv, 'k_hist_bwd<', 'hg_hist.hip', commit),
-    'k_hist_fwd_c2': entry(conv, 'k_hist_fwd<', 'hg_hist.hip', commit),
-}
-t, fetch, write = {}, 0.0, 0.0
-for name in ('k_thr_fwd_lean', 'k_hist_finish', 'k_thr_bwd_lean'):
-    e = entry(thr, name, 'hg_hist.hip', commit)
-    t[name] = {k: e[k] for k in ('fetch_kb_reported', 'fetch_bytes', 'write_bytes', 'duration_us_under_pmc')}
-    fetch += e['fetch_bytes']
-    write += e['write_bytes']
-t['total_fabric_bytes_fwd_bwd'] = fetch + write
-t['algorithmic_bytes_fwd_bwd'] = 78643200
-bench['thr_fwd_bwd_c2'] = dict(fetch_bytes=fetch, write_bytes=write, comment='k_thr_fwd_lean + k_hist_finish + k_thr_bwd_lean; FETCH_SIZE x 2',
-                               source='hg_hist.hip', source_sha16=digest('hg_hist.hip'), commit=commit)
-rec = dict(_note=' '.join(__doc__.split('Correction: ')[1].split('\n\n')[0].split()), thresholding_b32_256x256_h64=t, bench=bench)
+commit = sys.argv[4]
 rnd = sys.argv[5] if len(sys.argv) > 5 else '06'
-with open(os.path.join(ROOT, 'profiles', f'r{rnd}_pmc_traffic.json'), 'w') as f:
+path = os.path.join(ROOT, 'profiles', f'r{rnd}_pmc_traffic.json')
+old = json.load(open(path)) if '-' in sys.argv[1:4] else {}
+wino, conv, thr = (parse(p) if p != '-' else None for p in sys.argv[1:4])
+bench = dict(old.get('bench', {}))
+if wino:
+    bench['k_wino_fwd_256_128_64_b32'] = entry(wino, 'k_wino<2, 2, 8, false>', 'hg_wino.hip', commit)
+    bench['k_wino_wgrad_256_128_64_b32'] = entry(wino, 'k_wino_wgrad(', 'hg_wino.hip', commit)
+if conv:
+    bench['k_conv_fwd_256_128_64_b32'] = entry(conv, 'k_conv<', 'hg_conv.hip', commit)
+    bench['k_wgrad_256_128_64_b32'] = entry(conv, 'k_wgrad<', 'hg_conv.hip', commit)
+    bench['k_hist_bwd_c2'] = entry(conv, 'k_hist_bwd<', 'hg_hist.hip', commit)
+    bench['k_hist_fwd_c2'] = entry(conv, 'k_hist_fwd<', 'hg_hist.hip', commit)
+if len(sys.argv) > 6:
+    bench['k_conv_allclass_dgrad_s2_16_16_256_b64'] = entry(parse(sys.argv[6]), 'k_conv_allclass<', 'hg_conv.hip', commit)
+t = old.get('thresholding_b32_256x256_h64', {})
+if thr:
+    t, fetch, write = {}, 0.0, 0.0
+    for name in ('k_thr_fwd_lean', 'k_hist_finish', 'k_thr_bwd_lean'):
+        e = entry(thr, name, 'hg_hist.hip', commit)
+        t[name] = {k: e[k] for k in ('fetch_kb_reported', 'fetch_bytes', 'write_bytes', 'duration_us_under_pmc')}
+        fetch += e['fetch_bytes']
+        write += e['write_bytes']
+    t['total_fabric_bytes_fwd_bwd'] = fetch + write
+    t['algorithmic_bytes_fwd_bwd'] = 78643200
+    bench['thr_fwd_bwd_c2'] = dict(fetch_bytes=fetch, write_bytes=write, comment='k_thr_fwd_lean + k_hist_finish + k_thr_bwd_lean; FETCH_SIZE x 2',
+                                   source='hg_hist.hip', source_sha16=digest('hg_hist.hip'), commit=commit)
+rec = dict(_note=' '.join(__doc__.split('Correction: ')[1].split('\n\n')[0].split()), thresholding_b32_256x256_h64=t, bench=bench)
+with open(path, 'w') as f:
     json.dump(rec, f, indent=1)
 for k, v in bench.items():
     print(f'{k:30s} fetch {v["fetch_bytes"] / 1e6:8.1f} MB  write {v["write_bytes"] / 1e6:7.1f} MB')
