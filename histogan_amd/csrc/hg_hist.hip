@@ -220,6 +220,21 @@ __device__ __forceinline__ void project(const DevParams &P, float r, float g, fl
   iy = P.intensity ? __fsqrt_rn(__fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(r, r), __fmul_rn(g, g)), __fmul_rn(b, b)), kEps)) : 1.f;
 }
 
+// (u, v) of plane p: (a, b), (-a, c), (-b, -c)  (RGBuvHistBlock.py:112-115,150-153,190-193); the one-plane cases bin plane 1
+__device__ __forceinline__ void plane_uv(int p, float a, float bb, float c, float &u, float &v) {
+  u = p == 0 ? a : (p == 1 ? -a : -bb);
+  v = p == 0 ? bb : (p == 1 ? c : -c);
+}
+
+// bins per unit of u; 0 when all bins coincide (h == 1 or lo == hi)
+__device__ __forceinline__ double inv_step(const DevParams &P) { return P.step > 0.0 ? 1.0 / P.step : 0.0; }
+
+// grad_x of histogram pixel n beyond the three colour channels: zeros (with a resize the adjoint kernel writes grad_x)
+__device__ __forceinline__ void zero_extra_channels(const DevParams &P, int b, int n, float *gdst) {
+  if (P.mode == HG_RESIZE_NONE)
+    for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
+}
+
 // Per-pixel state of the backward kernels: from the forward's cache (two 16-byte loads) or recomputed (up to 12 taps of
 // the bilinear resize + three fp64 logarithms: ~370 VALU instructions per pixel that the MFMA-bound kernels pay for in
 // matrix-pipe time -- fp32 MFMA and VALU instructions do not overlap on gfx950, tools/ubench/mfma_valu_overlap.hip).
@@ -1228,6 +1243,17 @@ __global__ __launch_bounds__(256, 2) void k_hist_bwd_planes(const DevParams P, c
   }
 }
 
+// sum over a 1024-thread workgroup, in every thread: wave sums, 16 partials through LDS, added in index order (deterministic)
+__device__ __forceinline__ float block_sum_1024(float d, float *sm16) {
+  d = hg_wave_sum(d);
+  if ((threadIdx.x & 63) == 0) sm16[threadIdx.x >> 6] = d;
+  __syncthreads();
+  d = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) d += sm16[w];
+  return d;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Generic backward (any h, any hist_boundary): the reference's plane structure taken literally,
 // one pixel per lane, fp64 kernel evaluation, fp32 mat-vecs against Ghat held in global/L2 (every
@@ -1240,12 +1266,7 @@ __global__ __launch_bounds__(1024) void k_hist_ghat(const float *__restrict__ go
   const float *g = gout + (long long)b * n, *o = hist + (long long)b * n;
   float d = 0.f;
   for (int e = threadIdx.x; e < n; e += 1024) d = fmaf(g[e], o[e], d);
-  d = hg_wave_sum(d);
-  if ((threadIdx.x & 63) == 0) sm16[threadIdx.x >> 6] = d;
-  __syncthreads();
-  d = 0.f;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) d += sm16[w];      // fixed order: deterministic
+  d = block_sum_1024(d, sm16);
   const float inv = 1.f / sums[b];
   for (int e = threadIdx.x; e < n; e += 1024) gh[(long long)b * n + e] = (g[e] - d) * inv;
 }
@@ -1267,6 +1288,25 @@ __device__ __forceinline__ void kern_eval_d(const DevParams &P, float u, int i, 
   }
 }
 
+// Tail of the gather backwards with slopes (k_hist_bwd_generic, k_hist_rbf_bwd), one pixel per thread: from the planes'
+// slopes gu[p] = dL/du_p, gv[p] = dL/dv_p and isum = dL/d(w_n Iy), all before the pixel's histogram weight, to grad_x
+// (channels >= 3 zeroed) and, WG, the weight map's gradient.
+template <bool WG, bool LAB>
+__device__ __forceinline__ void gather_epilogue(const DevParams &P, const float *xb, int b, int n, float r, float g,
+                                                float bl, float iy, float wn, const float gu[3], const float gv[3],
+                                                float isum, float *gdst) {
+  // u0 = a, v0 = b, u1 = -a, v1 = c, u2 = -b, v2 = -c
+  const float wiy = __fmul_rn(wn, iy);             // weight map x Iy: what the pixel entered the histogram with
+  const float da = wiy * (gu[0] - gu[1]), db = wiy * (gv[0] - gu[2]), dc = wiy * (gv[1] - gv[2]);
+  const float dIy = P.intensity ? __fmul_rn(isum, wn) : 0.f;   // dL/dIy = w_n dL/d(w_n Iy)
+  if (LAB || P.proj != HG_PROJ_RGBUV)   // one plane, binned as (u, v) = (-a, c): gu[1] = dL/du, gv[1] = dL/dv (before the weight)
+    store_pixel_grad_proj<LAB>(P, xb, b, n, r, g, bl, iy, wiy * gu[1], wiy * gv[1], dIy, gdst);
+  else
+    store_pixel_grad(P, xb, b, n, r, g, bl, iy, da, db, dc, dIy, gdst);
+  zero_extra_channels(P, b, n, gdst);
+  if constexpr (WG) store_weight_grad(P, b, n, __fmul_rn(isum, iy));
+}
+
 template <int METHOD, bool WG = false, bool LAB = false>
 __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, const float *__restrict__ x,
                                                          const float *__restrict__ gh, float *__restrict__ gdst) {
@@ -1280,13 +1320,12 @@ __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, cons
   if (valid) { sample_rgb(P, xb, n, r_, g_, b_); wn = sample_weight(P, b, n); }
   float a, bb, c, iy;
   project<LAB>(P, r_, g_, b_, a, bb, c, iy);
-  // plane p: (u, v) = (su*U, sv*V) with U,V in {a,b,c}  (RGBuvHistBlock.py:112-115,150-153,190-193)
-  const float uvals[3] = {a, -a, -bb}, vvals[3] = {bb, c, -c};
   float gu[3] = {0.f, 0.f, 0.f}, gv[3] = {0.f, 0.f, 0.f}, isum = 0.f;
   for (int p = 0; p < 3; ++p) {
     if (P.green && p != 1) continue;
     const float *G = gh + ((long long)b * P.P + (P.green ? 0 : p)) * h * h;
-    const float u = uvals[p], v = vvals[p];
+    float u, v;
+    plane_uv(p, a, bb, c, u, v);
     // pass 1: T_i = sum_j G[i][j] kv_j ;  g_u += k'u_i T_i ;  dIy += ku_i T_i
     for (int j = 0; j < h; ++j) { float k, dk; kern_eval_d<METHOD>(P, v, j, k, dk); kbuf[j * 64 + lane] = k; }
     for (int i = 0; i < h; ++i) {
@@ -1306,19 +1345,7 @@ __global__ __launch_bounds__(64) void k_hist_bwd_generic(const DevParams P, cons
       gv[p] = fmaf(dk, Sx, gv[p]);
     }
   }
-  // u0 = a, v0 = b, u1 = -a, v1 = c, u2 = -b, v2 = -c
-  const float wiy = __fmul_rn(wn, iy);             // weight map x Iy: what the pixel entered the histogram with
-  const float da = wiy * (gu[0] - gu[1]), db = wiy * (gv[0] - gu[2]), dc = wiy * (gv[1] - gv[2]);
-  const float dIy = P.intensity ? __fmul_rn(isum, wn) : 0.f;
-  if (valid) {
-    if (LAB || P.proj != HG_PROJ_RGBUV)   // one plane, binned as (u, v) = (-a, c): gu[1] = dL/du, gv[1] = dL/dv (before the weight)
-      store_pixel_grad_proj<LAB>(P, xb, b, n, r_, g_, b_, iy, wiy * gu[1], wiy * gv[1], dIy, gdst);
-    else
-      store_pixel_grad(P, xb, b, n, r_, g_, b_, iy, da, db, dc, dIy, gdst);
-    if (P.mode == HG_RESIZE_NONE)
-      for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
-    if constexpr (WG) store_weight_grad(P, b, n, __fmul_rn(isum, iy));
-  }
+  if (valid) gather_epilogue<WG, LAB>(P, xb, b, n, r_, g_, b_, iy, wn, gu, gv, isum, gdst);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1347,6 +1374,11 @@ __device__ __forceinline__ bool thr_hit(const DevParams &P, float u, int i) {
 
 // single: the windows are narrower than the bin spacing (every symmetric boundary: eps = (hi-lo)/h < (hi-lo)/(h-1)), so
 // only the NEAREST bin can contain u -- and near a midpoint, where rounding could pick the other neighbour, neither does.
+// thr_windows_single is the one statement of that condition: the host's route and both thresholding kernels ask it.
+__host__ __device__ inline bool thr_windows_single(int h, double step, double half_eps) {
+  return h > 1 && step > 2.0 * half_eps * (1.0 + 1e-9);
+}
+
 __device__ __forceinline__ int thr_single(const DevParams &P, float u, double inv_step) {
   const double t = ((double)u - P.lo) * inv_step;
   if (!(t > -1.0 && t < (double)P.h)) return -1;
@@ -1384,6 +1416,16 @@ __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v
   for (int w = 0; w < NT / 64; ++w) t += sm[w];
   __syncthreads();
   return t;
+}
+
+// a workgroup's fixed-point grid of n bins as floats to dst; tot += this thread's share of the exact integer total
+template <int NT>
+__device__ __forceinline__ void flush_grid(const unsigned long long *bins, int n, float *dst, unsigned long long &tot) {
+  for (int e = threadIdx.x; e < n; e += NT) {
+    const unsigned long long v = bins[e];
+    tot += v;
+    dst[e] = (float)((double)v * (1.0 / kThrScale));
+  }
 }
 
 // Slab sum + normalisation (stage 4, RGBuvHistBlock.py:224-228: hist / (sum + 1e-6)) in ONE launch.  The producing
@@ -1455,7 +1497,7 @@ struct ThrFast {
 
 __device__ __forceinline__ ThrFast make_thr_fast(const DevParams &P) {
   ThrFast F;
-  const double is = P.step > 0.0 ? 1.0 / P.step : 0.0;
+  const double is = inv_step(P);
   F.inv_step = (float)is;
   F.c0 = (float)(-P.lo * is);
   F.thr_t = (float)(P.half_eps * is);
@@ -1539,66 +1581,58 @@ __global__ __launch_bounds__(256) void k_selftest_fastlog(uint32_t first, uint32
   atomicMax(&out[1], __float_as_uint(mabs));
 }
 
+// Scatter forward (k_hist_thr_fwd, k_hist_rbf_fwd): one workgroup bins the pixels [s * per_block, (s + 1) * per_block) of image b
+// into 64-bit fixed-point LDS grids, flushes them as a float slab and leaves the slab's exact total in slab_tot.
+// scatter(grid, u, v, iy) adds one pixel (weight iy, the weight map included) to one plane's grid: all a kernel adds.
 // ALL3: the grids of all planes are in LDS at once (3 h^2 x 8 B <= 150 KB, h <= 79): every pixel is read and projected
 // (3 fp64 logs) ONCE; otherwise plane after plane through one grid (the 2nd / 3rd read of a pixel hits L2).
-template <bool ALL3, bool LAB = false>
-__global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevParams P, const float *__restrict__ x,
-                                                                    float *__restrict__ slabs,
-                                                                    double *__restrict__ slab_tot, int per_block) {
+template <bool ALL3, bool LAB, typename Scatter>
+__device__ __forceinline__ void scatter_fwd(const DevParams &P, const float *__restrict__ x, float *__restrict__ slabs,
+                                            double *__restrict__ slab_tot, int per_block, Scatter scatter) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ unsigned long long sm_tot[16];
   unsigned long long *bins = reinterpret_cast<unsigned long long *>(smem);   // [planes][h][h]
   constexpr int NT = ALL3 ? 1024 : 256;
   unsigned long long tot = 0ull;
-  const int b = blockIdx.y, s = blockIdx.x, S = gridDim.x, h = P.h, hh = h * h;
+  const int b = blockIdx.y, s = blockIdx.x, S = gridDim.x, hh = P.h * P.h;
   const float *xb = x + (long long)b * P.sb;
   const int n0 = s * per_block, n1 = min(P.npix, n0 + per_block);
   float *slab = slabs + ((long long)(b * S + s) * P.P) * hh;
-  const double inv_step = P.step > 0.0 ? 1.0 / P.step : 0.0, w = P.half_eps * inv_step;
-  const bool single = P.h > 1 && P.step > 2.0 * P.half_eps * (1.0 + 1e-9);
+  auto fetch = [&](int n, float &a, float &bb, float &c, float &iy) __attribute__((always_inline)) {
+    float r, g, bl;
+    sample_rgb(P, xb, n, r, g, bl);
+    project<LAB>(P, r, g, bl, a, bb, c, iy);
+    iy = __fmul_rn(sample_weight(P, b, n), iy);         // weight map, before the fixed-point conversion
+  };
   if constexpr (ALL3) {
     for (int e = threadIdx.x; e < P.P * hh; e += NT) bins[e] = 0ull;
     __syncthreads();
     for (int n = n0 + threadIdx.x; n < n1; n += NT) {
-      float r, g, bl, a, bb, c, iy;
-      sample_rgb(P, xb, n, r, g, bl);
-      project<LAB>(P, r, g, bl, a, bb, c, iy);
-      iy = __fmul_rn(sample_weight(P, b, n), iy);       // weight map, before the fixed-point conversion
-      const unsigned long long q = (unsigned long long)((double)iy * kThrScale + 0.5);
+      float a, bb, c, iy;
+      fetch(n, a, bb, c, iy);
       if (P.green) {
-        thr_scatter_plane(P, bins, -a, c, inv_step, w, single, q);
+        scatter(bins, -a, c, iy);
       } else {
-        thr_scatter_plane(P, bins, a, bb, inv_step, w, single, q);
-        thr_scatter_plane(P, bins + hh, -a, c, inv_step, w, single, q);
-        thr_scatter_plane(P, bins + 2 * hh, -bb, -c, inv_step, w, single, q);
+        scatter(bins, a, bb, iy);
+        scatter(bins + hh, -a, c, iy);
+        scatter(bins + 2 * hh, -bb, -c, iy);
       }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < P.P * hh; e += NT) {
-      const unsigned long long v = bins[e];
-      tot += v;
-      slab[e] = (float)((double)v * (1.0 / kThrScale));
-    }
+    flush_grid<NT>(bins, P.P * hh, slab, tot);
   } else {
     for (int p = 0; p < 3; ++p) {
       if (P.green && p != 1) continue;
       for (int e = threadIdx.x; e < hh; e += NT) bins[e] = 0ull;
       __syncthreads();
       for (int n = n0 + threadIdx.x; n < n1; n += NT) {
-        float r, g, bl, a, bb, c, iy;
-        sample_rgb(P, xb, n, r, g, bl);
-        project<LAB>(P, r, g, bl, a, bb, c, iy);
-        iy = __fmul_rn(sample_weight(P, b, n), iy);
-        const float u = p == 0 ? a : (p == 1 ? -a : -bb), v = p == 0 ? bb : (p == 1 ? c : -c);
-        thr_scatter_plane(P, bins, u, v, inv_step, w, single, (unsigned long long)((double)iy * kThrScale + 0.5));
+        float a, bb, c, iy, u, v;
+        fetch(n, a, bb, c, iy);
+        plane_uv(p, a, bb, c, u, v);
+        scatter(bins, u, v, iy);
       }
       __syncthreads();
-      float *dst = slab + (long long)(P.green ? 0 : p) * hh;
-      for (int e = threadIdx.x; e < hh; e += NT) {
-        const unsigned long long v = bins[e];
-        tot += v;
-        dst[e] = (float)((double)v * (1.0 / kThrScale));
-      }
+      flush_grid<NT>(bins, hh, slab + (long long)(P.green ? 0 : p) * hh, tot);
       __syncthreads();
     }
   }
@@ -1606,10 +1640,23 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevPar
   if (threadIdx.x == 0) slab_tot[b * S + s] = (double)tot * (1.0 / kThrScale);
 }
 
+template <bool ALL3, bool LAB = false>
+__global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_thr_fwd(const DevParams P, const float *__restrict__ x,
+                                                                    float *__restrict__ slabs,
+                                                                    double *__restrict__ slab_tot, int per_block) {
+  const double is = inv_step(P), w = P.half_eps * is;
+  const bool single = thr_windows_single(P.h, P.step, P.half_eps);
+  scatter_fwd<ALL3, LAB>(P, x, slabs, slab_tot, per_block,
+                         [&](unsigned long long *grid, float u, float v, float iy) __attribute__((always_inline)) {
+    thr_scatter_plane(P, grid, u, v, is, w, single, (unsigned long long)((double)iy * kThrScale + 0.5));
+  });
+}
+
 // Backward of the thresholding histogram: the window has zero slope, so the only path to the pixel is the weight Iy:
 // dL/dIy = sum over planes of Ghat at the pixel's bin(s) -- a gather -- and dx_c = dL/dIy * x_c / Iy (store_pixel_grad).
 // WG: the weight map's gradient is that gather times the pixel's non-map factor -- also without intensity_scale, where the
-// colour gradient is identically zero.
+// colour gradient is identically zero.  The tail stays written out with literal zero slopes: on gather_epilogue (slopes as
+// run-time zeros) grad_x and grad_weight did not hash equal to the kernel as it was.
 template <bool WG = false, bool LAB = false>
 __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const float *__restrict__ x,
                                                       const float *__restrict__ gh, float *__restrict__ gdst) {
@@ -1619,29 +1666,31 @@ __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const f
   float r, g, bl, a, bb, c, iy;
   sample_rgb(P, xb, n, r, g, bl);
   project<LAB>(P, r, g, bl, a, bb, c, iy);
-  float dIy = 0.f;
+  float isum = 0.f;
   if (P.intensity || WG) {
-    const double inv_step = P.step > 0.0 ? 1.0 / P.step : 0.0, w = P.half_eps * inv_step;
-    const bool single = P.h > 1 && P.step > 2.0 * P.half_eps * (1.0 + 1e-9);
+    const double is = inv_step(P), w = P.half_eps * is;
+    const bool single = thr_windows_single(P.h, P.step, P.half_eps);
     for (int p = 0; p < 3; ++p) {
       if (P.green && p != 1) continue;
       const float *G = gh + ((long long)b * P.P + (P.green ? 0 : p)) * h * h;
-      const float u = p == 0 ? a : (p == 1 ? -a : -bb), v = p == 0 ? bb : (p == 1 ? c : -c);
+      float u, v;
+      plane_uv(p, a, bb, c, u, v);
       if (single) {
-        const int i = thr_single(P, u, inv_step), j = thr_single(P, v, inv_step);
-        if (i >= 0 && j >= 0) dIy += G[i * h + j];
+        const int i = thr_single(P, u, is), j = thr_single(P, v, is);
+        if (i >= 0 && j >= 0) isum += G[i * h + j];
         continue;
       }
       int ul, uh, vl, vh;
-      thr_range(P, u, inv_step, w, ul, uh);
-      thr_range(P, v, inv_step, w, vl, vh);
+      thr_range(P, u, is, w, ul, uh);
+      thr_range(P, v, is, w, vl, vh);
       for (int i = ul; i <= uh; ++i) {
         if (!thr_hit(P, u, i)) continue;
         for (int j = vl; j <= vh; ++j)
-          if (thr_hit(P, v, j)) dIy += G[i * h + j];
+          if (thr_hit(P, v, j)) isum += G[i * h + j];
       }
     }
   }
+  float dIy = isum;
   if constexpr (WG) {
     store_weight_grad(P, b, n, __fmul_rn(dIy, iy));
     if (!P.intensity) dIy = 0.f;
@@ -1649,8 +1698,7 @@ __global__ __launch_bounds__(256) void k_hist_thr_bwd(const DevParams P, const f
   dIy = __fmul_rn(dIy, sample_weight(P, b, n));       // weight map: dL/dIy = w_n dL/d(w_n Iy)
   if (LAB || P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj<LAB>(P, xb, b, n, r, g, bl, iy, 0.f, 0.f, dIy, gdst);
   else store_pixel_grad(P, xb, b, n, r, g, bl, iy, 0.f, 0.f, 0.f, dIy, gdst);
-  if (P.mode == HG_RESIZE_NONE)
-    for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
+  zero_extra_channels(P, b, n, gdst);
 }
 
 // XCD-aware (image, slice) of a workgroup in a (S, B) grid.  Block L = y*S + x runs on XCD L % 8 (observed placement;
@@ -1666,6 +1714,15 @@ __device__ __forceinline__ void xcd_image_slice(int B, int &b, int &s) {
     s = j % S;
     b = (j / S) * 8 + xcd;
   }
+}
+
+// one DIRECT tile of a lean kernel: four consecutive pixels of each colour plane and of the weight map (if any), 16-byte loads
+__device__ __forceinline__ void load_tile4(const float *xb, long long sc, const float *wb, int n, float4 &r4, float4 &g4,
+                                           float4 &b4, float4 &w4) {
+  r4 = *reinterpret_cast<const float4 *>(xb + n);
+  g4 = *reinterpret_cast<const float4 *>(xb + sc + n);
+  b4 = *reinterpret_cast<const float4 *>(xb + 2 * sc + n);
+  if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n);
 }
 
 // ---- lean scatter kernels: RGB-uv, three planes, `single` windows, all three grids in LDS ----------------------------
@@ -1699,12 +1756,7 @@ __global__ __launch_bounds__(1024) void k_thr_fwd_lean(const DevParams P, const 
   const float *wb = P.weight ? P.weight + (long long)b * P.wsb : nullptr;
   float4 w4 = make_float4(1.f, 1.f, 1.f, 1.f);
   int n = n0 + 4 * threadIdx.x;
-  if (DIRECT && n < n1) {
-    r4 = *reinterpret_cast<const float4 *>(xb + n);
-    g4 = *reinterpret_cast<const float4 *>(xb + P.sc + n);
-    b4 = *reinterpret_cast<const float4 *>(xb + 2 * P.sc + n);
-    if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n);
-  }
+  if (DIRECT && n < n1) load_tile4(xb, P.sc, wb, n, r4, g4, b4, w4);
   {
     ulonglong2 *b2 = reinterpret_cast<ulonglong2 *>(bins);
     for (int e = threadIdx.x; e < (3 * hh + 1) / 2; e += 1024) b2[e] = make_ulonglong2(0ull, 0ull);  // LDS is sized in 16-byte units
@@ -1723,12 +1775,7 @@ __global__ __launch_bounds__(1024) void k_thr_fwd_lean(const DevParams P, const 
   if constexpr (DIRECT) {
     for (; n < n1; n += 4096) {
       const float4 rc = r4, gc = g4, bc = b4, wc = w4;
-      if (n + 4096 < n1) {                              // next tile's loads before this tile's arithmetic
-        r4 = *reinterpret_cast<const float4 *>(xb + n + 4096);
-        g4 = *reinterpret_cast<const float4 *>(xb + P.sc + n + 4096);
-        b4 = *reinterpret_cast<const float4 *>(xb + 2 * P.sc + n + 4096);
-        if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n + 4096);
-      }
+      if (n + 4096 < n1) load_tile4(xb, P.sc, wb, n + 4096, r4, g4, b4, w4);   // next tile's loads before this tile's arithmetic
       pixel(clamp01(rc.x), clamp01(gc.x), clamp01(bc.x), clamp01(wc.x));
       pixel(clamp01(rc.y), clamp01(gc.y), clamp01(bc.y), clamp01(wc.y));
       pixel(clamp01(rc.z), clamp01(gc.z), clamp01(bc.z), clamp01(wc.z));
@@ -1769,11 +1816,7 @@ __global__ __launch_bounds__(1024) void k_thr_fwd_lean(const DevParams P, const 
       slab[e] = (float)((double)v * (1.0 / kThrScale));
     }
   } else {
-    for (int e = threadIdx.x; e < 3 * hh; e += 1024) {
-      const unsigned long long v = bins[e];
-      tot += v;
-      slab[e] = (float)((double)v * (1.0 / kThrScale));
-    }
+    flush_grid<1024>(bins, 3 * hh, slab, tot);
   }
   tot = block_sum_u64<1024>(tot, sm_tot);
   if (threadIdx.x == 0) slab_tot[b * S + s] = (double)tot * (1.0 / kThrScale);
@@ -1803,12 +1846,7 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
   const float *wb = P.weight ? P.weight + (long long)b * P.wsb : nullptr;   // weight map, as in k_thr_fwd_lean
   float4 w4 = make_float4(1.f, 1.f, 1.f, 1.f);
   int n = n0 + 4 * threadIdx.x;
-  if (DIRECT && n < n1) {
-    r4 = *reinterpret_cast<const float4 *>(xb + n);
-    g4 = *reinterpret_cast<const float4 *>(xb + P.sc + n);
-    b4 = *reinterpret_cast<const float4 *>(xb + 2 * P.sc + n);
-    if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n);
-  }
+  if (DIRECT && n < n1) load_tile4(xb, P.sc, wb, n, r4, g4, b4, w4);
   const bool al16 = (((uintptr_t)g | (uintptr_t)o) & 15) == 0;
   // <G, out> with every load in flight at once: a thread owns groups of four consecutive bins (16-byte loads), keeps
   // its G values in registers, and writes Ghat = (G - <G,out>) / S' to LDS once the sum is known.  Fixed summation order.
@@ -1833,12 +1871,7 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
   float gt = 0.f;
   const int et = 4 * nq + (int)threadIdx.x;            // tail bins (nel % 4 of them)
   if (et < nel) { gt = g[et]; d = fmaf(gt, o[et], d); }
-  d = hg_wave_sum(d);
-  if ((threadIdx.x & 63) == 0) sm16[threadIdx.x >> 6] = d;
-  __syncthreads();
-  d = 0.f;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) d += sm16[w];
+  d = block_sum_1024(d, sm16);
   const float inv = 1.f / sums[b];
 #pragma unroll
   for (int k = 0; k < MAXQ; ++k) {
@@ -1869,12 +1902,7 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
     float *gb = gdst + ((long long)b * P.C) * P.npix;
     for (; n < n1; n += 4096) {
       const float4 rc = r4, gc = g4, bc = b4, wc = w4;
-      if (n + 4096 < n1) {                              // next tile's loads before this tile's arithmetic
-        r4 = *reinterpret_cast<const float4 *>(xb + n + 4096);
-        g4 = *reinterpret_cast<const float4 *>(xb + P.sc + n + 4096);
-        b4 = *reinterpret_cast<const float4 *>(xb + 2 * P.sc + n + 4096);
-        if (wb) w4 = *reinterpret_cast<const float4 *>(wb + n + 4096);
-      }
+      if (n + 4096 < n1) load_tile4(xb, P.sc, wb, n + 4096, r4, g4, b4, w4);   // next tile's loads before this tile's arithmetic
       float4 or4, og4, ob4;
       [[maybe_unused]] float4 ow4 = make_float4(0.f, 0.f, 0.f, 0.f);
       pixel(clamp01(rc.x), clamp01(gc.x), clamp01(bc.x), clamp01(wc.x), or4.x, og4.x, ob4.x, ow4.x);
@@ -1905,8 +1933,7 @@ __global__ __launch_bounds__(1024) void k_thr_bwd_lean(const DevParams P, const 
       pixel(r, gg, bl, sample_weight(P, b, m), dr, dg, db, gwn);
       store_rgb_grad(P, xb, b, m, dr, dg, db, gdst);
       if constexpr (WG) store_weight_grad(P, b, m, gwn);
-      if (P.mode == HG_RESIZE_NONE)
-        for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + m] = 0.f;
+      zero_extra_channels(P, b, m, gdst);
     }
   }
 }
@@ -1929,18 +1956,10 @@ template <bool ALL3, bool LAB = false>
 __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_rbf_fwd(const DevParams P, const float *__restrict__ x,
                                                                     float *__restrict__ slabs,
                                                                     double *__restrict__ slab_tot, int per_block, int R) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ unsigned long long sm_tot[16];
-  unsigned long long *bins = reinterpret_cast<unsigned long long *>(smem);   // [planes][h][h]
-  constexpr int NT = ALL3 ? 1024 : 256;
-  unsigned long long tot = 0ull;
-  const int b = blockIdx.y, s = blockIdx.x, S = gridDim.x, h = P.h, hh = h * h;
-  const float *xb = x + (long long)b * P.sb;
-  const int n0 = s * per_block, n1 = min(P.npix, n0 + per_block);
-  float *slab = slabs + ((long long)(b * S + s) * P.P) * hh;
-  const double inv_step = P.step > 0.0 ? 1.0 / P.step : 0.0;
+  const int h = P.h;
+  const double is = inv_step(P);
   auto scatter = [&](unsigned long long *grid, float u, float v, float iy) __attribute__((always_inline)) {
-    const int ic = rbf_center(P, u, inv_step), jc = rbf_center(P, v, inv_step);
+    const int ic = rbf_center(P, u, is), jc = rbf_center(P, v, is);
     float ku[2 * HG_RBF_RMAX + 1], kv[2 * HG_RBF_RMAX + 1];
 #pragma unroll
     for (int d = 0; d < 2 * HG_RBF_RMAX + 1; ++d) {
@@ -1959,52 +1978,7 @@ __global__ __launch_bounds__(ALL3 ? 1024 : 256) void k_hist_rbf_fwd(const DevPar
       }
     }
   };
-  if constexpr (ALL3) {
-    for (int e = threadIdx.x; e < P.P * hh; e += NT) bins[e] = 0ull;
-    __syncthreads();
-    for (int n = n0 + threadIdx.x; n < n1; n += NT) {
-      float r, g, bl, a, bb, c, iy;
-      sample_rgb(P, xb, n, r, g, bl);
-      project<LAB>(P, r, g, bl, a, bb, c, iy);
-      iy = __fmul_rn(sample_weight(P, b, n), iy);       // weight map
-      if (P.green) {
-        scatter(bins, -a, c, iy);
-      } else {
-        scatter(bins, a, bb, iy);
-        scatter(bins + hh, -a, c, iy);
-        scatter(bins + 2 * hh, -bb, -c, iy);
-      }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < P.P * hh; e += NT) {
-      const unsigned long long v = bins[e];
-      tot += v;
-      slab[e] = (float)((double)v * (1.0 / kThrScale));
-    }
-  } else {
-    for (int p = 0; p < 3; ++p) {
-      if (P.green && p != 1) continue;
-      for (int e = threadIdx.x; e < hh; e += NT) bins[e] = 0ull;
-      __syncthreads();
-      for (int n = n0 + threadIdx.x; n < n1; n += NT) {
-        float r, g, bl, a, bb, c, iy;
-        sample_rgb(P, xb, n, r, g, bl);
-        project<LAB>(P, r, g, bl, a, bb, c, iy);
-        iy = __fmul_rn(sample_weight(P, b, n), iy);
-        scatter(bins, p == 0 ? a : (p == 1 ? -a : -bb), p == 0 ? bb : (p == 1 ? c : -c), iy);
-      }
-      __syncthreads();
-      float *dst = slab + (long long)(P.green ? 0 : p) * hh;
-      for (int e = threadIdx.x; e < hh; e += NT) {
-        const unsigned long long v = bins[e];
-        tot += v;
-        dst[e] = (float)((double)v * (1.0 / kThrScale));
-      }
-      __syncthreads();
-    }
-  }
-  tot = block_sum_u64<NT>(tot, sm_tot);
-  if (threadIdx.x == 0) slab_tot[b * S + s] = (double)tot * (1.0 / kThrScale);
+  scatter_fwd<ALL3, LAB>(P, x, slabs, slab_tot, per_block, scatter);
 }
 
 // Backward of the truncated RBF histogram: the generic backward's two mat-vecs per plane restricted to the (2R+1)^2
@@ -2018,13 +1992,14 @@ __global__ __launch_bounds__(256) void k_hist_rbf_bwd(const DevParams P, const f
   float r, g, bl, a, bb, c, iy;
   sample_rgb(P, xb, n, r, g, bl);
   project<LAB>(P, r, g, bl, a, bb, c, iy);
-  const double inv_step = P.step > 0.0 ? 1.0 / P.step : 0.0;
+  const double is = inv_step(P);
   float gu[3] = {0.f, 0.f, 0.f}, gv[3] = {0.f, 0.f, 0.f}, isum = 0.f;
   for (int p = 0; p < 3; ++p) {
     if (P.green && p != 1) continue;
     const float *G = gh + ((long long)b * P.P + (P.green ? 0 : p)) * h * h;
-    const float u = p == 0 ? a : (p == 1 ? -a : -bb), v = p == 0 ? bb : (p == 1 ? c : -c);
-    const int ic = rbf_center(P, u, inv_step), jc = rbf_center(P, v, inv_step);
+    float u, v;
+    plane_uv(p, a, bb, c, u, v);
+    const int ic = rbf_center(P, u, is), jc = rbf_center(P, v, is);
     float ku[2 * HG_RBF_RMAX + 1], dku[2 * HG_RBF_RMAX + 1], kv[2 * HG_RBF_RMAX + 1], dkv[2 * HG_RBF_RMAX + 1];
 #pragma unroll
     for (int d = 0; d < 2 * HG_RBF_RMAX + 1; ++d) {
@@ -2055,14 +2030,7 @@ __global__ __launch_bounds__(256) void k_hist_rbf_bwd(const DevParams P, const f
 #pragma unroll
     for (int dj = 0; dj < 2 * HG_RBF_RMAX + 1; ++dj) gv[p] = fmaf(dkv[dj], Sx[dj], gv[p]);
   }
-  const float wn = sample_weight(P, b, n), wiy = __fmul_rn(wn, iy);   // weight map x Iy: the pixel's histogram weight
-  const float da = wiy * (gu[0] - gu[1]), db = wiy * (gv[0] - gu[2]), dc = wiy * (gv[1] - gv[2]);
-  const float dIy = P.intensity ? __fmul_rn(isum, wn) : 0.f;
-  if (LAB || P.proj != HG_PROJ_RGBUV) store_pixel_grad_proj<LAB>(P, xb, b, n, r, g, bl, iy, wiy * gu[1], wiy * gv[1], dIy, gdst);
-  else store_pixel_grad(P, xb, b, n, r, g, bl, iy, da, db, dc, dIy, gdst);
-  if (P.mode == HG_RESIZE_NONE)
-    for (int cc = 3; cc < P.C; ++cc) gdst[((long long)b * P.C + cc) * P.npix + n] = 0.f;
-  if constexpr (WG) store_weight_grad(P, b, n, __fmul_rn(isum, iy));
+  gather_epilogue<WG, LAB>(P, xb, b, n, r, g, bl, iy, sample_weight(P, b, n), gu, gv, isum, gdst);
 }
 
 // Adjoint of the bilinear resize (deterministic gather) fused with the clamp mask.
@@ -2215,12 +2183,12 @@ inline int rbf_radius(const hg_hist_params *p) {
   return (R >= 1 && R <= HG_RBF_RMAX) ? R : 0;
 }
 
-// `single` windows: narrower than the bin spacing, so a value falls into at most one bin (every symmetric boundary)
+// thr_windows_single of the call's bins
 inline bool thr_single(const hg_hist_params *p) {
   if (p->h < 2) return false;
   const double step = (p->hi - p->lo) / (double)(p->h - 1);
   const double half_eps = ((p->lo < 0 ? -p->lo : p->lo) + (p->hi < 0 ? -p->hi : p->hi)) / (double)p->h / 2.0;
-  return step > 2.0 * half_eps * (1.0 + 1e-9);
+  return thr_windows_single(p->h, step, half_eps);
 }
 
 // The one place the dispatch rule lives, and the one reader of the three A/B switches (read on every call):

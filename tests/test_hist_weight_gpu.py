@@ -134,7 +134,15 @@ GPU_DEF_EXTRA = [
 ]
 
 
-@pytest.mark.parametrize('proj,kw,shape,layout,pre_relu', C.DEF_CASES + GPU_DEF_EXTRA)
+# three planes whose LDS grids do not fit together (h = 81): the plane-after-plane branch of the scatter forwards.  A list of
+# its own, appended after every other: the case indices of tests/test_hist_weight_grad_gpu.py stay what they were.
+GPU_DEF_PLANES = [
+    ('rgbuv', dict(h=81, insz=64, method='thresholding'), (2, 3, 24, 28), 'bhw', False),
+    ('rgbuv', dict(h=81, insz=64, method='RBF', sigma=0.02), (2, 3, 24, 28), 'bhw', False),
+]
+
+
+@pytest.mark.parametrize('proj,kw,shape,layout,pre_relu', C.DEF_CASES + GPU_DEF_EXTRA + GPU_DEF_PLANES)
 def test_fractional_weights_and_resizing_match_the_definition(proj, kw, shape, layout, pre_relu, gpu_device):
     fam, _ = family(torch.empty(*shape, device=gpu_device), proj, kw)
     e_f, e_b = C.check_definition(proj, kw, shape, layout, pre_relu, gpu_device)

@@ -19,7 +19,7 @@ import test_hist_weight_grad_cpu as WC
 from conftest import relmax
 from hist_weight_ref import BWD_TOL, make_block, sample_image
 from test_hist_weight_cpu import DEF_CASES
-from test_hist_weight_gpu import EXACT_CASES, GPU_DEF_EXTRA, family
+from test_hist_weight_gpu import EXACT_CASES, GPU_DEF_EXTRA, GPU_DEF_PLANES, family
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +54,7 @@ OWN_CASES = [
     ('rgbuv', dict(h=16, insz=64, method='thresholding', intensity_scale=False), (2, 3, 40, 48), 'bhw', False),
     ('rgbuv', dict(h=16, insz=64, method='thresholding', intensity_scale=False), (2, 3, 41, 45), 'b1hw', True),
 ]
-CASES = DEF_CASES + GPU_DEF_EXTRA + OWN_CASES
+CASES = DEF_CASES + GPU_DEF_EXTRA + OWN_CASES + GPU_DEF_PLANES
 WANT = {           # case index -> the family it must run on: every backward family at least once
     0: 'dense fwd + k_hist_bwd',                # T = 1, bilinear
     1: 'dense fwd + k_hist_bwd',                # T = 1, sampling, C = 4
@@ -74,6 +74,8 @@ WANT = {           # case index -> the family it must run on: every backward fam
     15: 'truncated RBF scatter / gather',       # bilinear
     16: 'lean scatter',
     17: 'lean scatter',
+    18: 'thresholding scatter / gather',        # h = 81, three planes: plane-after-plane forward
+    19: 'truncated RBF scatter / gather',       # h = 81, three planes, radius 2
 }
 
 
