@@ -253,6 +253,11 @@ def _load():
     lib.hg_srgb_to_lab.argtypes = [vp, i64, i64, i64, i64, vp, i32, i32, i32, vp]
     lib.hg_lab_to_srgb.restype = ctypes.c_int
     lib.hg_lab_to_srgb.argtypes = [vp, i64, i64, i64, i64, vp, i32, i32, i32, vp]
+    lib.hg_delta_e_workspace_bytes.restype = sz
+    lib.hg_delta_e_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.hg_delta_e.restype = ctypes.c_int
+    lib.hg_delta_e.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, vp, i64, i64, i64, i32, vp, vp, vp, i32, i32, i32,
+                               vp, sz, vp]
     return lib
 
 
@@ -276,7 +281,7 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
            'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd', 'hg_noise_grad',
            'hg_resize_axis', 'hg_pyr_down', 'hg_pyr_up_add', 'hg_color_moments_workspace_bytes', 'hg_color_moments',
            'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc', 'hg_bgu_normal_workspace_bytes', 'hg_bgu_normal',
-           'hg_bgu_slice', 'hg_srgb_to_lab', 'hg_lab_to_srgb')
+           'hg_bgu_slice', 'hg_srgb_to_lab', 'hg_lab_to_srgb', 'hg_delta_e_workspace_bytes', 'hg_delta_e')
 
 
 class HgError(RuntimeError):

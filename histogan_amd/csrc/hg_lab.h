@@ -1,5 +1,6 @@
 // hg_lab.h -- sRGB <-> normalised CIE Lab, the one statement of the chain that the HG_PROJ_LAB projection of hg_hist.hip and
-// the stand-alone conversions of hg_post.hip (hg_srgb_to_lab, hg_lab_to_srgb) evaluate.
+// the stand-alone conversions of hg_post.hip (hg_srgb_to_lab, hg_lab_to_srgb) evaluate, and -- unrounded, in Lab units -- the
+// colour differences of hg_deltae.hip (hg_delta_e).
 //
 //   c_lin = c / 12.92 (c <= 0.04045), else ((c + 0.055) / 1.055)^2.4
 //   (X, Y, Z) = M c_lin, M the D65 matrix below with every row divided by its own sum (so white is (1, 1, 1))
@@ -89,6 +90,38 @@ __device__ __forceinline__ void lab_to_srgb(float Ln, float an, float bn, float 
   r = enc(kMi[0][0] * X + kMi[0][1] * Y + kMi[0][2] * Z);
   g = enc(kMi[1][0] * X + kMi[1][1] * Y + kMi[1][2] * Z);
   b = enc(kMi[2][0] * X + kMi[2][1] * Y + kMi[2][2] * Z);
+}
+
+// The chain WITHOUT its rounding and without the 8-bit normalisation, for the colour differences of hg_deltae.hip: c (sRGB in
+// [0, 1], the fp32 inputs widened) -> lab = (L, a, b) in Lab units, fp64.  With SLOPES it also leaves what lab_pullback needs:
+// dlin[j] = (c_lin)'(c_j) and dfp[i] = f'(t_i), the same closed forms as srgb_to_lab_grad (no second pow / cbrt).
+template <bool SLOPES>
+__device__ __forceinline__ void srgb_to_lab_f64(const double (&c)[3], double (&lab)[3], double (&dlin)[3], double (&dfp)[3]) {
+  double lin[3], f[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    lin[j] = srgb_lin(c[j]);
+    if constexpr (SLOPES) dlin[j] = c[j] <= kKnee ? 1.0 / 12.92 : 2.4 * lin[j] / (c[j] + 0.055);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double t = kM[i][0] * lin[0] + kM[i][1] * lin[1] + kM[i][2] * lin[2];
+    f[i] = lab_f(t);
+    if constexpr (SLOPES) dfp[i] = t > kDelta3 ? f[i] / (3.0 * t) : kSlope;
+  }
+  lab[0] = 116.0 * f[1] - 16.0;
+  lab[1] = 500.0 * (f[0] - f[1]);
+  lab[2] = 200.0 * (f[1] - f[2]);
+}
+
+// (d/dL, d/da, d/db) in Lab units -> (d/dr, d/dg, d/db) through the Jacobian of srgb_to_lab_f64 at the point whose slopes
+// dlin, dfp are given; fp64, not rounded.
+__device__ __forceinline__ void lab_pullback(const double (&dlin)[3], const double (&dfp)[3], const double (&dlab)[3],
+                                             double (&dc)[3]) {
+  const double dfx = 500.0 * dlab[1], dfz = -200.0 * dlab[2];
+  const double dxyz[3] = {dfx * dfp[0], (116.0 * dlab[0] - dfx - dfz) * dfp[1], dfz * dfp[2]};
+#pragma unroll
+  for (int j = 0; j < 3; ++j) dc[j] = (kM[0][j] * dxyz[0] + kM[1][j] * dxyz[1] + kM[2][j] * dxyz[2]) * dlin[j];
 }
 
 }  // namespace hg_lab

@@ -9,6 +9,10 @@ host-built resize tables (fp64, passed as fp32) and the 3x3 algebra of MKL stay 
 Device layouts: float images are (C, H, W) -- any strides -- and come back contiguous; uint8 images are (H, W, C), as
 PIL and the reference's uint8 path hold them.  The drop-ins at the reference's import paths (utils/imresize.py,
 utils/pyramid_upsampling.py, utils/color_transfer_MKL.py) convert to and from the reference's host types around these.
+
+Also here, with no counterpart in the reference: the sRGB <-> CIE Lab conversions, and the CIE colour difference between
+two sRGB images (delta_e, delta_e_map: dE76 and CIEDE2000) as a differentiable loss and as the metric reported for
+recolourings.
 """
 import ctypes
 from functools import lru_cache
@@ -191,6 +195,116 @@ def lab_to_srgb(x):
     """The exact inverse of srgb_to_lab, clipped to [0, 1] (hg_lab_to_srgb): normalised Lab -> sRGB, e.g. to save what a
     network trained on Lab images generates.  Not differentiable."""
     return _lab_convert(x, lib.hg_lab_to_srgb, 'lab_to_srgb')
+
+
+# ---- device: CIE colour difference (hg_delta_e) -----------------------------------------------------------------------
+_DE_KINDS = {'76': 76, '2000': 2000, 76: 76, 2000: 2000}
+
+
+def delta_e_kind(kind, what='delta_e'):
+    """'76' | '2000' | 76 | 2000 -> the C ABI's integer; anything else raises ValueError (no HIP call is made)."""
+    try:
+        if isinstance(kind, bool):
+            raise KeyError(kind)
+        return _DE_KINDS[kind]
+    except (KeyError, TypeError):
+        raise ValueError(f"{what}: kind must be '76' or '2000' (dE76, CIEDE2000), not {kind!r}") from None
+
+
+def _de_image(t, what, name):
+    need_gpu(t, what, _FOUND)
+    if t.dim() != 4 or t.shape[1] != 3 or not t.is_floating_point():
+        raise ValueError(f'{what}: {name} must be a float (B, 3, H, W) or (3, H, W) tensor, got {t.dtype} {tuple(t.shape)}')
+    t = t.detach()
+    return t if t.dtype == torch.float32 else t.float()
+
+
+def _delta_e_launch(pred, target, weight, kind, want_map, want_grad, what):
+    """One hg_delta_e call on (B, 3, H, W) images: (mean (B,), map (B, H, W) or None, grad (B, 3, H, W) or None), fp32."""
+    x1, x2 = _de_image(pred, what, 'pred'), _de_image(target, what, 'target')
+    if x1.shape != x2.shape or x1.device != x2.device:
+        raise ValueError(f'{what}: pred and target must have one shape and device, got {tuple(x1.shape)} on {x1.device} and '
+                         f'{tuple(x2.shape)} on {x2.device}')
+    B, _, H, W = x1.shape
+    w, wptr, wstr = None, None, (0, 0, 0)
+    if weight is not None:
+        need_gpu(weight, what, _FOUND)
+        w = weight.detach()
+        if w.dim() == 4 and w.shape[1] == 1:
+            w = w[:, 0]
+        if tuple(w.shape) != (B, H, W) or not w.is_floating_point() or w.device != x1.device:
+            raise ValueError(f'{what}: weight must be a float (B, H, W) or (B, 1, H, W) map = {(B, H, W)} on {x1.device}, got '
+                             f'{weight.dtype} {tuple(weight.shape)} on {weight.device}')
+        w = w if w.dtype == torch.float32 else w.float()
+        wptr, wstr = w.data_ptr(), w.stride()
+    dev = x1.device
+    with on_device(dev):
+        mean = torch.empty((B,), dtype=torch.float32, device=dev)
+        dmap = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_map else None
+        grad = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if want_grad else None
+        nb = lib.hg_delta_e_workspace_bytes(B, H, W)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
+        check(lib.hg_delta_e(x1.data_ptr(), *x1.stride(), x2.data_ptr(), *x2.stride(), wptr, *wstr, kind, mean.data_ptr(),
+                             None if dmap is None else dmap.data_ptr(), None if grad is None else grad.data_ptr(), B, H, W,
+                             ws.data_ptr(), nb, raw_stream(dev)), 'hg_delta_e')
+    return mean, dmap, grad
+
+
+class DeltaEFunction(torch.autograd.Function):
+    """mean dE per sample; the gradient for `pred` is computed in the forward (one fused launch, as HellingerFunction) and
+    saved, the backward scales it by the upstream vector.  target and weight get no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, kind):
+        want = ctx.needs_input_grad[0]
+        mean, _, grad = _delta_e_launch(pred, target, weight, kind, False, want, 'delta_e')
+        ctx.dtype = pred.dtype
+        if want:
+            ctx.save_for_backward(grad)
+        return mean
+
+    @staticmethod
+    def backward(ctx, up):
+        (grad,) = ctx.saved_tensors
+        return (grad * up[:, None, None, None]).to(ctx.dtype), None, None, None
+
+
+def _de_batched(pred, target, what):
+    for t, name in ((pred, 'pred'), (target, 'target')):
+        need_gpu(t, what, _FOUND)
+        if t.dim() not in (3, 4):
+            raise ValueError(f'{what}: {name} must be a float (B, 3, H, W) or (3, H, W) tensor, got {t.dtype} {tuple(t.shape)}')
+    single = pred.dim() == 3
+    return single, (pred.unsqueeze(0) if single else pred), (target.unsqueeze(0) if target.dim() == 3 else target)
+
+
+def delta_e(pred, target, kind='2000', weight=None):
+    """The CIE colour difference between two sRGB images as a loss: fp32 (B,) per-sample means of dE over the pixels (a
+    0-dim tensor for (3, H, W) inputs), in Lab units.  kind: '2000' (CIEDE2000, kL = kC = kH = 1) or '76' (the Euclidean
+    distance in Lab).  pred, target: float (B, 3, H, W) or (3, H, W), any strides, clamped to [0, 1] as they are read; both go
+    through the chain of srgb_to_lab in fp64 without its rounding (include/hg_post.h, hg_delta_e, states every formula and
+    the conventions at the singular points).  weight: optional (B, H, W) / (B, 1, H, W) map (for (3, H, W) inputs also
+    (H, W)), clamped to [0, 1]: the mean becomes sum w dE / sum w, and 0 for an all-zero map.
+
+    Differentiable with respect to `pred` (finite everywhere; zero where pred == target and for components outside [0, 1]);
+    target and weight get no gradient, and a weight that requires grad raises ValueError."""
+    k = delta_e_kind(kind)
+    if torch.is_tensor(weight) and weight.requires_grad:          # before any HIP call
+        raise ValueError('delta_e: the weight map gets no gradient, but it requires grad; pass weight.detach()')
+    single, p4, t4 = _de_batched(pred, target, 'delta_e')
+    if weight is not None and single and torch.is_tensor(weight) and weight.dim() == 2:
+        weight = weight.unsqueeze(0)
+    out = DeltaEFunction.apply(p4, t4, weight, k)
+    return out[0] if single else out
+
+
+def delta_e_map(pred, target, kind='2000'):
+    """The per-pixel dE of delta_e: fp32 (B, H, W), or (H, W) for (3, H, W) inputs.  Not differentiable: the result carries no
+    graph whatever the inputs require."""
+    k = delta_e_kind(kind, 'delta_e_map')
+    single, p4, t4 = _de_batched(pred, target, 'delta_e_map')
+    _, dmap, _ = _delta_e_launch(p4, t4, None, k, True, False, 'delta_e_map')
+    return dmap[0] if single else dmap
 
 
 # ---- device: pyramids -------------------------------------------------------------------------------------------------

@@ -11,7 +11,8 @@ training pass (gfused.py) with frozen weights: its backward returns the style an
 (hg_noise_grad, include/hg_nets.h) and launches no weight-gradient convolution.  With latent_noise the variables are
 the per-layer noise feature maps, fed through GeneratorBlock.forward_(noise1=, noise2=) -- plain autograd, as before.
 
-Not here: the VGG perceptual term (see `project`), face_preprocessing, command-line front ends and file I/O.  The caller
+Not here: the VGG perceptual term (see `project`; the weight-free perceptual colour term in its place is the CIE colour
+difference, `delta_e_weight`), face_preprocessing, command-line front ends and file I/O.  The caller
 post-processes `recolor`'s output with post.pyramid_upsampling / post.color_transfer_mkl as the reference's scripts do.
 """
 import torch
@@ -40,7 +41,8 @@ def _render(GAN, styles, h_w, in_noise=None, noise1_list=None, noise2_list=None)
 
 
 def project(GAN, image, steps=1000, lr=0.1, pixel_loss='L1', pixel_loss_weight=1.0, optimize_noise=True, latent_noise=False,
-            noise_reg_weight=0.0, style_reg_weight=0.0, hist_block=None, seed=None, vgg_loss_weight=0.0, hist=None):
+            noise_reg_weight=0.0, style_reg_weight=0.0, hist_block=None, seed=None, vgg_loss_weight=0.0, hist=None,
+            delta_e_weight=0.0, delta_e_kind='2000'):
     """Adam on [styles] (+ the noise) against the frozen SE / HE / GE of `GAN` until GE reproduces `image`.
 
     image: (B, 3, S, S) in [0, 1] on the generator's device.  hist_block: the histogram module that gives the image's own
@@ -49,7 +51,11 @@ def project(GAN, image, steps=1000, lr=0.1, pixel_loss='L1', pixel_loss_weight=1
     styles alone.  seed: of the draw of the latent and the noise image (None: the global generator).
 
     Per step (:466-504):  pixel_loss_weight * (L1 | L2)(image, rgb) + noise_reg_weight * mean(noise)^2 (latent_noise: the
-    sum over both maps of a layer, averaged over the layers) + style_reg_weight * mean(styles)^2 / rows.
+    sum over both maps of a layer, averaged over the layers) + style_reg_weight * mean(styles)^2 / rows
+    + delta_e_weight * mean_b(post.delta_e(rgb, image, delta_e_kind)) when delta_e_weight is not 0: the CIE colour difference
+    ('2000': CIEDE2000, '76': dE76) as the perceptual colour term, where the reference has its VGG loss.  dE is in Lab units --
+    a few units for a fair reproduction, against a pixel term of a few hundredths -- so a useful delta_e_weight is around 1e-2
+    of pixel_loss_weight.  With the default 0 nothing of it is launched.
 
     Returns (data, losses, rgb): the dict the reference pickles -- {'styles', 'in_noise'} or {'styles', 'noise1_list',
     'noise2_list'} --, the loss of every step (floats) and the image rendered from `data`, which
@@ -60,6 +66,9 @@ def project(GAN, image, steps=1000, lr=0.1, pixel_loss='L1', pixel_loss_weight=1
             'the reference tree (torchvision downloads them), and a perceptual loss on random weights verifies nothing')
     if pixel_loss not in ('L1', 'L2'):
         raise ValueError('pixel loss should be either L1 or L2')
+    if delta_e_weight:
+        from . import post
+        delta_e_kind = post.delta_e_kind(delta_e_kind, 'project')          # ValueError before a device is touched
     if hist is None and hist_block is None:
         raise ValueError('project: give the histogram block (hist_block) or the image\'s histogram (hist)')
     GE = GAN.GE
@@ -95,6 +104,8 @@ def project(GAN, image, steps=1000, lr=0.1, pixel_loss='L1', pixel_loss_weight=1
         rgb = _render(GAN, styles, h_w, in_noise, noise1_list, noise2_list)
         rec = torch.mean(torch.abs(image - rgb)) if pixel_loss == 'L1' else F.mse_loss(image, rgb)
         loss = pixel_loss_weight * rec
+        if delta_e_weight:
+            loss = loss + delta_e_weight * post.delta_e(rgb, image, delta_e_kind).mean()
         if optimize_noise and latent_noise:
             reg = sum(n1.mean() ** 2 + n2.mean() ** 2 for n1, n2 in zip(noise1_list, noise2_list))
             loss = loss + noise_reg_weight * reg / len(noise1_list)

@@ -14,6 +14,9 @@
  *   hg_f32_to_u8_hwc          fp32 planar -> uint8 HWC, clamp(x*255 + 0.5, 0, 255) truncated (torchvision save_image)
  *   hg_srgb_to_lab            sRGB -> normalised CIE Lab (L/100, (a+128)/255, (b+128)/255): what LabHistBlock bins, for the
  *   hg_lab_to_srgb            reference README's "convert loaded images into the CIE LAB space", and its exact inverse
+ *   hg_delta_e                CIE colour difference (dE76, CIEDE2000) of two sRGB images: per-sample mean, map and gradient
+ *                             in one pass (no code of the reference: the perceptual colour term of a projection, and the dE
+ *                             reported for recolourings)
  *
  * Conventions as in hg_hist.h: return 0 / negative HG_E* / positive hipError_t; device pointers unless stated; fp32;
  * enqueue on `stream`; never allocate or synchronise; nothing is launched for invalid arguments.  Planar images are
@@ -116,6 +119,47 @@ int hg_srgb_to_lab(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int
                    int32_t H, int32_t W, void *stream);
 int hg_lab_to_srgb(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_t xs_w, float *out, int32_t B,
                    int32_t H, int32_t W, void *stream);
+
+/* CIE colour difference between two sRGB images as a fused loss and metric (since version 110): the per-sample weighted
+ * mean of dE, optionally the per-pixel dE and the gradient of the mean with respect to the first image, in one pass.
+ *
+ * Per pixel both images go through the chain of hg_srgb_to_lab above in fp64, on the fp32 inputs clamped to [0, 1], WITHOUT
+ * the rounding to fp32 and without the 8-bit normalisation: L = 116 f(Y) - 16, a = 500 (f(X) - f(Y)), b = 200 (f(Y) - f(Z)).
+ * Index 1 is the first image x1 (`pred`), index 2 the second x2 (`target`).
+ *   kind = 76:    dE = sqrt(dL^2 + da^2 + db^2)
+ *   kind = 2000:  CIEDE2000 (Sharma, Wu, Dalal 2005; kL = kC = kH = 1), angles in degrees:
+ *     C_i = sqrt(a_i^2 + b_i^2), Cm = (C_1 + C_2) / 2
+ *     G = (1 - sqrt(Cm^7 / (Cm^7 + 25^7))) / 2, a'_i = (1 + G) a_i, C'_i = sqrt(a'_i^2 + b_i^2)
+ *     h'_i = atan2(b_i, a'_i) mapped into [0, 360), and 0 when C'_i = 0
+ *     dh' = h'_2 - h'_1 brought into (-180, 180] by -+360; 0 when C'_1 C'_2 = 0
+ *     dL' = L_2 - L_1, dC' = C'_2 - C'_1, dH' = 2 sqrt(C'_1 C'_2) sin(dh' / 2)
+ *     Lm = (L_1 + L_2) / 2, Cm' = (C'_1 + C'_2) / 2
+ *     hm' = (h'_1 + h'_2) / 2 when |h'_1 - h'_2| <= 180; otherwise (h'_1 + h'_2 + 360) / 2 when the sum is < 360, else
+ *           (h'_1 + h'_2 - 360) / 2; when C'_1 C'_2 = 0, hm' = h'_1 + h'_2
+ *     T = 1 - 0.17 cos(hm' - 30) + 0.24 cos(2 hm') + 0.32 cos(3 hm' + 6) - 0.20 cos(4 hm' - 63)
+ *     dtheta = 30 exp(-((hm' - 275) / 25)^2), R_C = 2 sqrt(Cm'^7 / (Cm'^7 + 25^7))
+ *     S_L = 1 + 0.015 (Lm - 50)^2 / sqrt(20 + (Lm - 50)^2), S_C = 1 + 0.045 Cm', S_H = 1 + 0.015 Cm' T
+ *     R_T = -sin(2 dtheta) R_C
+ *     dE = sqrt((dL'/S_L)^2 + (dC'/S_C)^2 + (dH'/S_H)^2 + R_T (dC'/S_C) (dH'/S_H))
+ * Per sample b, with the optional map w (clamped to [0, 1] like hg_hist_params.weight; NULL = 1):
+ *   mean[b] = sum_n w_n dE_n / sum_n w_n, and 0 when sum w = 0; summed in fp64 in a fixed order, rounded once.
+ *   map[b, n] = dE_n (not weighted), rounded once.
+ *   grad[b, c, n] = d mean[b] / d x1[b, c, n]: the partials of dE with respect to (L_1, a_1, b_1) pulled back through the
+ *     Jacobian of the chain in fp64 and rounded once.  It is 0 for a component outside [0, 1] (the clamp's mask is
+ *     inclusive, as aten's clamp backward).  A square root whose argument is 0 (dE = 0, C_i = 0, C'_i = 0) has slope 0, and
+ *     so has atan2 at the origin; at a branch of dh' or hm' the slope is that of the branch the forward takes.  Hence grad
+ *     is finite for every input, and x1 == x2 gives mean = 0 and grad = 0 (exactly: a pixel whose clamped components equal
+ *     the other image's has dE = 0 and slope 0 by construction).  There is no gradient for x2 or w.
+ * x1, x2: fp32 (B, 3, H, W), weight: fp32 (B, H, W), each with its own element strides; mean (B), map (B, H, W) and grad
+ * (B, 3, H, W) are contiguous; map and grad may be NULL.  mean has the same bits whichever of map and grad are requested,
+ * and a map of ones gives the bits of NULL.  workspace: hg_delta_e_workspace_bytes(B, H, W) bytes, 8-byte aligned.
+ * HG_EINVAL before any launch for a NULL x1, x2, mean or workspace, a size < 1, B > 65535, more than 2^31 - 1 blocks of 256
+ * pixels per image, a kind other than 76 and 2000, or a workspace that is too small (the query returns 0 for refused sizes). */
+size_t hg_delta_e_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int hg_delta_e(const float *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_t s1_w, const float *x2, int64_t s2_b,
+               int64_t s2_c, int64_t s2_h, int64_t s2_w, const float *weight, int64_t ws_b, int64_t ws_h, int64_t ws_w,
+               int32_t kind, float *mean, float *map, float *grad, int32_t B, int32_t H, int32_t W, void *workspace,
+               size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
