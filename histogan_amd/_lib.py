@@ -258,6 +258,16 @@ def _load():
     lib.hg_delta_e.restype = ctypes.c_int
     lib.hg_delta_e.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, vp, i64, i64, i64, i32, vp, vp, vp, i32, i32, i32,
                                vp, sz, vp]
+    lib.hg_ssim_tile.restype = ctypes.c_int
+    lib.hg_ssim_tile.argtypes = []
+    lib.hg_ssim_finish_threads.restype = ctypes.c_int
+    lib.hg_ssim_finish_threads.argtypes = []
+    lib.hg_ssim_workspace_bytes.restype = sz
+    lib.hg_ssim_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.hg_ssim_fwd.restype = ctypes.c_int
+    lib.hg_ssim_fwd.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
+    lib.hg_ssim_bwd.restype = ctypes.c_int
+    lib.hg_ssim_bwd.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, i32, i32, i32, vp]
     return lib
 
 
@@ -281,7 +291,8 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
            'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd', 'hg_noise_grad',
            'hg_resize_axis', 'hg_pyr_down', 'hg_pyr_up_add', 'hg_color_moments_workspace_bytes', 'hg_color_moments',
            'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc', 'hg_bgu_normal_workspace_bytes', 'hg_bgu_normal',
-           'hg_bgu_slice', 'hg_srgb_to_lab', 'hg_lab_to_srgb', 'hg_delta_e_workspace_bytes', 'hg_delta_e')
+           'hg_bgu_slice', 'hg_srgb_to_lab', 'hg_lab_to_srgb', 'hg_delta_e_workspace_bytes', 'hg_delta_e',
+           'hg_ssim_tile', 'hg_ssim_finish_threads', 'hg_ssim_workspace_bytes', 'hg_ssim_fwd', 'hg_ssim_bwd')
 
 
 class HgError(RuntimeError):

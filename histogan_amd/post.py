@@ -12,7 +12,8 @@ utils/pyramid_upsampling.py, utils/color_transfer_MKL.py) convert to and from th
 
 Also here, with no counterpart in the reference: the sRGB <-> CIE Lab conversions, and the CIE colour difference between
 two sRGB images (delta_e, delta_e_map: dE76 and CIEDE2000) as a differentiable loss and as the metric reported for
-recolourings.
+recolourings; and SSIM / MS-SSIM of the lightness plane or of the components (ssim, ssim_map, ms_ssim), the structure term
+and the number reported for "structure preserved under recolouring".
 """
 import ctypes
 from functools import lru_cache
@@ -305,6 +306,167 @@ def delta_e_map(pred, target, kind='2000'):
     single, p4, t4 = _de_batched(pred, target, 'delta_e_map')
     _, dmap, _ = _delta_e_launch(p4, t4, None, k, True, False, 'delta_e_map')
     return dmap[0] if single else dmap
+
+
+# ---- device: SSIM and MS-SSIM (hg_ssim_fwd, hg_ssim_bwd) --------------------------------------------------------------
+SSIM_TILE = 32                    # hg_ssim_tile(): a workgroup's tile of the map (forward) and of the input (backward)
+SSIM_FINISH_THREADS = 256         # hg_ssim_finish_threads(): thread t of a sample's finish block sums partials t, t + 256, ...
+SSIM_WINDOW = 11
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+MS_SSIM_MIN_SIZE = SSIM_WINDOW << (len(MS_SSIM_WEIGHTS) - 1)          # 176 -> 88 -> 44 -> 22 -> 11
+_SSIM_MODES = {'L': 0, 'rgb': 1}                  # HG_SSIM_L, HG_SSIM_RGB; + 2: HG_SSIM_PLANES1, HG_SSIM_PLANES3
+
+
+def ssim_channels(channels, what='ssim'):
+    """'L' | 'rgb' -> the C ABI's mode; anything else raises ValueError (no HIP call is made)."""
+    if not isinstance(channels, str) or channels not in _SSIM_MODES:
+        raise ValueError(f"{what}: channels must be 'L' (the lightness plane) or 'rgb' (the three components), not {channels!r}")
+    return _SSIM_MODES[channels]
+
+
+def _ssim_images(pred, target, channels, what, min_size):
+    """Every refusal of ssim / ssim_map / ms_ssim, before any HIP call: (mode, single, pred (B, 3, H, W), target)."""
+    mode = ssim_channels(channels, what)
+    for t, name in ((pred, 'pred'), (target, 'target')):
+        if not torch.is_tensor(t) or t.dim() not in (3, 4) or t.shape[-3] != 3 or not t.is_floating_point():
+            got = f'{t.dtype} {tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f'{what}: {name} must be a float (B, 3, H, W) or (3, H, W) tensor, got {got}')
+    single = pred.dim() == 3
+    p4, t4 = (pred.unsqueeze(0) if single else pred), (target.unsqueeze(0) if target.dim() == 3 else target)
+    if p4.shape != t4.shape or p4.device != t4.device:
+        raise ValueError(f'{what}: pred and target must have one shape and device, got {tuple(p4.shape)} on {p4.device} and '
+                         f'{tuple(t4.shape)} on {t4.device}')
+    B, _, H, W = p4.shape
+    if min(H, W) < min_size:
+        raise ValueError(f'{what}: images must be at least {min_size} x {min_size}, got {H} x {W}')
+    if not 1 <= B <= 65535:
+        raise ValueError(f'{what}: the batch must be 1 .. 65535, got {B}')
+    need_gpu(p4, what, _FOUND)
+    return mode, single, p4, t4
+
+
+def _ssim_f32(t):
+    t = t.detach()
+    return t if t.dtype == torch.float32 else t.float()
+
+
+def _ssim_fwd(x1, x2, mode, want_map=False, want_pool=False):
+    """One hg_ssim_fwd call: x1, x2 fp32 (B, 3, H, W) images (mode 0, 1) or contiguous fp64 (B, planes, H, W) planes (mode 2,
+    3) -> (means fp64 (B, 2) = (mean ssim, mean cs), map fp32 (B, H-10, W-10) or None, (pooled planes of x1, of x2) or None)."""
+    B, _, H, W = x1.shape
+    planes = 3 if mode in (1, 3) else 1
+    dev = x1.device
+    with on_device(dev):
+        means = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        smap = torch.empty((B, H - 10, W - 10), dtype=torch.float32, device=dev) if want_map else None
+        pools = tuple(torch.empty((B, planes, H // 2, W // 2), dtype=torch.float64, device=dev) for _ in range(2)) if want_pool else None
+        nb = lib.hg_ssim_workspace_bytes(B, H, W)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
+        check(lib.hg_ssim_fwd(x1.data_ptr(), *x1.stride(), x2.data_ptr(), *x2.stride(), mode, means.data_ptr(),
+                              None if smap is None else smap.data_ptr(), None if pools is None else pools[0].data_ptr(),
+                              None if pools is None else pools[1].data_ptr(), B, H, W, ws.data_ptr(), nb, raw_stream(dev)),
+              'hg_ssim_fwd')
+    return means, smap, pools
+
+
+def _ssim_bwd(x1, x2, mode, coef, coarse=None):
+    """One hg_ssim_bwd call: the gradient of sum_b (coef[b, 0] mean_ssim[b] + coef[b, 1] mean_cs[b]) -- coef fp64 (B, 2) on
+    the device -- plus the pooled planes' gradient `coarse`: fp32 (B, 3, H, W) for the images, fp64 for planes."""
+    B, _, H, W = x1.shape
+    dev = x1.device
+    with on_device(dev):
+        grad = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if mode < 2 else torch.empty_like(x1)
+        check(lib.hg_ssim_bwd(x1.data_ptr(), *x1.stride(), x2.data_ptr(), *x2.stride(), mode, coef.data_ptr(),
+                              None if coarse is None else coarse.data_ptr(), grad.data_ptr(), B, H, W, raw_stream(dev)), 'hg_ssim_bwd')
+    return grad
+
+
+class SsimFunction(torch.autograd.Function):
+    """Mean ssim per sample.  Only the images are kept: the backward kernel recomputes the moments, with the upstream vector
+    as its coefficients, so the gradient is rounded once.  target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mode):
+        x1, x2 = _ssim_f32(pred), _ssim_f32(target)
+        means, _, _ = _ssim_fwd(x1, x2, mode)
+        ctx.mode, ctx.dtype = mode, pred.dtype
+        ctx.save_for_backward(x1, x2)
+        return means[:, 0].float()
+
+    @staticmethod
+    def backward(ctx, up):
+        x1, x2 = ctx.saved_tensors
+        u = up.double()
+        return _ssim_bwd(x1, x2, ctx.mode, torch.stack((u, torch.zeros_like(u)), dim=1)).to(ctx.dtype), None, None
+
+
+class MsSsimFunction(torch.autograd.Function):
+    """ms = prod_{s<5} max(mean cs_s, 0)^w_s * max(mean ssim_5, 0)^w_5: five forward launches, each writing the next level's
+    pooled fp64 planes, and five backward launches from the coarsest level up; the per-level coefficients come from the fp64
+    means by torch ops on the device.  Kept between the two: the images, the pooled planes and the means."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mode):
+        levels = len(MS_SSIM_WEIGHTS)
+        planes = [(_ssim_f32(pred), _ssim_f32(target))]
+        means = []
+        for s in range(levels):
+            m, _, pools = _ssim_fwd(*planes[s], mode if s == 0 else mode + 2, want_pool=s + 1 < levels)
+            means.append(m)
+            if pools is not None:
+                planes.append(pools)
+        means = torch.stack(means)                                              # (levels, B, 2)
+        w = torch.tensor(MS_SSIM_WEIGHTS, dtype=torch.float64, device=means.device)[:, None]
+        base = torch.cat((means[:-1, :, 1], means[-1:, :, 0]))                  # cs of levels 1-4, ssim of level 5
+        ms = torch.prod(base.clamp(min=0.0) ** w, dim=0)
+        ctx.mode, ctx.dtype = mode, pred.dtype
+        ctx.save_for_backward(base, ms, w, *[t for pair in planes for t in pair])
+        return ms.float()
+
+    @staticmethod
+    def backward(ctx, up):
+        base, ms, w, *flat = ctx.saved_tensors
+        levels = len(MS_SSIM_WEIGHTS)
+        pos = base > 0                                                          # slope 0 at the clamp
+        slope = torch.where(pos, w * ms / torch.where(pos, base, torch.ones_like(base)), torch.zeros_like(base)) * up.double()
+        zero = torch.zeros_like(slope[0])
+        g = None
+        for s in reversed(range(levels)):
+            coef = torch.stack((slope[s], zero) if s == levels - 1 else (zero, slope[s]), dim=1)
+            g = _ssim_bwd(flat[2 * s], flat[2 * s + 1], ctx.mode if s == 0 else ctx.mode + 2, coef, g)
+        return g.to(ctx.dtype), None, None
+
+
+def ssim(pred, target, channels='L'):
+    """SSIM between two sRGB images as a loss term: fp32 (B,) per-sample means of the ssim map (a 0-dim tensor for (3, H, W)
+    inputs); 1 for equal images.  pred, target: float (B, 3, H, W) or (3, H, W), any strides, clamped to [0, 1] as they are
+    read.  channels: 'L' -- one plane, CIE L* / 100 by the chain of srgb_to_lab in fp64 without its rounding -- or 'rgb' -- the
+    three components, averaged.  11-tap Gaussian window (sigma 1.5), valid positions only, C1 = 1e-4, C2 = 9e-4;
+    include/hg_post.h (hg_ssim_fwd) states every formula.  H, W >= 11.
+
+    Differentiable with respect to `pred` (finite everywhere; exactly zero for equal images and for components outside
+    [0, 1]); target gets no gradient."""
+    mode, single, p4, t4 = _ssim_images(pred, target, channels, 'ssim', SSIM_WINDOW)
+    out = SsimFunction.apply(p4, t4, mode)
+    return out[0] if single else out
+
+
+def ssim_map(pred, target, channels='L'):
+    """The ssim map of `ssim`: fp32 (B, H - 10, W - 10), or (H - 10, W - 10) for (3, H, W) inputs; with 'rgb' the mean over the
+    three planes.  Not differentiable: the result carries no graph whatever the inputs require."""
+    mode, single, p4, t4 = _ssim_images(pred, target, channels, 'ssim_map', SSIM_WINDOW)
+    _, smap, _ = _ssim_fwd(_ssim_f32(p4), _ssim_f32(t4), mode, want_map=True)
+    return smap[0] if single else smap
+
+
+def ms_ssim(pred, target, channels='L'):
+    """Multi-scale SSIM (Wang, Simoncelli, Bovik 2003): fp32 (B,) (0-dim for (3, H, W) inputs).  Five levels with the weights
+    MS_SSIM_WEIGHTS; between levels the PLANES of `ssim` are averaged over 2 x 2 blocks in fp64 (an odd trailing row or column
+    is dropped); ms = prod_{s<5} max(mean cs_s, 0)^w_s * max(mean ssim_5, 0)^w_5 with slope 0 at the clamp.  min(H, W) >= 176.
+    Differentiable with respect to `pred`."""
+    mode, single, p4, t4 = _ssim_images(pred, target, channels, 'ms_ssim', MS_SSIM_MIN_SIZE)
+    out = MsSsimFunction.apply(p4, t4, mode)
+    return out[0] if single else out
 
 
 # ---- device: pyramids -------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ training pass (gfused.py) with frozen weights: its backward returns the style an
 the per-layer noise feature maps, fed through GeneratorBlock.forward_(noise1=, noise2=) -- plain autograd, as before.
 
 Not here: the VGG perceptual term (see `project`; the weight-free perceptual colour term in its place is the CIE colour
-difference, `delta_e_weight`), face_preprocessing, command-line front ends and file I/O.  The caller
+difference, `delta_e_weight`, and SSIM / MS-SSIM of the lightness plane, `ssim_weight`), face_preprocessing, command-line front ends and file I/O.  The caller
 post-processes `recolor`'s output with post.pyramid_upsampling / post.color_transfer_mkl as the reference's scripts do.
 """
 import torch
@@ -42,7 +42,7 @@ def _render(GAN, styles, h_w, in_noise=None, noise1_list=None, noise2_list=None)
 
 def project(GAN, image, steps=1000, lr=0.1, pixel_loss='L1', pixel_loss_weight=1.0, optimize_noise=True, latent_noise=False,
             noise_reg_weight=0.0, style_reg_weight=0.0, hist_block=None, seed=None, vgg_loss_weight=0.0, hist=None,
-            delta_e_weight=0.0, delta_e_kind='2000'):
+            delta_e_weight=0.0, delta_e_kind='2000', ssim_weight=0.0, ssim_kind='ssim'):
     """Adam on [styles] (+ the noise) against the frozen SE / HE / GE of `GAN` until GE reproduces `image`.
 
     image: (B, 3, S, S) in [0, 1] on the generator's device.  hist_block: the histogram module that gives the image's own
@@ -56,6 +56,9 @@ def project(GAN, image, steps=1000, lr=0.1, pixel_loss='L1', pixel_loss_weight=1
     ('2000': CIEDE2000, '76': dE76) as the perceptual colour term, where the reference has its VGG loss.  dE is in Lab units --
     a few units for a fair reproduction, against a pixel term of a few hundredths -- so a useful delta_e_weight is around 1e-2
     of pixel_loss_weight.  With the default 0 nothing of it is launched.
+    + ssim_weight * mean_b(1 - post.ssim(rgb, image)) when ssim_weight is not 0: the structure of the lightness plane,
+    independent of its colour; ssim_kind='ms-ssim' takes post.ms_ssim instead and needs image_size >= 176.  With the default 0
+    nothing of it is launched.
 
     Returns (data, losses, rgb): the dict the reference pickles -- {'styles', 'in_noise'} or {'styles', 'noise1_list',
     'noise2_list'} --, the loss of every step (floats) and the image rendered from `data`, which
@@ -69,6 +72,13 @@ def project(GAN, image, steps=1000, lr=0.1, pixel_loss='L1', pixel_loss_weight=1
     if delta_e_weight:
         from . import post
         delta_e_kind = post.delta_e_kind(delta_e_kind, 'project')          # ValueError before a device is touched
+    if ssim_weight:
+        from . import post
+        if ssim_kind not in ('ssim', 'ms-ssim'):                            # ValueError before a device is touched
+            raise ValueError(f"project: ssim_kind must be 'ssim' or 'ms-ssim', not {ssim_kind!r}")
+        if ssim_kind == 'ms-ssim' and GAN.GE.image_size < post.MS_SSIM_MIN_SIZE:
+            raise ValueError(f'project: ssim_kind=\'ms-ssim\' needs image_size >= {post.MS_SSIM_MIN_SIZE}, got {GAN.GE.image_size}')
+        ssim_fn = post.ms_ssim if ssim_kind == 'ms-ssim' else post.ssim
     if hist is None and hist_block is None:
         raise ValueError('project: give the histogram block (hist_block) or the image\'s histogram (hist)')
     GE = GAN.GE
@@ -106,6 +116,8 @@ def project(GAN, image, steps=1000, lr=0.1, pixel_loss='L1', pixel_loss_weight=1
         loss = pixel_loss_weight * rec
         if delta_e_weight:
             loss = loss + delta_e_weight * post.delta_e(rgb, image, delta_e_kind).mean()
+        if ssim_weight:
+            loss = loss + ssim_weight * (1.0 - ssim_fn(rgb, image)).mean()
         if optimize_noise and latent_noise:
             reg = sum(n1.mean() ** 2 + n2.mean() ** 2 for n1, n2 in zip(noise1_list, noise2_list))
             loss = loss + noise_reg_weight * reg / len(noise1_list)

@@ -26,7 +26,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import ddp, reops
+from . import ddp, post, reops
 from .conv import enable_pack_cache, weights_changed
 from .hist import hellinger_loss
 from .nets import Discriminator, HistVectorizer
@@ -67,7 +67,8 @@ def sobel_op(x, dir=0, kernel=None):
 
 
 class reconstruction_loss(object):
-    """'L1' | '1st gradient' (Sobel magnitude) | '2nd gradient' (Laplacian); reference :279-326."""
+    """'L1' | '1st gradient' (Sobel magnitude) | '2nd gradient' (Laplacian); reference :279-326.  'SSIM' (no counterpart in
+    the reference): mean_b(1 - post.ssim) of the lightness planes, structure preserved whatever the colours do."""
 
     def __init__(self, loss):
         self.loss = loss
@@ -82,6 +83,9 @@ class reconstruction_loss(object):
         if self.loss == '2nd gradient':
             # the stencil is linear: one pass over the difference image
             return torch.mean(torch.abs(laplacian_op(input - target)))
+        if self.loss == 'SSIM':
+            # the trainer passes the generated image second, and post.ssim differentiates its first argument
+            return torch.mean(1.0 - post.ssim(target[:, :3], input[:, :3]))
         return None
 
 
@@ -185,6 +189,8 @@ class recoloringTrainer():
             self.rec_loss_func = reconstruction_loss('1st gradient')
         elif self.rec_loss == 'laplacian':
             self.rec_loss_func = reconstruction_loss('2nd gradient')
+        elif self.rec_loss == 'ssim':
+            self.rec_loss_func = reconstruction_loss('SSIM')
         else:
             raise Exception('Unknown reconstruction losst!')
         self.name = name

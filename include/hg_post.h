@@ -17,6 +17,9 @@
  *   hg_delta_e                CIE colour difference (dE76, CIEDE2000) of two sRGB images: per-sample mean, map and gradient
  *                             in one pass (no code of the reference: the perceptual colour term of a projection, and the dE
  *                             reported for recolourings)
+ *   hg_ssim_fwd, hg_ssim_bwd  SSIM of two images (of their L* plane or of their components): per-sample means of ssim and cs,
+ *                             map, pooled planes for the next MS-SSIM level; gradient by a second tiled pass (no code of the
+ *                             reference: the structure term of a projection and of ReHistoGAN's reconstruction loss)
  *
  * Conventions as in hg_hist.h: return 0 / negative HG_E* / positive hipError_t; device pointers unless stated; fp32;
  * enqueue on `stream`; never allocate or synchronise; nothing is launched for invalid arguments.  Planar images are
@@ -160,6 +163,66 @@ int hg_delta_e(const float *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_
                int64_t s2_c, int64_t s2_h, int64_t s2_w, const float *weight, int64_t ws_b, int64_t ws_h, int64_t ws_w,
                int32_t kind, float *mean, float *map, float *grad, int32_t B, int32_t H, int32_t W, void *workspace,
                size_t workspace_bytes, void *stream);
+
+/* SSIM (and, level by level, MS-SSIM) of two images as a fused loss and metric (since version 111): per sample the mean of
+ * ssim and the mean of cs, optionally the ssim map, and in a second call the gradient with respect to the first image.
+ *
+ * Planes.  mode HG_SSIM_L: x1, x2 are fp32 (B, 3, H, W) sRGB images with their own element strides, clamped to [0, 1] as they
+ * are read; one plane, P = L / 100 with L = 116 f(Y) - 16 from the chain of hg_srgb_to_lab above in fp64, unrounded.
+ * HG_SSIM_RGB: the same images, three planes, the clamped components.  HG_SSIM_PLANES1 / HG_SSIM_PLANES3: x1, x2 are
+ * contiguous fp64 (B, 1 | 3, H, W) planes, taken as they are (the strides are ignored): the pooled planes of a coarser
+ * MS-SSIM level.  x is the plane of x1 (`pred`), y that of x2 (`target`).
+ * Window.  11 taps g_k = exp(-(k - 5)^2 / 4.5) / sum_k, fp64; the 2-D window is the outer product; only valid positions
+ * count, so the map is (H - 10) x (W - 10) and H, W >= 11.
+ * Per position, with the window means mx, my, exx, eyy, exy of x, y, x^2, y^2, x y:
+ *   sxx = exx - mx^2, syy = eyy - my^2, sxy = exy - mx my;  C1 = 1e-4, C2 = 9e-4 (data range 1)
+ *   A2 = mx^2 + my^2 + C1, B2 = sxx + syy + C2
+ *   l = (2 mx my + C1) / A2,  cs = (2 sxy + C2) / B2,  ssim = l cs
+ * hg_ssim_fwd:
+ *   means[b] = (mean ssim, mean cs) over the N = (H - 10)(W - 10) * planes positions of sample b, fp64 (B, 2): block partials
+ *     summed in a fixed order; the same bits whichever optional outputs are requested.
+ *   map (optional): fp32 (B, H - 10, W - 10), ssim averaged over the planes in fp64, rounded once.
+ *   pool1, pool2 (optional, both or neither): the planes of x1 and x2 averaged over 2 x 2 blocks, fp64 (B, planes, H/2, W/2)
+ *     contiguous, an odd trailing row or column dropped (F.avg_pool2d(., 2)): the input of the next MS-SSIM level as
+ *     HG_SSIM_PLANES*.  They stay fp64: a rounding to fp32 in front of exx - mx^2 would cost what the fp64 evaluation buys.
+ *   workspace: hg_ssim_workspace_bytes(B, H, W) bytes, 8-byte aligned (the block partials).
+ * hg_ssim_bwd: the gradient of  sum_b (a_b mean_ssim[b] + c_b mean_cs[b])  with respect to the planes of x1, coef = fp64
+ *   (B, 2) = (a_b, c_b) in device memory.  With adj = the adjoint of the valid blur (zero-padded full correlation with g):
+ *     dP = adj(M) + 2 x adj(Exx) + y adj(Exy)
+ *     Exx = -(a l + c)(2 sxy + C2) / B2^2,  Exy = 2 (a l + c) / B2,
+ *     M = a cs dl/dmx - 2 mx Exx - my Exy,  dl/dmx = 2 (my - l mx) / A2,      all three divided by N
+ *   coarse (optional): fp64 (B, planes, H/2, W/2), the gradient of the pooled planes: 0.25 coarse[i/2, j/2] is added at every
+ *     pixel a pooled pixel covers.
+ *   grad: HG_SSIM_PLANES*: fp64 (B, planes, H, W), dP.  HG_SSIM_RGB: fp32 (B, 3, H, W), dP rounded once, 0 for a component
+ *     outside [0, 1] (the clamp's inclusive mask).  HG_SSIM_L: fp32 (B, 3, H, W), dP / 100 pulled back through the Jacobian of
+ *     the chain (as hg_delta_e), rounded once, with the same mask.
+ *   Nothing is kept between the two calls: the moments are recomputed.  Denominators are at least C1 and C2, so the gradient
+ *   is finite for every input; equal planes give ssim = 1 and gradient 0 exactly (l and cs are evaluated as 1 minus
+ *   what separates them from 1 -- l = 1 - (mx - my)^2 / A2, cs = 1 - ((sxx - sxy) + (syy - sxy)) / B2 -- and the gradient's
+ *   cancelling sums as differences that vanish term by term, so no contraction into fma's can leave a residue; in HG_SSIM_L
+ *   equal clamped pixels give equal plane values by construction).  There is no
+ *   gradient for x2.
+ * MS-SSIM (composed by the caller, histogan_amd/post.py): five levels s, weights (0.0448, 0.2856, 0.3001, 0.2363, 0.1333),
+ *   ms = prod_{s<5} max(mean cs_s, 0)^w_s * max(mean ssim_5, 0)^w_5 with slope 0 at the clamp; min(H, W) >= 176.
+ * hg_ssim_tile(): the edge of a workgroup's tile (of the map in hg_ssim_fwd, of the input in hg_ssim_bwd);
+ * hg_ssim_finish_threads(): the threads of the block that sums a sample's partials.
+ * HG_EINVAL before any launch for a NULL x1, x2, means / coef / grad or workspace, only one of pool1 and pool2, H or W < 11,
+ * B < 1 or > 65535, an unknown mode, or a workspace that is too small (the query returns 0 for refused sizes). */
+#define HG_SSIM_L 0
+#define HG_SSIM_RGB 1
+#define HG_SSIM_PLANES1 2
+#define HG_SSIM_PLANES3 3
+#define HG_SSIM_TILE 32
+#define HG_SSIM_FINISH_THREADS 256
+int hg_ssim_tile(void);
+int hg_ssim_finish_threads(void);
+size_t hg_ssim_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int hg_ssim_fwd(const void *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_t s1_w, const void *x2, int64_t s2_b,
+                int64_t s2_c, int64_t s2_h, int64_t s2_w, int32_t mode, double *means, float *map, double *pool1,
+                double *pool2, int32_t B, int32_t H, int32_t W, void *workspace, size_t workspace_bytes, void *stream);
+int hg_ssim_bwd(const void *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_t s1_w, const void *x2, int64_t s2_b,
+                int64_t s2_c, int64_t s2_h, int64_t s2_w, int32_t mode, const double *coef, const double *coarse, void *grad,
+                int32_t B, int32_t H, int32_t W, void *stream);
 
 #ifdef __cplusplus
 }
