@@ -65,6 +65,28 @@ class HgConvRoute(ctypes.Structure):
                [('blocks', ctypes.c_int64), ('slab_bytes', ctypes.c_size_t)]
 
 
+class HgWinoQuery(ctypes.Structure):
+    """struct hg_wino_query (include/hg_wino.h): the call hg_wino_route / hg_wino_wgrad_route is asked about."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'B', 'K', 'N', 'H', 'W', 'fe', 'have_workspace')] + \
+               [('workspace_bytes', ctypes.c_size_t)]
+
+
+class HgWinoRoute(ctypes.Structure):
+    """struct hg_wino_plan (include/hg_wino.h): what hg_wino_route fills in."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'variant', 'fe', 'nblk', 'nch', 'lTW', 'lTH', 'lNI', 'bt_x', 'bt_y',
+                                              'blocks', 'ksplit', 'chunks_per_split', 'last_split_chunks', 'empty_splits', 'xcd',
+                                              'grid', 'persistent', 'reduce', 'cus', 'supported', 'reserved')] + \
+               [('slab_bytes', ctypes.c_size_t)]
+
+
+class HgWinoWgradRoute(ctypes.Structure):
+    """struct hg_wino_wgrad_plan (include/hg_wino.h): what hg_wino_wgrad_route fills in."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'lPW', 'lPH', 'lPI', 'lcg', 'lrg', 'nchunks', 'ktiles', 'ntiles',
+                                              'splits', 'chunks_per_split', 'last_split_chunks', 'empty_splits', 'reduce_groups',
+                                              'xcd', 'grid', 'persistent', 'cus', 'supported', 'reserved')] + \
+               [('slab_bytes', ctypes.c_size_t)]
+
+
 class GlinLayer(ctypes.Structure):
     """struct hg_glin_layer (include/hg_linear.h)."""
     _fields_ = [('x', ctypes.c_void_p), ('w', ctypes.c_void_p), ('b', ctypes.c_void_p), ('y', ctypes.c_void_p),
@@ -216,6 +238,10 @@ def _load():
     lib.hg_wino_wgrad_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
     lib.hg_wino_wgrad.restype = ctypes.c_int
     lib.hg_wino_wgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]
+    lib.hg_wino_route.restype = ctypes.c_int
+    lib.hg_wino_route.argtypes = [ctypes.POINTER(HgWinoQuery), ctypes.POINTER(HgWinoRoute)]
+    lib.hg_wino_wgrad_route.restype = ctypes.c_int
+    lib.hg_wino_wgrad_route.argtypes = [ctypes.POINTER(HgWinoQuery), ctypes.POINTER(HgWinoWgradRoute)]
     # include/hg_augment.h
     lib.hg_augment_spatial.restype = ctypes.c_int
     lib.hg_augment_spatial.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
@@ -287,7 +313,7 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
            'hg_augment_color', 'hg_grouped_linear_fwd', 'hg_grouped_linear_bwd_input_workspace_bytes',
            'hg_grouped_linear_bwd_input', 'hg_grouped_linear_bwd_params',
            'hg_wino_supported', 'hg_wino_packed_elems', 'hg_wino_pack_weights', 'hg_wino_pack_blocks', 'hg_wino_pack_weights_multi', 'hg_wino_workspace_bytes', 'hg_wino_conv2d',
-           'hg_wino_wgrad_supported', 'hg_wino_wgrad_workspace_bytes', 'hg_wino_wgrad',
+           'hg_wino_wgrad_supported', 'hg_wino_wgrad_workspace_bytes', 'hg_wino_wgrad', 'hg_wino_route', 'hg_wino_wgrad_route',
            'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd', 'hg_noise_grad',
            'hg_resize_axis', 'hg_pyr_down', 'hg_pyr_up_add', 'hg_color_moments_workspace_bytes', 'hg_color_moments',
            'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc', 'hg_bgu_normal_workspace_bytes', 'hg_bgu_normal',
@@ -314,6 +340,29 @@ def conv_route(B, K, N, Hi, Wi, ksize, stride=1, dgrad=False, fe=False, workspac
                     int(workspace_bytes is None or workspace_bytes > 0), unlimited if workspace_bytes is None else workspace_bytes)
     r = HgConvRoute(struct_size=ctypes.sizeof(HgConvRoute))
     check(lib.hg_conv2d_route(ctypes.byref(q), ctypes.byref(r)), 'hg_conv2d_route')
+    return r
+
+
+def _wino_query(B, K, N, H, W, fe, workspace_bytes):
+    unlimited = ctypes.c_size_t(-1).value
+    return HgWinoQuery(ctypes.sizeof(HgWinoQuery), B, K, N, H, W, int(fe), int(workspace_bytes is None or workspace_bytes > 0),
+                       unlimited if workspace_bytes is None else workspace_bytes)
+
+
+def wino_route(B, K, N, H, W, fe=False, workspace_bytes=None):
+    """hg_wino_route: the filled HgWinoRoute of a hg_wino_conv2d call (host only, no launch).  workspace_bytes None: as the
+    workspace query plans (a workspace of any size); 0: no workspace."""
+    q = _wino_query(B, K, N, H, W, fe, workspace_bytes)
+    r = HgWinoRoute(struct_size=ctypes.sizeof(HgWinoRoute))
+    check(lib.hg_wino_route(ctypes.byref(q), ctypes.byref(r)), 'hg_wino_route')
+    return r
+
+
+def wino_wgrad_route(B, K, N, H, W, workspace_bytes=None):
+    """hg_wino_wgrad_route: the filled HgWinoWgradRoute of a hg_wino_wgrad call (host only, no launch)."""
+    q = _wino_query(B, K, N, H, W, False, workspace_bytes)
+    r = HgWinoWgradRoute(struct_size=ctypes.sizeof(HgWinoWgradRoute))
+    check(lib.hg_wino_wgrad_route(ctypes.byref(q), ctypes.byref(r)), 'hg_wino_wgrad_route')
     return r
 
 

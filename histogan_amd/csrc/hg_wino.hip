@@ -834,10 +834,28 @@ inline int variant_of(int N) { return force_variant() >= 0 ? force_variant() : (
 struct WinoPlan {
   int variant, NB, TB, KC, nblk, nch;
   int lTW, lTH, lNI, tiles_w, tiles_h, bt_x, bt_y, groups;
-  int ksplit;
-  long long blocks;   // before the K split
+  int ksplit;           // as launched: the planned split, or 1 where the workspace does not hold its slabs
+  int planned_ksplit;   // for a workspace of any size (hg_wino_workspace_bytes, hg_wino_supported)
+  long long blocks;     // before the K split
+  // the launch (everything hg_wino_conv2d / launch_wino used to decide after the plan) and what hg_wino_route reports
+  int cps, last_chunks, empty_splits;   // chunks per split (as k_wino computes it), of the last split that has any, splits with none
+  int xcd, persistent, reduce, cus;
+  long long grid;
+  size_t slab_bytes, planned_slab_bytes;
 };
-inline bool make_plan(int B, int K, int N, int H, int W, WinoPlan &p) {
+inline int wino_persist() {
+  static const int persist = getenv("HG_WINO_PERSIST") ? atoi(getenv("HG_WINO_PERSIST")) : 1;
+  return persist;
+}
+// The one place that decides a hg_wino_conv2d call: geometry, K split, the short-workspace fallback, block order, grid.
+// have_ws / ws_bytes: the call's workspace (true, SIZE_MAX: "as the workspace query plans").
+//
+// Empty K splits (a split z with z * ceil(nch / ksplit) >= nch): the planner never takes one.  If split ks - 1 of ks is empty,
+// ks - 1 splits have the same chunks per split, no more rounds and a smaller slab term, so t(ks - 1) < t(ks) and ks loses
+// against a candidate the loop has already seen (it needs ks >= 10, so ks - 1 is a split too).  The scan of
+// tests/test_wino_route_cpu.py finds none among 137 376 routes (profiles/wino_route_scan.json).  HG_WINO_KSPLIT can force
+// one (130 chunks in 14 splits of 10): k_wino then runs no chunk for it and stores a zero slab.
+inline bool make_plan(int B, int K, int N, int H, int W, bool have_ws, size_t ws_bytes, WinoPlan &p) {
   if (B <= 0 || K <= 0 || N <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1)) return false;
   p.variant = variant_of(N);
   p.NB = p.variant ? 32 : 64;
@@ -874,15 +892,44 @@ inline bool make_plan(int B, int K, int N, int H, int W, WinoPlan &p) {
     if (ks > 1) t += 4.0 + 0.02 * ks * rounds;   // slab traffic + the reduce launch
     if (t < best_t * 0.97) { best_t = t; best = ks; }
   }
-  p.ksplit = force_ks > 0 ? (force_ks < p.nch ? force_ks : p.nch) : best;
+  p.planned_ksplit = force_ks > 0 ? (force_ks < p.nch ? force_ks : p.nch) : best;
+  const size_t out_bytes = (size_t)B * N * H * W * sizeof(float);
+  p.planned_slab_bytes = p.planned_ksplit > 1 ? p.planned_ksplit * out_bytes : 0;
+  // too little workspace for the slabs (or none): no split, same kernel and tile geometry
+  p.ksplit = p.planned_ksplit > 1 && have_ws && ws_bytes >= p.planned_slab_bytes ? p.planned_ksplit : 1;
+  p.slab_bytes = p.ksplit > 1 ? p.planned_slab_bytes : 0;
+  p.reduce = p.ksplit > 1;
+  p.cps = (p.nch + p.ksplit - 1) / p.ksplit;
+  const int used = (p.nch + p.cps - 1) / p.cps;   // splits that own a chunk
+  p.empty_splits = p.ksplit - used;
+  p.last_chunks = p.nch - (used - 1) * p.cps;
+  // block order: see tile_setup (k_wino)
+  p.xcd = p.nblk > 1 && p.nblk < 8 && (p.blocks / p.nblk) % 8 == 0;
+  p.cus = cus;
+  const long long total = p.blocks * p.ksplit;
+  p.grid = wino_persist() && total > cus ? cus : total;   // (512 threads, ~215 registers: one workgroup per CU)
+  p.persistent = total > p.grid;
   return true;
+}
+inline bool wino_beats_direct(int K, const WinoPlan &p) {
+  // measured against the direct kernel at the C3 shapes (tools/wino_probe.py, profiles/r05_wino_probe_v5.txt): both variants
+  // win from 32 input channels on -- the 64-channel variant 1.27x at 32 -> 64 and 1.5-2.2x from 64 up, the 32-channel variant
+  // (twice the transform work per MFMA) 1.15-1.23x at 32 -> 32 and 1.38x at 64 -> 32 @256^2; 16 -> 32 loses (0.8-0.93x)
+  constexpr int kMinK = 32;
+  if (K < kMinK) return false;
+  return p.blocks * p.planned_ksplit >= p.cus / 2;
 }
 
 struct WgPlan {
   int lPW, lPH, lPI, lcg, lrg, nchunks, ktiles, ntiles, splits;
   size_t slab_bytes;
+  // the launch (everything hg_wino_wgrad used to decide after the plan) and what hg_wino_wgrad_route reports
+  int cps, last_chunks, empty_splits;   // as k_wino_wgrad computes them
+  int reduce_groups;                    // SG of k_wino_wgrad_reduce
+  int xcd, total_blocks, grid, persistent, cus;
 };
 inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// The one place that decides a hg_wino_wgrad call.
 inline bool make_wg_plan(int B, int K, int N, int H, int W, WgPlan &p) {
   if (B <= 0 || K <= 0 || N <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1)) return false;
   const int tw = W / 2, th = H / 2;
@@ -909,7 +956,25 @@ inline bool make_wg_plan(int B, int K, int N, int H, int W, WgPlan &p) {
   if (s < 1) s = 1;
   p.splits = s;
   p.slab_bytes = (size_t)s * 16 * (p.ntiles * 64) * (p.ktiles * 64) * sizeof(float);
+  p.cps = (p.nchunks + s - 1) / s;
+  const int used = (p.nchunks + p.cps - 1) / p.cps;   // splits that own a chunk; the others store zero slabs
+  p.empty_splits = s - used;
+  p.last_chunks = p.nchunks - (used - 1) * p.cps;
+  p.reduce_groups = s >= 16 ? 32 : s >= 4 ? 8 : 1;     // many splits: few (n, k) per block; few splits: many
+  p.xcd = s % 8 == 0;                                  // block order: see k_wino_wgrad
+  p.cus = cus;
+  p.total_blocks = tiles * s;
+  p.grid = wino_persist() && p.total_blocks > cus ? cus : p.total_blocks;
+  p.persistent = p.total_blocks > p.grid;
   return true;
+}
+inline bool wino_wgrad_beats_direct(int K, int N, int H, int W, const WgPlan &p) {
+  // 64 x 64 channel tiles: a layer with fewer channels on a side multiplies padding (and the transforms, done once per
+  // 64 x 64 tile, stop amortising: 0.75x at 32 -> 64); 2x2 maps are slab traffic rather than arithmetic (0.84-0.95x);
+  // measured 1.25-1.9x elsewhere (tools/wino_probe.py, profiles/r05_wino_probe_v5.txt)
+  constexpr int kMinChannels = 64, kMinSide = 4;
+  if (K < kMinChannels || N < kMinChannels || H < kMinSide || W < kMinSide) return false;
+  return p.nchunks / p.splits >= 4;
 }
 
 template <int TC, int TP, int KC>
@@ -923,10 +988,7 @@ int launch_wino(const WinoArgs &a, const WinoPlan &p, bool fe, hipStream_t st) {
     if (e != hipSuccess) return (int)e;
     attr[dev][fe] = true;
   }
-  const long long total = p.blocks * a.ksplit;
-  static const int persist = getenv("HG_WINO_PERSIST") ? atoi(getenv("HG_WINO_PERSIST")) : 1;
-  const long long grid = persist && total > num_cus() ? num_cus() : total;   // (512 threads, ~215 registers: one per CU)
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(512), lds, st, a);
   HG_LAUNCH_CHECK();
   return HG_OK;
 }
@@ -937,13 +999,8 @@ extern "C" {
 
 int hg_wino_supported(int32_t B, int32_t K, int32_t N, int32_t H, int32_t W) {
   WinoPlan p;
-  if (!make_plan(B, K, N, H, W, p)) return 0;
-  // measured against the direct kernel at the C3 shapes (tools/wino_probe.py, profiles/r05_wino_probe_v5.txt): both variants
-  // win from 32 input channels on -- the 64-channel variant 1.27x at 32 -> 64 and 1.5-2.2x from 64 up, the 32-channel variant
-  // (twice the transform work per MFMA) 1.15-1.23x at 32 -> 32 and 1.38x at 64 -> 32 @256^2; 16 -> 32 loses (0.8-0.93x)
-  constexpr int kMinK = 32;
-  if (K < kMinK) return 0;
-  return p.blocks * p.ksplit >= num_cus() / 2;
+  if (!make_plan(B, K, N, H, W, true, SIZE_MAX, p)) return 0;
+  return wino_beats_direct(K, p);
 }
 
 size_t hg_wino_packed_elems(int32_t Co, int32_t Ci, int32_t mode) {
@@ -977,8 +1034,31 @@ int hg_wino_pack_weights_multi(const hg_wino_pack_item *items_dev, int32_t n_ite
 
 size_t hg_wino_workspace_bytes(int32_t B, int32_t K, int32_t N, int32_t H, int32_t W) {
   WinoPlan p;
-  if (!make_plan(B, K, N, H, W, p) || p.ksplit == 1) return 0;
-  return (size_t)p.ksplit * B * N * H * W * sizeof(float);
+  if (!make_plan(B, K, N, H, W, true, SIZE_MAX, p)) return 0;
+  return p.planned_slab_bytes;
+}
+
+int hg_wino_route(const hg_wino_query *q, hg_wino_plan *out) {
+  if (!q || q->struct_size != (int32_t)sizeof(hg_wino_query) || !out || out->struct_size != (int32_t)sizeof(hg_wino_plan)) return HG_EINVAL;
+  WinoPlan p;
+  if (!make_plan(q->B, q->K, q->N, q->H, q->W, q->have_workspace != 0, q->workspace_bytes, p)) return HG_EUNSUPPORTED;
+  out->variant = p.variant;
+  out->fe = q->fe != 0;
+  out->nblk = p.nblk; out->nch = p.nch;
+  out->lTW = p.lTW; out->lTH = p.lTH; out->lNI = p.lNI;
+  out->bt_x = p.bt_x; out->bt_y = p.bt_y;
+  out->blocks = (int32_t)p.blocks;
+  out->ksplit = p.ksplit;
+  out->chunks_per_split = p.cps; out->last_split_chunks = p.last_chunks; out->empty_splits = p.empty_splits;
+  out->xcd = p.xcd;
+  out->grid = (int32_t)p.grid;
+  out->persistent = p.persistent;
+  out->reduce = p.reduce;
+  out->cus = p.cus;
+  out->supported = wino_beats_direct(q->K, p);
+  out->reserved = 0;
+  out->slab_bytes = p.slab_bytes;
+  return HG_OK;
 }
 
 int hg_wino_conv2d(const float *in, const float *u, float *out, const float *iscale, const float *oscale,
@@ -990,8 +1070,7 @@ int hg_wino_conv2d(const float *in, const float *u, float *out, const float *isc
   if (noise_img && (noise_S < H || noise_S < W || (noise_S & 1))) return HG_EINVAL;
   if (addend && (iscale || oscale || noise_img || lrelu_slope > 0.f)) return HG_EINVAL;
   WinoPlan p;
-  if (!make_plan(B, K, N, H, W, p)) return HG_EUNSUPPORTED;
-  if (p.ksplit > 1 && (!workspace || workspace_bytes < (size_t)p.ksplit * B * N * H * W * sizeof(float))) p.ksplit = 1;
+  if (!make_plan(B, K, N, H, W, workspace != nullptr, workspace_bytes, p)) return HG_EUNSUPPORTED;
   WinoArgs a;
   a.in = in; a.u = u; a.out = out; a.iscale = iscale; a.oscale = oscale; a.bias = bias; a.addend = addend;
   a.noise_w = noise_w; a.noise_img = noise_img; a.noise_S = noise_S; a.slope = lrelu_slope;
@@ -1000,12 +1079,12 @@ int hg_wino_conv2d(const float *in, const float *u, float *out, const float *isc
   a.tiles_w = p.tiles_w; a.tiles_h = p.tiles_h; a.bt_x = p.bt_x; a.bt_y = p.bt_y;
   a.ksplit = p.ksplit; a.slab = (float *)workspace;
   a.blocks = (int)p.blocks; a.total_tiles = (int)(p.blocks * p.ksplit);
-  a.xcd = p.nblk > 1 && p.nblk < 8 && (p.blocks / p.nblk) % 8 == 0;
+  a.xcd = p.xcd;
   hipStream_t st = (hipStream_t)stream;
   const bool fe = iscale != nullptr;
   int rc = p.variant == 0 ? launch_wino<2, 2, 8>(a, p, fe, st) : launch_wino<1, 4, 4>(a, p, fe, st);
   if (rc) return rc;
-  if (p.ksplit > 1) {
+  if (p.reduce) {
     const long long total = (long long)B * N * H * W;   // H, W even -> a multiple of 4
     long long nb = (total / 4 + 255) / 256;
     if (nb > 4096) nb = 4096;
@@ -1025,12 +1104,31 @@ size_t hg_wino_wgrad_workspace_bytes(int32_t B, int32_t K, int32_t N, int32_t H,
 int hg_wino_wgrad_supported(int32_t B, int32_t K, int32_t N, int32_t H, int32_t W) {
   WgPlan p;
   if (!make_wg_plan(B, K, N, H, W, p)) return 0;
-  // 64 x 64 channel tiles: a layer with fewer channels on a side multiplies padding (and the transforms, done once per
-  // 64 x 64 tile, stop amortising: 0.75x at 32 -> 64); 2x2 maps are slab traffic rather than arithmetic (0.84-0.95x);
-  // measured 1.25-1.9x elsewhere (tools/wino_probe.py, profiles/r05_wino_probe_v5.txt)
-  constexpr int kMinChannels = 64, kMinSide = 4;
-  if (K < kMinChannels || N < kMinChannels || H < kMinSide || W < kMinSide) return 0;
-  return p.nchunks / p.splits >= 4;
+  return wino_wgrad_beats_direct(K, N, H, W, p);
+}
+
+int hg_wino_wgrad_route(const hg_wino_query *q, hg_wino_wgrad_plan *out) {
+  if (!q || q->struct_size != (int32_t)sizeof(hg_wino_query) || !out || out->struct_size != (int32_t)sizeof(hg_wino_wgrad_plan))
+    return HG_EINVAL;
+  WgPlan p;
+  if (!make_wg_plan(q->B, q->K, q->N, q->H, q->W, p)) return HG_EUNSUPPORTED;
+  out->lPW = p.lPW; out->lPH = p.lPH; out->lPI = p.lPI;
+  out->lcg = p.lcg; out->lrg = p.lrg;
+  out->nchunks = p.nchunks;
+  out->ktiles = p.ktiles; out->ntiles = p.ntiles;
+  out->splits = p.splits;
+  out->chunks_per_split = p.cps; out->last_split_chunks = p.last_chunks; out->empty_splits = p.empty_splits;
+  out->reduce_groups = p.reduce_groups;
+  out->xcd = p.xcd;
+  out->grid = p.grid;
+  out->persistent = p.persistent;
+  out->cus = p.cus;
+  out->supported = wino_wgrad_beats_direct(q->K, q->N, q->H, q->W, p);
+  out->reserved = 0;
+  out->slab_bytes = p.slab_bytes;
+  if (!q->have_workspace) return HG_EINVAL;
+  if (q->workspace_bytes < p.slab_bytes) return HG_EWORKSPACE;
+  return HG_OK;
 }
 
 int hg_wino_wgrad(const float *in, const float *gout, float *gw, int32_t B, int32_t K, int32_t N, int32_t H, int32_t W,
@@ -1054,16 +1152,14 @@ int hg_wino_wgrad(const float *in, const float *gout, float *gw, int32_t B, int3
     if (e != hipSuccess) return (int)e;
     attr[dev] = true;
   }
-  a.xtiles = p.ktiles * p.ntiles; a.total_blocks = a.xtiles * p.splits;
-  a.xcd = p.splits % 8 == 0;
-  static const int persist = getenv("HG_WINO_PERSIST") ? atoi(getenv("HG_WINO_PERSIST")) : 1;
-  const int grid = persist && a.total_blocks > num_cus() ? num_cus() : a.total_blocks;
-  hipLaunchKernelGGL(k_wino_wgrad, dim3((unsigned)grid), dim3(512), lds, st, a);
+  a.xtiles = p.ktiles * p.ntiles; a.total_blocks = p.total_blocks;
+  a.xcd = p.xcd;
+  hipLaunchKernelGGL(k_wino_wgrad, dim3((unsigned)p.grid), dim3(512), lds, st, a);
   HG_LAUNCH_CHECK();
-  if (p.splits >= 16)
+  if (p.reduce_groups == 32)
     hipLaunchKernelGGL(k_wino_wgrad_reduce<32>, dim3((unsigned)((a.Kp + 31) / 32), (unsigned)N), dim3(256), 0, st, a.slab, gw, N, K,
                        a.Np, a.Kp, p.splits);
-  else if (p.splits >= 4)
+  else if (p.reduce_groups == 8)
     hipLaunchKernelGGL(k_wino_wgrad_reduce<8>, dim3((unsigned)((a.Kp + 127) / 128), (unsigned)N), dim3(256), 0, st, a.slab, gw, N, K,
                        a.Np, a.Kp, p.splits);
   else

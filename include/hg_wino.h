@@ -68,6 +68,68 @@ size_t hg_wino_wgrad_workspace_bytes(int32_t B, int32_t K, int32_t N, int32_t H,
 int hg_wino_wgrad(const float *in, const float *gout, float *gw, int32_t B, int32_t K, int32_t N, int32_t H, int32_t W,
                   void *workspace, size_t workspace_bytes, void *stream);
 
+/* Which launches hg_wino_conv2d / hg_wino_wgrad take (since version 112).  The library decides this once per call, as one
+ * plan: the same plan sizes the workspace, answers the *_supported queries, fills the kernel arguments of the launches and
+ * is what the two queries below return.  Host logic only: nothing is launched, no device is touched and none is needed
+ * (256 CUs are assumed where no device answers).  The HG_WINO_* environment knobs act on the plan, so the route reports
+ * what they force. */
+typedef struct hg_wino_query {
+  int32_t struct_size;          /* sizeof(hg_wino_query) as the caller compiled it (ABI guard)                               */
+  int32_t B, K, N, H, W;        /* as passed to hg_wino_conv2d / hg_wino_wgrad                                               */
+  int32_t fe;                   /* hg_wino_conv2d: != 0: the call passes iscale (the kernel instance with the input scale)  */
+  int32_t have_workspace;       /* the call's workspace != NULL                                                              */
+  size_t workspace_bytes;       /* the call's workspace_bytes ((size_t)-1: as the workspace query plans, "unlimited")        */
+} hg_wino_query;
+
+typedef struct hg_wino_plan {
+  int32_t struct_size;          /* in: sizeof(hg_wino_plan) as the caller compiled it (ABI guard)                           */
+  int32_t variant;              /* 0: k_wino<2,2,8> (64 channels x 64 tiles, 8-channel chunks), 1: k_wino<1,4,4> (32 x 128, 4) */
+  int32_t fe;                   /* the FE instance of that kernel (input scale)                                              */
+  int32_t nblk, nch;            /* channel blocks of N, K chunks                                                             */
+  int32_t lTW, lTH, lNI;        /* log2 of a block's tile grid: tiles per row, rows, images                                  */
+  int32_t bt_x, bt_y;           /* block tiles per map row / column (ragged where tiles_w, tiles_h are no multiple)          */
+  int32_t blocks;               /* work items per K split: nblk x bt_x x bt_y x image groups                                 */
+  int32_t ksplit;               /* K splits as launched (1: the kernel writes `out` itself)                                  */
+  int32_t chunks_per_split;     /* ceil(nch / ksplit): split z owns chunks [z, z + 1) x that, clamped to nch                 */
+  int32_t last_split_chunks;    /* chunks of the last split that owns any (1 ... chunks_per_split)                           */
+  int32_t empty_splits;         /* trailing splits that own no chunk (they store zero slabs)                                 */
+  int32_t xcd;                  /* 1: the channel blocks of a block tile are dispatched eight apart (one XCD)                */
+  int32_t grid;                 /* workgroups launched: min(blocks x ksplit, CUs) (HG_WINO_PERSIST=0: blocks x ksplit)       */
+  int32_t persistent;           /* 1: blocks x ksplit > grid -- workgroups loop over work items                              */
+  int32_t reduce;               /* 1: k_wino_reduce follows (ksplit > 1)                                                     */
+  int32_t cus;                  /* compute units planned for                                                                 */
+  int32_t supported;            /* == hg_wino_supported(B, K, N, H, W)                                                       */
+  int32_t reserved;
+  size_t slab_bytes;            /* workspace the route uses: ksplit x B x N x H x W x 4 (== hg_wino_workspace_bytes for an
+                                   unlimited workspace), 0 without a split                                                   */
+} hg_wino_plan;
+
+typedef struct hg_wino_wgrad_plan {
+  int32_t struct_size;          /* in: sizeof(hg_wino_wgrad_plan) as the caller compiled it (ABI guard)                     */
+  int32_t lPW, lPH, lPI;        /* log2 of the 8-tile chunk pattern: tiles per row, rows, images                             */
+  int32_t lcg, lrg;             /* log2 of the column / row groups of a map                                                  */
+  int32_t nchunks;              /* chunks of the launch: image groups x row groups x column groups                           */
+  int32_t ktiles, ntiles;       /* 64-channel tiles of K and N                                                               */
+  int32_t splits;               /* pixel splits (slabs)                                                                      */
+  int32_t chunks_per_split;     /* ceil(nchunks / splits)                                                                    */
+  int32_t last_split_chunks;    /* chunks of the last split that owns any                                                    */
+  int32_t empty_splits;         /* trailing splits that own no chunk (they store zero slabs)                                 */
+  int32_t reduce_groups;        /* SG of k_wino_wgrad_reduce<SG>: 32 (splits >= 16), 8 (>= 4) or 1                           */
+  int32_t xcd;                  /* 1: the (n, k) tiles of a split are dispatched eight apart (one XCD)                       */
+  int32_t grid;                 /* workgroups launched: min(ktiles x ntiles x splits, CUs)                                   */
+  int32_t persistent;           /* 1: more blocks than workgroups                                                            */
+  int32_t cus;                  /* compute units planned for                                                                 */
+  int32_t supported;            /* == hg_wino_wgrad_supported(B, K, N, H, W)                                                 */
+  int32_t reserved;
+  size_t slab_bytes;            /* == hg_wino_wgrad_workspace_bytes(B, K, N, H, W)                                           */
+} hg_wino_wgrad_plan;
+
+/* Fill *out (all fields but struct_size) for the call `q` describes.  Return codes are those of the call: NULL pointers
+ * or a stale struct_size HG_EINVAL, a shape the call does not serve HG_EUNSUPPORTED; hg_wino_wgrad_route also HG_EINVAL
+ * without a workspace and HG_EWORKSPACE for one that is too small (hg_wino_wgrad refuses both), after filling *out. */
+int hg_wino_route(const hg_wino_query *q, hg_wino_plan *out);
+int hg_wino_wgrad_route(const hg_wino_query *q, hg_wino_wgrad_plan *out);
+
 #ifdef __cplusplus
 }
 #endif

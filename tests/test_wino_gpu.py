@@ -1,9 +1,18 @@
 """Winograd F(2x2, 3x3) convolutions (include/hg_wino.h) through the C ABI against torch's fp64 convolution: the output, the
 data gradient (transposed / flipped operand), the weight gradient, the fused epilogue of the generator stage (modulation,
 demodulation, noise, LeakyReLU: histoGAN/histoGAN.py:420-440, 465-476), the residual addend of the discriminator block
-(:520-524) -- on ragged maps (tile masks), batch tails inside an image group, both channel-block variants, forced K splits,
-launches with more tiles than CUs (the persistent tile loop), the padding corners of the 16-byte row loads; determinism; and
-the autograd dispatch (conv2d takes the Winograd form exactly where hg_wino_supported says so, with the same gradients).
+(:520-524) -- on ragged maps (tile masks), batch tails inside an image group, both channel-block variants, the padding corners
+of the 16-byte row loads; determinism; and the autograd dispatch (conv2d takes the Winograd form exactly where
+hg_wino_supported says so, with the same gradients).
+
+What these shapes reach of the host-side plans on a 256-CU chip (hg_wino_route / hg_wino_wgrad_route answer for any shape):
+the fp64 cases have natural K splits of 2 and 3 with equal splits, the XCD block order with two channel blocks only, and one
+launch with more tiles than CUs ((4, 64, 96, 128, 128): two whole rounds of the persistent loop, 64-channel variant, no K
+split); more splits come from HG_WINO_KSPLIT / HG_WINO_WG_SPLITS in the subprocess test, at one shape each; the weight-gradient
+cases have five of the ten chunk patterns, one or two chunks per block but for two shapes (five, with empty splits; sixteen),
+no launch with more blocks than CUs (the dispatch test has them, at its 1e-5 bar).
+Branch coverage -- one fp64 case per branch of make_plan / make_wg_plan, each asserting the route it was chosen for -- lives in
+tests/test_wino_route_gpu.py.
 
 Bars: 2e-6 max-norm relative for outputs and data gradients, 4e-6 for weight gradients -- tighter than the direct kernel's
 5e-6 / 1e-5 (tests/test_c3_parity_gpu.py): sixteen accumulation chains of depth K instead of one of depth 9 K."""
