@@ -294,6 +294,34 @@ def _load():
     lib.hg_ssim_fwd.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
     lib.hg_ssim_bwd.restype = ctypes.c_int
     lib.hg_ssim_bwd.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, i32, i32, i32, vp]
+    lib.hg_idt_block_pixels.restype = ctypes.c_int
+    lib.hg_idt_block_pixels.argtypes = []
+    lib.hg_idt_max_bins.restype = ctypes.c_int
+    lib.hg_idt_max_bins.argtypes = []
+    lib.hg_idt_group_pixels.restype = ctypes.c_int
+    lib.hg_idt_group_pixels.argtypes = []
+    lib.hg_idt_target_chunk.restype = ctypes.c_int
+    lib.hg_idt_target_chunk.argtypes = [i32]
+    lib.hg_idt_blocks.restype = ctypes.c_int
+    lib.hg_idt_blocks.argtypes = [i64]
+    lib.hg_idt_plane_stride.restype = i64
+    lib.hg_idt_plane_stride.argtypes = [i64]
+    lib.hg_idt_workspace_bytes.restype = sz
+    lib.hg_idt_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    lib.hg_idt_clear.restype = ctypes.c_int
+    lib.hg_idt_clear.argtypes = [vp, i64, vp, i64, vp]
+    lib.hg_idt_range.restype = ctypes.c_int
+    lib.hg_idt_range.argtypes = [vp, i64, i64, i64, vp, i32, vp, vp, vp]
+    lib.hg_idt_hist.restype = ctypes.c_int
+    lib.hg_idt_hist.argtypes = [vp, i64, i64, i64, vp, i32, i32, vp, vp, i32, vp]
+    lib.hg_idt_table.restype = ctypes.c_int
+    lib.hg_idt_table.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp]
+    lib.hg_idt_apply.restype = ctypes.c_int
+    lib.hg_idt_apply.argtypes = [vp, i64, vp, vp, i32, vp, vp, f32, vp, vp, i32, vp]
+    lib.hg_idt_target_tables.restype = ctypes.c_int
+    lib.hg_idt_target_tables.argtypes = [vp, i64, i64, i64, vp, i32, i32, vp, vp, vp]
+    lib.hg_idt_run.restype = ctypes.c_int
+    lib.hg_idt_run.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i32, i32, f32, vp, i32, vp, sz, vp]
     return lib
 
 
@@ -318,7 +346,10 @@ EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg
            'hg_resize_axis', 'hg_pyr_down', 'hg_pyr_up_add', 'hg_color_moments_workspace_bytes', 'hg_color_moments',
            'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc', 'hg_bgu_normal_workspace_bytes', 'hg_bgu_normal',
            'hg_bgu_slice', 'hg_srgb_to_lab', 'hg_lab_to_srgb', 'hg_delta_e_workspace_bytes', 'hg_delta_e',
-           'hg_ssim_tile', 'hg_ssim_finish_threads', 'hg_ssim_workspace_bytes', 'hg_ssim_fwd', 'hg_ssim_bwd')
+           'hg_ssim_tile', 'hg_ssim_finish_threads', 'hg_ssim_workspace_bytes', 'hg_ssim_fwd', 'hg_ssim_bwd',
+           'hg_idt_block_pixels', 'hg_idt_max_bins', 'hg_idt_group_pixels', 'hg_idt_target_chunk', 'hg_idt_blocks', 'hg_idt_plane_stride',
+           'hg_idt_workspace_bytes', 'hg_idt_clear', 'hg_idt_range', 'hg_idt_hist', 'hg_idt_table', 'hg_idt_apply',
+           'hg_idt_target_tables', 'hg_idt_run')
 
 
 class HgError(RuntimeError):

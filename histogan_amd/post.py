@@ -12,8 +12,10 @@ utils/pyramid_upsampling.py, utils/color_transfer_MKL.py) convert to and from th
 
 Also here, with no counterpart in the reference: the sRGB <-> CIE Lab conversions, and the CIE colour difference between
 two sRGB images (delta_e, delta_e_map: dE76 and CIEDE2000) as a differentiable loss and as the metric reported for
-recolourings; and SSIM / MS-SSIM of the lightness plane or of the components (ssim, ssim_map, ms_ssim), the structure term
-and the number reported for "structure preserved under recolouring".
+recolourings; SSIM / MS-SSIM of the lightness plane or of the components (ssim, ssim_map, ms_ssim), the structure term
+and the number reported for "structure preserved under recolouring"; and the iterative distribution transfer
+(color_transfer_idt, idt_rotations), the nonlinear colour transfer that reaches the target distributions -- bimodal, skewed,
+saturated -- an affine map cannot.
 """
 import ctypes
 from functools import lru_cache
@@ -594,11 +596,11 @@ def MKL(A, B):
     return Ua @ Da_inv @ Uc @ Dc @ Uc.T @ Da_inv @ Ua.T
 
 
-def _pixels(t, what):
+def _pixels(t, what, fn='color_transfer_mkl'):
     """(tensor, n, pix_stride, chan_stride) of an (H, W, 3) fp32 view (a CHW image's .permute(1, 2, 0) is one)."""
-    need_gpu(t, 'color_transfer_mkl', _FOUND)
+    need_gpu(t, fn, _FOUND)
     if t.dim() != 3 or t.shape[2] != 3:
-        raise ValueError(f'color_transfer_mkl: {what} must be an (H, W, 3) image, got {tuple(t.shape)}')
+        raise ValueError(f'{fn}: {what} must be an (H, W, 3) image, got {tuple(t.shape)}')
     t = t.float()
     if t.stride(0) != t.shape[1] * t.stride(1) or t.stride(1) <= 0 or t.stride(2) <= 0:
         t = t.contiguous()
@@ -635,6 +637,84 @@ def color_transfer_mkl(source, target, quantize=False):
         check(lib.hg_color_affine(src.data_ptr(), n, ps, cs, coef.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                   out.data_ptr(), int(quantize), raw_stream(src.device)), 'hg_color_affine')
     return out, T
+
+
+# ---- iterative distribution transfer (hg_idt_*, include/hg_post.h) ---------------------------------------------------
+def idt_rotations(iterations, seed=0):
+    """The (iterations, 3, 3) fp64 rotations of color_transfer_idt (row a = axis a): the identity first, then proper rotations
+    drawn from numpy.random.RandomState(seed) -- the Q of the QR decomposition of a 3x3 normal matrix, its columns multiplied
+    by the signs of R's diagonal (which makes Q uniform over the orthogonal group) and the first column flipped when the
+    determinant is negative."""
+    iterations = int(iterations)
+    if iterations < 1:
+        raise ValueError(f'idt_rotations: iterations must be at least 1, got {iterations}')
+    rs = np.random.RandomState(seed)
+    out = np.empty((iterations, 3, 3), dtype=np.float64)
+    out[0] = np.eye(3)
+    for i in range(1, iterations):
+        q, r = np.linalg.qr(rs.standard_normal((3, 3)))
+        q = q * np.sign(np.diag(r))
+        if np.linalg.det(q) < 0:
+            q[:, 0] = -q[:, 0]
+        out[i] = q
+    return out
+
+
+def idt_encode_range(lo, hi):
+    """A range set of include/hg_post.h, uint32[6], from three minima and three maxima (fp32): the order-preserving unsigned
+    image of each float.  Returned as an int64 numpy array (torch has no uint32 arithmetic); idt_range_tensor uploads it."""
+    f = np.concatenate([np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)])
+    u = f.view(np.uint32).astype(np.int64)
+    return np.where(u & 0x80000000, u ^ 0xffffffff, u | 0x80000000)
+
+
+def idt_decode_range(enc):
+    """(lo (3,), hi (3,)) fp32 of range sets (..., 6) read back from the device (any integer dtype holding the 32 bits)."""
+    u = np.asarray(enc).astype(np.int64) & 0xffffffff
+    bits = np.where(u & 0x80000000, u & 0x7fffffff, u ^ 0xffffffff).astype(np.uint32)
+    f = bits.view(np.float32)
+    return f[..., :3], f[..., 3:]
+
+
+def idt_range_tensor(enc, device):
+    """Encoded range sets as the int32 device tensor whose bits the kernels read as uint32."""
+    return torch.from_numpy(np.asarray(enc, dtype=np.int64).astype(np.uint32).view(np.int32).copy()).to(device)
+
+
+def color_transfer_idt(source, target, iterations=20, bins=256, relaxation=1.0, rotations=None, seed=0, quantize=False):
+    """Iterative distribution transfer (Pitie, Kokaram, Dahyot 2007) on the GPU: maps the colours of `source` onto the colour
+    DISTRIBUTION of `target`, not only its mean and covariance as color_transfer_mkl does.  Per rotation the colour cloud is
+    projected on three orthogonal axes, each 1-D marginal is matched to the target's by CDF matching on a linear-binned
+    `bins`-node histogram, and the pixels move by `relaxation` times the difference (hg_idt_run, include/hg_post.h holds the
+    definition).  source, target: (H, W, 3) fp32 device views of any two sizes.  rotations: (iterations, 3, 3) orthonormal
+    matrices, row a = axis a; None draws idt_rotations(iterations, seed).  Returns (out, rotations): out is (H, W, 3) fp32
+    clipped to [0, 1], or uint8 = (uint8)(out*255) when quantize; rotations the fp64 array that was used (passed to the
+    kernels as fp32).  The whole transfer is enqueued on the current stream without a host read-back, and its result does
+    not depend on the order of any sum: two calls give the same bits.
+
+    bins: the default of 256 is meant for photographs and 256x256 targets.  The quantile map is ill-conditioned where
+    target nodes are empty, so more bins than about a sixteenth of the smaller image's pixels buy noise, not fidelity
+    (with ~1000 pixels per image, 256 bins already differ by 1e-4 between fp32 and fp64 arithmetic, 1024 bins by 1e-2)."""
+    fn = 'color_transfer_idt'
+    src, n0, ps0, cs0 = _pixels(source, 'source', fn)
+    tgt, n1, ps1, cs1 = _pixels(target, 'target', fn)
+    if tgt.device != src.device:
+        raise ValueError(f'{fn}: source and target must be on one device, got {src.device} and {tgt.device}')
+    if rotations is None:
+        rotations = idt_rotations(iterations, seed)
+    rotations = np.ascontiguousarray(rotations, dtype=np.float64)
+    if rotations.ndim != 3 or rotations.shape[1:] != (3, 3) or rotations.shape[0] < 1:
+        raise ValueError(f'{fn}: rotations must be (iterations, 3, 3), got {rotations.shape}')
+    iters, bins = rotations.shape[0], int(bins)
+    out = torch.empty(source.shape[:2] + (3,), dtype=torch.uint8 if quantize else torch.float32, device=src.device)
+    with on_device(src.device):
+        rot = torch.from_numpy(rotations.astype(np.float32)).to(src.device)
+        nb = lib.hg_idt_workspace_bytes(n0, n1, iters, bins)
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=src.device)
+        check(lib.hg_idt_run(src.data_ptr(), n0, ps0, cs0, tgt.data_ptr(), n1, ps1, cs1, rot.data_ptr(), iters, bins,
+                             float(relaxation), out.data_ptr(), int(quantize), ws.data_ptr(), nb, raw_stream(src.device)),
+              'hg_idt_run')
+    return out, rotations
 
 
 # ---- bilateral guided upsampling (upsampling/BGU.m, bguFit.m, bguSlice.m) -----------------------------------------------

@@ -13,7 +13,9 @@ the per-layer noise feature maps, fed through GeneratorBlock.forward_(noise1=, n
 
 Not here: the VGG perceptual term (see `project`; the weight-free perceptual colour term in its place is the CIE colour
 difference, `delta_e_weight`, and SSIM / MS-SSIM of the lightness plane, `ssim_weight`), face_preprocessing, command-line front ends and file I/O.  The caller
-post-processes `recolor`'s output with post.pyramid_upsampling / post.color_transfer_mkl as the reference's scripts do.
+post-processes `recolor`'s output with post.pyramid_upsampling / post.color_transfer_mkl as the reference's scripts do, or
+with post.color_transfer_idt (recoloringTrainer.evaluate's post_recoloring='idt'), the nonlinear transfer, where the
+recoloured image's whole colour distribution is wanted on the photo and not only its mean and covariance.
 """
 import torch
 import torch.nn.functional as F

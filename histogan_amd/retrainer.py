@@ -456,12 +456,18 @@ class recoloringTrainer():
         it at the photo's size padded up to multiples of 2**pyramid_levels, as the reference does; `post_recoloring`
         then maps `original_image` (the photo, (H, W, 3) in [0, 1]) onto the colours of the unclamped network output
         with the Monge-Kantorovich transfer and overwrites the same file at the photo's size.  Both need a batch of
-        one (ValueError otherwise).  `resizing_method='BGU_native'` carries the result back with bilateral guided
-        upsampling instead (post.bgu_upsampling: the arithmetic of the reference's upsampling/BGU.m on the network's
+        one (ValueError otherwise).  `post_recoloring='idt'` does the same with the iterative distribution transfer
+        (post.color_transfer_idt: nonlinear, matches the output's whole colour distribution rather than its mean and
+        covariance); any other string raises ValueError, and True keeps meaning the Monge-Kantorovich map.
+        `resizing_method='BGU_native'` carries the result back with bilateral guided upsampling instead (post.bgu_upsampling: the arithmetic of the reference's upsampling/BGU.m on the network's
         8-bit output, without the JPEG round trip) and writes it at exactly the photo's size.
         `resizing_method='BGU'`, which in the reference runs an external Windows executable, raises
         NotImplementedError."""
         upscale = resizing == 'upscaling'
+        if isinstance(post_recoloring, str) and post_recoloring != 'idt':
+            raise ValueError(f"recoloringTrainer.evaluate: post_recoloring={post_recoloring!r} (True: the Monge-Kantorovich "
+                             "linear transfer; 'idt': the iterative distribution transfer)")
+        recolor = 'idt' if post_recoloring == 'idt' else post_recoloring is True
         if upscale and resizing_method not in ('pyramid', 'BGU_native'):
             raise NotImplementedError(f"recoloringTrainer.evaluate: resizing_method={resizing_method!r} for 'upscaling' "
                                       "(implemented: 'pyramid' and 'BGU_native'; 'BGU' runs an external executable in "
@@ -480,7 +486,7 @@ class recoloringTrainer():
             img_bt_sz = image_batch.shape[0]
         noise = self.rng.image_noise(hist_batch.shape[0], image_batch.shape[-1])
         generated_images = self._recolor(image_batch, hist_batch, noise)
-        if (upscale or post_recoloring is True) and generated_images.shape[0] != 1:
+        if (upscale or recolor) and generated_images.shape[0] != 1:
             raise ValueError('recoloringTrainer.evaluate: upscaling / post_recoloring need a batch of one image, got '
                              f'{generated_images.shape[0]}')
         if num is not None and self.is_main:
@@ -493,9 +499,9 @@ class recoloringTrainer():
             if resizing == 'downscaling' and original_size is not None:
                 from PIL import Image
                 Image.open(output_name).resize((original_size[0], original_size[1])).save(output_name)
-            if upscale or post_recoloring is True:
+            if upscale or recolor:
                 self._full_resolution(generated_images, output_name, upscale, pyramid_levels, swapping_levels,
-                                      level_blending, input_image_name, original_image, post_recoloring is True,
+                                      level_blending, input_image_name, original_image, recolor,
                                       resizing_method)
             if save_input is True:
                 save_image_grid(image_batch[:img_bt_sz] if multi else image_batch,
@@ -523,7 +529,8 @@ class recoloringTrainer():
             if original_image is None:
                 raise ValueError('recoloringTrainer.evaluate: post_recoloring needs original_image')
             src = torch.from_numpy(np.ascontiguousarray(original_image, dtype=np.float32)).to(self.device)
-            out, _ = post.color_transfer_mkl(src, generated_images[0].permute(1, 2, 0), quantize=True)
+            transfer = post.color_transfer_idt if recolor == 'idt' else post.color_transfer_mkl
+            out, _ = transfer(src, generated_images[0].permute(1, 2, 0), quantize=True)
             post.save_rgb(out, output_name)
 
     def print_log(self):

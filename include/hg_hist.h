@@ -28,6 +28,12 @@ extern "C" {
 #define HG_ERESIZE (-3)   /* unknown resize mode    (RGBuvHistBlock.py:90-93)            */
 #define HG_EWORKSPACE (-4)/* workspace too small                                         */
 #define HG_EUNSUPPORTED (-5)
+/* the refusals of the distribution transfer (hg_idt_*, hg_post.h), one code each */
+#define HG_EIDT_BINS (-20)        /* bins < 2                                             */
+#define HG_EIDT_BINS_LDS (-21)    /* bins > hg_idt_max_bins(): the counters exceed LDS    */
+#define HG_EIDT_ITERATIONS (-22)  /* iterations < 1, or more rotations than one call takes */
+#define HG_EIDT_RELAXATION (-23)  /* relaxation outside (0, 1]                            */
+#define HG_EIDT_PIXELS (-24)      /* a pixel count outside [1, 2^32 - 1]                  */
 
 /* soft-bin kernel, RGBuvHistBlock.py:124-140 */
 #define HG_METHOD_THRESHOLDING 0

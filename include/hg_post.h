@@ -20,10 +20,15 @@
  *   hg_ssim_fwd, hg_ssim_bwd  SSIM of two images (of their L* plane or of their components): per-sample means of ssim and cs,
  *                             map, pooled planes for the next MS-SSIM level; gradient by a second tiled pass (no code of the
  *                             reference: the structure term of a projection and of ReHistoGAN's reconstruction loss)
+ *   hg_idt_run, hg_idt_*      iterative distribution transfer (Pitie, Kokaram, Dahyot 2007): the nonlinear colour transfer next
+ *                             to hg_color_affine's linear one -- rotate the colour cloud, match the three 1-D marginals by
+ *                             CDF matching, rotate back, repeat (no code of the reference, whose color_transfer_MKL.py took
+ *                             the linear half of the same toolbox)
  *
  * Conventions as in hg_hist.h: return 0 / negative HG_E* / positive hipError_t; device pointers unless stated; fp32;
  * enqueue on `stream`; never allocate or synchronise; nothing is launched for invalid arguments.  Planar images are
- * contiguous (C, H, W).  Every result is deterministic: no atomics, fixed reduction order.
+ * contiguous (C, H, W).  Every result is deterministic: no atomics, fixed reduction order (hg_idt_*: integer atomics
+ * only, whose sums do not depend on their order).
  */
 #ifndef HG_POST_H
 #define HG_POST_H
@@ -223,6 +228,88 @@ int hg_ssim_fwd(const void *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_
 int hg_ssim_bwd(const void *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_t s1_w, const void *x2, int64_t s2_b,
                 int64_t s2_c, int64_t s2_h, int64_t s2_w, int32_t mode, const double *coef, const double *coarse, void *grad,
                 int32_t B, int32_t H, int32_t W, void *stream);
+
+/* Iterative distribution transfer (since version 113).  Inputs: n_src source pixels x_j and n_tgt target pixels y_j (3
+ * channels, addressed as in hg_color_moments; the two counts are independent), `iterations` rotations R_i (fp32 DEVICE array
+ * (iterations, 3, 3) row-major, orthonormal, row a = axis a), bins = n >= 2 nodes and relaxation rho in (0, 1].  For every
+ * rotation in order and every axis a independently:
+ *   1. v_j = R_i[a] . x_j = fma(R[a][2], x2, fma(R[a][1], x1, R[a][0] x0)), [lo0, hi0] = min / max of v; likewise w_j,
+ *      [lo1, hi1] for the target.
+ *   2. Linear-binned fixed-point histogram over n nodes, the same rule for source and target over their own ranges:
+ *      u = (v - lo) (n - 1) / (hi - lo) clamped to [0, n - 1], k = min(floor(u), n - 2), t = u - k, q = floor(t 65536 + 0.5);
+ *      node k receives 65536 - q and node k + 1 receives q.  Every pixel deposits 65536 units: sum_k h[k] == 65536 N exactly.
+ *      On an axis with !(hi - lo > 2^-20) every pixel deposits into node 0.
+ *   3. C0, C1 = inclusive integer prefix sums of the source and target histograms, totals T0, T1.  For node k: the smallest
+ *      j with C1[j] T0 >= C0[k] T1, compared as exact 128-bit products (exact for any counts the entry points admit);
+ *      u' = 0 if j == 0, else j - 1 + (C0[k] T1 - C1[j-1] T0) / (C1[j] T0 - C1[j-1] T0), the two differences converted to
+ *      fp64 and divided there.  M[k] = lo1 + u' / (n - 1) (hi1 - lo1) in fp64, stored as fp32.  Flat stretches of the target
+ *      CDF map to their left end.
+ *   4. v' = (1 - t) M[k] + t M[k + 1] with the k, t of step 2, d_a = v' - v.
+ *   5. If !(hi0 - lo0 > 2^-20), d_a = 0 (no division happens).  A degenerate target axis needs no case: every M[k] = lo1.
+ * Then x_j += rho R_i^T d_j.  After the last rotation the output is clipped to [0, 1] and written as (n_src, 3) HWC, fp32
+ * (16-byte aligned) or uint8 = (uint8)(v * 255) (truncation, 4-byte aligned) when out_u8 != 0, as hg_color_affine.
+ * Histograms, prefix sums and the search are integers, so nothing depends on the order of a sum: repeats are bit-identical.
+ *
+ * Device state, in the caller's workspace slots (hg_idt_run lays them out in its own workspace):
+ *   a range set   uint32[6] = enc(lo[0..2]), enc(hi[0..2]) with enc(f) = bits(f) ^ 0xffffffff when f is negative, else
+ *                 bits(f) | 0x80000000: unsigned order is float order, so min / max are integer atomics.  Cleared = (0xffffffff
+ *                 x 3, 0 x 3).
+ *   a histogram   uint64[3 * bins], axis-major.  Cleared = 0.
+ *   a map         fp32[3 * bins], axis-major.
+ *   the planes    the working copy of the source: fp32[3 * hg_idt_plane_stride(n)], channel c of pixel p at
+ *                 [c * stride + p], stride = n rounded up to a multiple of 4, 16-byte aligned.
+ * Limits: hg_idt_max_bins() nodes (3 * bins uint32 counters, and as many fp32 map nodes, in 48 KiB of LDS); pixel counts in
+ * [1, 2^32 - 1]; a workgroup flushes its LDS counters after every hg_idt_block_pixels() (< 65536) pixels, so they cannot
+ * overflow; hg_idt_target_chunk(bins) = the rotations whose counters fit LDS together, i.e. that one histogram launch takes;
+ * hg_idt_blocks(n) = the workgroups every per-pixel launch gives n pixels (each a contiguous share, a multiple of 4 pixels,
+ * walked hg_idt_group_pixels() = 256 lanes x 4 pixels at a time on the planes).
+ * The queries return 0 for refused arguments.
+ * Refusals, before any launch: a NULL or misaligned pointer, a non-positive stride HG_EINVAL; bins < 2 HG_EIDT_BINS;
+ * bins > hg_idt_max_bins() HG_EIDT_BINS_LDS; iterations (nrot) < 1, or nrot > hg_idt_target_chunk(bins) in hg_idt_hist,
+ * HG_EIDT_ITERATIONS; relaxation outside (0, 1] HG_EIDT_RELAXATION; a pixel count outside [1, 2^32 - 1] HG_EIDT_PIXELS; a
+ * workspace below hg_idt_workspace_bytes HG_EWORKSPACE.
+ *
+ *   hg_idt_clear          resets n_ranges range sets and n_counters histogram counters (either may be 0).
+ *   hg_idt_range          steps 1 of nrot rotations over strided pixels: atomic min / max into ranges[nrot][6] (cleared by the
+ *                         caller); with planes != NULL also writes the working copy.
+ *   hg_idt_hist           step 2 of nrot <= hg_idt_target_chunk(bins) rotations with the given range sets, added to
+ *                         hist[nrot][3 * bins].  Pixels with pix_stride 1, a 16-byte aligned base and a chan_stride that is a
+ *                         multiple of 4 and at least hg_idt_plane_stride(n) (the planes) are read 16 bytes per lane.  blocks: 0 =
+ *                         hg_idt_blocks(n), else that many workgroups (at most 2048).
+ *   hg_idt_table          step 3 from a source and a target histogram and the target's range set, one workgroup per axis;
+ *                         then zeroes src_hist (clear_src_hist != 0) and clears the range set next_range (unless NULL).
+ *   hg_idt_apply          steps 4, 5 and the update on the planes with the source's range set `range` and the map.  With
+ *                         rotation_next != NULL the planes are updated in place and the range of the updated pixels'
+ *                         projections with rotation_next is reduced into next_range (cleared before) in the same pass;
+ *                         with rotation_next == NULL it is the last rotation: the clipped result goes to `out`.
+ *   hg_idt_target_tables  range sets and histograms of the target for all rotations (clears them first): one pass for the
+ *                         ranges, then one histogram launch per hg_idt_target_chunk(bins) rotations.
+ *   hg_idt_run            the whole transfer, enqueued on `stream` with no host read-back: target tables, one range pass over
+ *                         the source (which also makes the planes), then hist, table, apply per rotation (per rotation the
+ *                         source is read twice and written once: 36 bytes per pixel). */
+int hg_idt_block_pixels(void);
+int hg_idt_max_bins(void);
+int hg_idt_group_pixels(void);
+int hg_idt_target_chunk(int32_t bins);
+int hg_idt_blocks(int64_t n);
+int64_t hg_idt_plane_stride(int64_t n);
+size_t hg_idt_workspace_bytes(int64_t n_src, int64_t n_tgt, int32_t iterations, int32_t bins);
+int hg_idt_clear(uint32_t *ranges, int64_t n_ranges, uint64_t *hist, int64_t n_counters, void *stream);
+int hg_idt_range(const float *x, int64_t n, int64_t pix_stride, int64_t chan_stride, const float *rotations, int32_t nrot,
+                 uint32_t *ranges, float *planes, void *stream);
+int hg_idt_hist(const float *x, int64_t n, int64_t pix_stride, int64_t chan_stride, const float *rotations, int32_t nrot,
+                int32_t bins, const uint32_t *ranges, uint64_t *hist, int32_t blocks, void *stream);
+int hg_idt_table(uint64_t *src_hist, const uint64_t *tgt_hist, const uint32_t *tgt_range, int32_t bins, float *map,
+                 uint32_t *next_range, int32_t clear_src_hist, void *stream);
+int hg_idt_apply(float *planes, int64_t n, const float *rotation, const float *rotation_next, int32_t bins,
+                 const uint32_t *range, const float *map, float relaxation, uint32_t *next_range, void *out, int32_t out_u8,
+                 void *stream);
+int hg_idt_target_tables(const float *target, int64_t n, int64_t pix_stride, int64_t chan_stride, const float *rotations,
+                         int32_t iterations, int32_t bins, uint32_t *tgt_range, uint64_t *tgt_hist, void *stream);
+int hg_idt_run(const float *source, int64_t n_src, int64_t src_pix_stride, int64_t src_chan_stride, const float *target,
+               int64_t n_tgt, int64_t tgt_pix_stride, int64_t tgt_chan_stride, const float *rotations, int32_t iterations,
+               int32_t bins, float relaxation, void *out, int32_t out_u8, void *workspace, size_t workspace_bytes,
+               void *stream);
 
 #ifdef __cplusplus
 }
