@@ -93,263 +93,148 @@ class GlinLayer(ctypes.Structure):
                 ('gw', ctypes.c_void_p), ('gb', ctypes.c_void_p), ('N', ctypes.c_int32), ('group', ctypes.c_int32)]
 
 
+def _signatures():
+    """name -> (restype, [argtypes]) of every symbol the headers under include/ declare, grouped by header.  _load applies it
+    and EXPORTS is its keys: tests/test_cabi_cpu.py holds it against the prototypes."""
+    ci, vp, sz, i32, i64, f32 = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    P = ctypes.POINTER
+    PP, GL = P(HgHistParams), P(GlinLayer)
+    return {
+        # include/hg_hist.h
+        'hg_version': (ci, []),
+        'hg_error_string': (ctypes.c_char_p, [ci]),
+        'hg_rgbuv_hist_workspace_bytes': (ci, [PP, P(sz), P(sz)]),
+        'hg_rgbuv_hist_uses_proj_cache': (ci, [PP]),
+        'hg_rgbuv_hist_route': (ci, [PP, ci, P(HgHistRoute)]),
+        'hg_rgbuv_hist_fwd': (ci, [PP, vp, vp, vp, vp, sz, vp]),
+        'hg_rgbuv_hist_bwd': (ci, [PP, vp, vp, vp, vp, vp, vp, sz, vp]),
+        'hg_rgbuv_hist_bwd_w_workspace_bytes': (ci, [PP, P(sz)]),
+        'hg_rgbuv_hist_bwd_w': (ci, [PP, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        'hg_hellinger_workspace_bytes': (sz, [i64]),
+        'hg_hellinger_fwd_bwd': (ci, [vp, vp, i64, i32, f32, vp, vp, vp, sz, vp]),
+        'hg_selftest_fastlog': (ci, [vp, vp]),
+        # include/hg_nets.h
+        'hg_modulate_fwd': (ci, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        'hg_modulate_bwd': (ci, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+        'hg_nets_workspace_bytes': (sz, [i32, i32, i32, i32]),
+        'hg_torgb_fwd': (ci, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        'hg_torgb_bwd_workspace_bytes': (sz, [i32, i32, i32, i32]),
+        'hg_torgb_bwd': (ci, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+        'hg_gstage_bwd_workspace_bytes': (sz, [i32, i32, i32, i32]),
+        'hg_gstage_bwd': (ci, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                               i32, vp, sz, vp]),
+        'hg_channel_sum': (ci, [vp, vp, i32, i32, i32, vp, sz, vp]),
+        'hg_demod_noise_lrelu_fwd': (ci, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        'hg_demod_noise_lrelu_bwd': (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+        'hg_noise_grad': (ci, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        'hg_lrelu_bwd_channel_sum': (ci, [vp, vp, f32, vp, vp, i32, i32, i32, vp, sz, vp]),
+        'hg_demod_style_grad_workspace_bytes': (sz, [i32, i32, i32]),
+        'hg_demod_style_grad': (ci, [vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+        'hg_demod_weight_term': (ci, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        'hg_diffgrad_step': (ci, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, vp]),
+        'hg_diffgrad_step_size': (f32, [f32, f32, f32, i32]),
+        'hg_diffgrad_step_dev': (ci, [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, vp]),
+        'hg_ema_update': (ci, [vp, vp, i64, f32, vp]),
+        # include/hg_conv.h
+        'hg_conv_packed_elems': (sz, [i32, i32, i32, i32]),
+        'hg_conv_pack_weights': (ci, [vp, vp, i32, i32, i32, i32, vp]),
+        'hg_conv_pack_weights_both': (ci, [vp, vp, vp, i32, i32, i32, vp]),
+        'hg_conv2d_fwd': (ci, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+        'hg_conv2d_fwd_add': (ci, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+        'hg_modconv2d_fwd': (ci, [vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+        'hg_conv2d_workspace_bytes': (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
+        'hg_conv_pack_blocks': (i32, [i32, i32]),
+        'hg_conv_pack_weights_multi': (ci, [vp, i32, i32, vp]),
+        'hg_conv2d_plan': (ci, [i32, i32, i32, i32, i32, i32, i32, i32, P(i32)]),
+        'hg_conv2d_route': (ci, [P(HgConvQuery), P(HgConvRoute)]),
+        'hg_conv2d_dgrad': (ci, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+        'hg_conv2d_wgrad_workspace_bytes': (sz, [i32, i32, i32, i32, i32, i32, i32]),
+        'hg_conv2d_wgrad': (ci, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+        # include/hg_recolor.h
+        'hg_instnorm_workspace_bytes': (sz, [i64]),
+        'hg_instnorm_lrelu_fwd': (ci, [vp, vp, vp, i64, i32, f32, f32, vp, sz, vp]),
+        'hg_instnorm_lrelu_bwd': (ci, [vp, vp, vp, vp, i64, i32, f32, vp, sz, vp]),
+        'hg_stencil3': (ci, [vp, vp, P(f32), i32, i32, i32, i32, i32, vp]),
+        'hg_depthwise_valid': (ci, [vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+        # include/hg_linear.h
+        'hg_grouped_linear_fwd': (ci, [GL, i32, i32, i32, vp]),
+        'hg_grouped_linear_bwd_input_workspace_bytes': (sz, [GL, i32, i32, i32]),
+        'hg_grouped_linear_bwd_input': (ci, [GL, i32, P(vp), i32, i32, i32, vp, sz, vp]),
+        'hg_grouped_linear_bwd_params': (ci, [GL, i32, i32, i32, vp]),
+        # include/hg_wino.h
+        'hg_wino_supported': (ci, [i32, i32, i32, i32, i32]),
+        'hg_wino_packed_elems': (sz, [i32, i32, i32]),
+        'hg_wino_pack_weights': (ci, [vp, vp, i32, i32, i32, vp]),
+        'hg_wino_pack_blocks': (i32, [i32, i32, i32, i32]),
+        'hg_wino_pack_weights_multi': (ci, [vp, i32, i32, vp]),
+        'hg_wino_workspace_bytes': (sz, [i32, i32, i32, i32, i32]),
+        'hg_wino_conv2d': (ci, [vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+        'hg_wino_wgrad_supported': (ci, [i32, i32, i32, i32, i32]),
+        'hg_wino_wgrad_workspace_bytes': (sz, [i32, i32, i32, i32, i32]),
+        'hg_wino_wgrad': (ci, [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+        'hg_wino_route': (ci, [P(HgWinoQuery), P(HgWinoRoute)]),
+        'hg_wino_wgrad_route': (ci, [P(HgWinoQuery), P(HgWinoWgradRoute)]),
+        # include/hg_augment.h
+        'hg_augment_spatial': (ci, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        'hg_augment_workspace_bytes': (sz, [i32]),
+        'hg_sample_mean': (ci, [vp, vp, i32, i64, vp, sz, vp]),
+        'hg_augment_color': (ci, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        # include/hg_post.h
+        'hg_resize_axis': (ci, [vp, i32, i64, i64, i64, i32, vp, i32, i64, i64, i64, i32, i32, i32, i32, vp, vp, i32, i32,
+                                vp]),
+        'hg_pyr_down': (ci, [vp, vp, i32, i32, i32, vp]),
+        'hg_pyr_up_add': (ci, [vp, vp, vp, f32, vp, vp, f32, vp, i32, i32, i32, vp]),
+        'hg_color_moments_workspace_bytes': (sz, [i64]),
+        'hg_color_moments': (ci, [vp, i64, i64, i64, vp, vp, sz, vp]),
+        'hg_color_affine': (ci, [vp, i64, i64, i64, P(f32), vp, i32, vp]),
+        'hg_u8_hwc_to_f32': (ci, [vp, vp, i32, i64, vp]),
+        'hg_f32_to_u8_hwc': (ci, [vp, vp, i32, i64, vp]),
+        'hg_bgu_normal_workspace_bytes': (sz, [i32, i32, i32]),
+        'hg_bgu_normal': (ci, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+        'hg_bgu_slice': (ci, [vp, i32, i32, i32, vp, i64, i64, i64, vp, i32, i32, i32, vp]),
+        'hg_srgb_to_lab': (ci, [vp, i64, i64, i64, i64, vp, i32, i32, i32, vp]),
+        'hg_lab_to_srgb': (ci, [vp, i64, i64, i64, i64, vp, i32, i32, i32, vp]),
+        'hg_delta_e_workspace_bytes': (sz, [i32, i32, i32]),
+        'hg_delta_e': (ci, [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, vp, i64, i64, i64, i32, vp, vp, vp, i32, i32,
+                            i32, vp, sz, vp]),
+        'hg_ssim_tile': (ci, []),
+        'hg_ssim_finish_threads': (ci, []),
+        'hg_ssim_workspace_bytes': (sz, [i32, i32, i32]),
+        'hg_ssim_fwd': (ci, [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp, sz,
+                             vp]),
+        'hg_ssim_bwd': (ci, [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, i32, i32, i32, vp]),
+        'hg_idt_block_pixels': (ci, []),
+        'hg_idt_max_bins': (ci, []),
+        'hg_idt_group_pixels': (ci, []),
+        'hg_idt_target_chunk': (ci, [i32]),
+        'hg_idt_blocks': (ci, [i64]),
+        'hg_idt_plane_stride': (i64, [i64]),
+        'hg_idt_workspace_bytes': (sz, [i64, i64, i32, i32]),
+        'hg_idt_clear': (ci, [vp, i64, vp, i64, vp]),
+        'hg_idt_range': (ci, [vp, i64, i64, i64, vp, i32, vp, vp, vp]),
+        'hg_idt_hist': (ci, [vp, i64, i64, i64, vp, i32, i32, vp, vp, i32, vp]),
+        'hg_idt_table': (ci, [vp, vp, vp, i32, vp, vp, i32, vp]),
+        'hg_idt_apply': (ci, [vp, i64, vp, vp, i32, vp, vp, f32, vp, vp, i32, vp]),
+        'hg_idt_target_tables': (ci, [vp, i64, i64, i64, vp, i32, i32, vp, vp, vp]),
+        'hg_idt_run': (ci, [vp, i64, i64, i64, vp, i64, i64, i64, vp, i32, i32, f32, vp, i32, vp, sz, vp]),
+    }
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
             f'{LIB_PATH} not found: the gfx950 HIP library has not been built. '
             f'Run `python -m histogan_amd.build` (needs hipcc). There is no CPU/PyTorch fallback.')
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    vp, sz, i32, i64, f32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    PP = ctypes.POINTER(HgHistParams)
-    lib.hg_version.restype = ctypes.c_int
-    lib.hg_version.argtypes = []
-    lib.hg_error_string.restype = ctypes.c_char_p
-    lib.hg_error_string.argtypes = [ctypes.c_int]
-    lib.hg_rgbuv_hist_workspace_bytes.restype = ctypes.c_int
-    lib.hg_rgbuv_hist_workspace_bytes.argtypes = [PP, ctypes.POINTER(sz), ctypes.POINTER(sz)]
-    lib.hg_rgbuv_hist_uses_proj_cache.restype = ctypes.c_int
-    lib.hg_rgbuv_hist_uses_proj_cache.argtypes = [PP]
-    lib.hg_rgbuv_hist_route.restype = ctypes.c_int
-    lib.hg_rgbuv_hist_route.argtypes = [PP, ctypes.c_int, ctypes.POINTER(HgHistRoute)]
-    lib.hg_rgbuv_hist_fwd.restype = ctypes.c_int
-    lib.hg_rgbuv_hist_fwd.argtypes = [PP, vp, vp, vp, vp, sz, vp]
-    lib.hg_rgbuv_hist_bwd.restype = ctypes.c_int
-    lib.hg_rgbuv_hist_bwd.argtypes = [PP, vp, vp, vp, vp, vp, vp, sz, vp]
-    lib.hg_rgbuv_hist_bwd_w_workspace_bytes.restype = ctypes.c_int
-    lib.hg_rgbuv_hist_bwd_w_workspace_bytes.argtypes = [PP, ctypes.POINTER(sz)]
-    lib.hg_rgbuv_hist_bwd_w.restype = ctypes.c_int
-    lib.hg_rgbuv_hist_bwd_w.argtypes = [PP, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    lib.hg_hellinger_workspace_bytes.restype = sz
-    lib.hg_hellinger_workspace_bytes.argtypes = [i64]
-    lib.hg_hellinger_fwd_bwd.restype = ctypes.c_int
-    lib.hg_hellinger_fwd_bwd.argtypes = [vp, vp, i64, i32, f32, vp, vp, vp, sz, vp]
-    lib.hg_selftest_fastlog.restype = ctypes.c_int
-    lib.hg_selftest_fastlog.argtypes = [vp, vp]
-    # include/hg_nets.h
-    lib.hg_modulate_fwd.restype = ctypes.c_int
-    lib.hg_modulate_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.hg_modulate_bwd.restype = ctypes.c_int
-    lib.hg_modulate_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]
-    lib.hg_nets_workspace_bytes.restype = sz
-    lib.hg_nets_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    lib.hg_torgb_fwd.restype = ctypes.c_int
-    lib.hg_torgb_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.hg_torgb_bwd_workspace_bytes.restype = sz
-    lib.hg_torgb_bwd_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    lib.hg_torgb_bwd.restype = ctypes.c_int
-    lib.hg_torgb_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]
-    lib.hg_gstage_bwd_workspace_bytes.restype = sz
-    lib.hg_gstage_bwd_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    lib.hg_gstage_bwd.restype = ctypes.c_int
-    lib.hg_gstage_bwd.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32,
-                                  vp, sz, vp]
-    lib.hg_channel_sum.restype = ctypes.c_int
-    lib.hg_channel_sum.argtypes = [vp, vp, i32, i32, i32, vp, sz, vp]
-    lib.hg_demod_noise_lrelu_fwd.restype = ctypes.c_int
-    lib.hg_demod_noise_lrelu_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.hg_demod_noise_lrelu_bwd.restype = ctypes.c_int
-    lib.hg_demod_noise_lrelu_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]
-    lib.hg_noise_grad.restype = ctypes.c_int
-    lib.hg_noise_grad.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.hg_lrelu_bwd_channel_sum.restype = ctypes.c_int
-    lib.hg_lrelu_bwd_channel_sum.argtypes = [vp, vp, f32, vp, vp, i32, i32, i32, vp, sz, vp]
-    lib.hg_demod_style_grad_workspace_bytes.restype = ctypes.c_size_t
-    lib.hg_demod_style_grad_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.hg_demod_style_grad.restype = ctypes.c_int
-    lib.hg_demod_style_grad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
-    lib.hg_demod_weight_term.restype = ctypes.c_int
-    lib.hg_demod_weight_term.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.hg_diffgrad_step.restype = ctypes.c_int
-    lib.hg_diffgrad_step.argtypes = [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, vp]
-    lib.hg_diffgrad_step_size.restype = f32
-    lib.hg_diffgrad_step_size.argtypes = [f32, f32, f32, i32]
-    lib.hg_diffgrad_step_dev.restype = ctypes.c_int
-    lib.hg_diffgrad_step_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, vp]
-    lib.hg_ema_update.restype = ctypes.c_int
-    lib.hg_ema_update.argtypes = [vp, vp, i64, f32, vp]
-    # include/hg_conv.h
-    lib.hg_conv_packed_elems.restype = sz
-    lib.hg_conv_packed_elems.argtypes = [i32, i32, i32, i32]
-    lib.hg_conv_pack_weights.restype = ctypes.c_int
-    lib.hg_conv_pack_weights.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    lib.hg_conv_pack_weights_both.restype = ctypes.c_int
-    lib.hg_conv_pack_weights_both.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    lib.hg_conv2d_fwd.restype = ctypes.c_int
-    lib.hg_conv2d_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
-    lib.hg_conv2d_fwd_add.restype = ctypes.c_int
-    lib.hg_conv2d_fwd_add.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
-    lib.hg_modconv2d_fwd.restype = ctypes.c_int
-    lib.hg_modconv2d_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
-    lib.hg_conv2d_workspace_bytes.restype = sz
-    lib.hg_conv2d_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32]
-    lib.hg_conv_pack_blocks.restype = ctypes.c_int32
-    lib.hg_conv_pack_blocks.argtypes = [i32, i32]
-    lib.hg_conv_pack_weights_multi.restype = ctypes.c_int
-    lib.hg_conv_pack_weights_multi.argtypes = [vp, i32, i32, vp]
-    lib.hg_conv2d_plan.restype = ctypes.c_int
-    lib.hg_conv2d_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
-    lib.hg_conv2d_route.restype = ctypes.c_int
-    lib.hg_conv2d_route.argtypes = [ctypes.POINTER(HgConvQuery), ctypes.POINTER(HgConvRoute)]
-    lib.hg_conv2d_dgrad.restype = ctypes.c_int
-    lib.hg_conv2d_dgrad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
-    lib.hg_conv2d_wgrad_workspace_bytes.restype = sz
-    lib.hg_conv2d_wgrad_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32]
-    lib.hg_conv2d_wgrad.restype = ctypes.c_int
-    lib.hg_conv2d_wgrad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
-    # include/hg_recolor.h
-    lib.hg_instnorm_workspace_bytes.restype = sz
-    lib.hg_instnorm_workspace_bytes.argtypes = [i64]
-    lib.hg_instnorm_lrelu_fwd.restype = ctypes.c_int
-    lib.hg_instnorm_lrelu_fwd.argtypes = [vp, vp, vp, i64, i32, f32, f32, vp, sz, vp]
-    lib.hg_instnorm_lrelu_bwd.restype = ctypes.c_int
-    lib.hg_instnorm_lrelu_bwd.argtypes = [vp, vp, vp, vp, i64, i32, f32, vp, sz, vp]
-    lib.hg_stencil3.restype = ctypes.c_int
-    lib.hg_stencil3.argtypes = [vp, vp, ctypes.POINTER(f32), i32, i32, i32, i32, i32, vp]
-    lib.hg_depthwise_valid.restype = ctypes.c_int
-    lib.hg_depthwise_valid.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp]
-    # include/hg_linear.h
-    GL = ctypes.POINTER(GlinLayer)
-    lib.hg_grouped_linear_fwd.restype = ctypes.c_int
-    lib.hg_grouped_linear_fwd.argtypes = [GL, i32, i32, i32, vp]
-    lib.hg_grouped_linear_bwd_input_workspace_bytes.restype = sz
-    lib.hg_grouped_linear_bwd_input_workspace_bytes.argtypes = [GL, i32, i32, i32]
-    lib.hg_grouped_linear_bwd_input.restype = ctypes.c_int
-    lib.hg_grouped_linear_bwd_input.argtypes = [GL, i32, ctypes.POINTER(vp), i32, i32, i32, vp, sz, vp]
-    lib.hg_grouped_linear_bwd_params.restype = ctypes.c_int
-    lib.hg_grouped_linear_bwd_params.argtypes = [GL, i32, i32, i32, vp]
-    # include/hg_wino.h
-    lib.hg_wino_supported.restype = ctypes.c_int
-    lib.hg_wino_supported.argtypes = [i32, i32, i32, i32, i32]
-    lib.hg_wino_packed_elems.restype = sz
-    lib.hg_wino_packed_elems.argtypes = [i32, i32, i32]
-    lib.hg_wino_pack_weights.restype = ctypes.c_int
-    lib.hg_wino_pack_weights.argtypes = [vp, vp, i32, i32, i32, vp]
-    lib.hg_wino_pack_blocks.restype = ctypes.c_int32
-    lib.hg_wino_pack_blocks.argtypes = [i32, i32, i32, i32]
-    lib.hg_wino_pack_weights_multi.restype = ctypes.c_int
-    lib.hg_wino_pack_weights_multi.argtypes = [vp, i32, i32, vp]
-    lib.hg_wino_workspace_bytes.restype = sz
-    lib.hg_wino_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
-    lib.hg_wino_conv2d.restype = ctypes.c_int
-    lib.hg_wino_conv2d.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, i32, i32, i32, i32, i32, vp, sz, vp]
-    lib.hg_wino_wgrad_supported.restype = ctypes.c_int
-    lib.hg_wino_wgrad_supported.argtypes = [i32, i32, i32, i32, i32]
-    lib.hg_wino_wgrad_workspace_bytes.restype = sz
-    lib.hg_wino_wgrad_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
-    lib.hg_wino_wgrad.restype = ctypes.c_int
-    lib.hg_wino_wgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]
-    lib.hg_wino_route.restype = ctypes.c_int
-    lib.hg_wino_route.argtypes = [ctypes.POINTER(HgWinoQuery), ctypes.POINTER(HgWinoRoute)]
-    lib.hg_wino_wgrad_route.restype = ctypes.c_int
-    lib.hg_wino_wgrad_route.argtypes = [ctypes.POINTER(HgWinoQuery), ctypes.POINTER(HgWinoWgradRoute)]
-    # include/hg_augment.h
-    lib.hg_augment_spatial.restype = ctypes.c_int
-    lib.hg_augment_spatial.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.hg_augment_workspace_bytes.restype = sz
-    lib.hg_augment_workspace_bytes.argtypes = [i32]
-    lib.hg_sample_mean.restype = ctypes.c_int
-    lib.hg_sample_mean.argtypes = [vp, vp, i32, i64, vp, sz, vp]
-    lib.hg_augment_color.restype = ctypes.c_int
-    lib.hg_augment_color.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    # include/hg_post.h
-    lib.hg_resize_axis.restype = ctypes.c_int
-    lib.hg_resize_axis.argtypes = [vp, i32, i64, i64, i64, i32, vp, i32, i64, i64, i64, i32, i32, i32, i32, vp, vp, i32,
-                                   i32, vp]
-    lib.hg_pyr_down.restype = ctypes.c_int
-    lib.hg_pyr_down.argtypes = [vp, vp, i32, i32, i32, vp]
-    lib.hg_pyr_up_add.restype = ctypes.c_int
-    lib.hg_pyr_up_add.argtypes = [vp, vp, vp, f32, vp, vp, f32, vp, i32, i32, i32, vp]
-    lib.hg_color_moments_workspace_bytes.restype = sz
-    lib.hg_color_moments_workspace_bytes.argtypes = [i64]
-    lib.hg_color_moments.restype = ctypes.c_int
-    lib.hg_color_moments.argtypes = [vp, i64, i64, i64, vp, vp, sz, vp]
-    lib.hg_color_affine.restype = ctypes.c_int
-    lib.hg_color_affine.argtypes = [vp, i64, i64, i64, ctypes.POINTER(f32), vp, i32, vp]
-    lib.hg_u8_hwc_to_f32.restype = ctypes.c_int
-    lib.hg_u8_hwc_to_f32.argtypes = [vp, vp, i32, i64, vp]
-    lib.hg_f32_to_u8_hwc.restype = ctypes.c_int
-    lib.hg_f32_to_u8_hwc.argtypes = [vp, vp, i32, i64, vp]
-    lib.hg_bgu_normal_workspace_bytes.restype = sz
-    lib.hg_bgu_normal_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.hg_bgu_normal.restype = ctypes.c_int
-    lib.hg_bgu_normal.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
-    lib.hg_bgu_slice.restype = ctypes.c_int
-    lib.hg_bgu_slice.argtypes = [vp, i32, i32, i32, vp, i64, i64, i64, vp, i32, i32, i32, vp]
-    lib.hg_srgb_to_lab.restype = ctypes.c_int
-    lib.hg_srgb_to_lab.argtypes = [vp, i64, i64, i64, i64, vp, i32, i32, i32, vp]
-    lib.hg_lab_to_srgb.restype = ctypes.c_int
-    lib.hg_lab_to_srgb.argtypes = [vp, i64, i64, i64, i64, vp, i32, i32, i32, vp]
-    lib.hg_delta_e_workspace_bytes.restype = sz
-    lib.hg_delta_e_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.hg_delta_e.restype = ctypes.c_int
-    lib.hg_delta_e.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, vp, i64, i64, i64, i32, vp, vp, vp, i32, i32, i32,
-                               vp, sz, vp]
-    lib.hg_ssim_tile.restype = ctypes.c_int
-    lib.hg_ssim_tile.argtypes = []
-    lib.hg_ssim_finish_threads.restype = ctypes.c_int
-    lib.hg_ssim_finish_threads.argtypes = []
-    lib.hg_ssim_workspace_bytes.restype = sz
-    lib.hg_ssim_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.hg_ssim_fwd.restype = ctypes.c_int
-    lib.hg_ssim_fwd.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
-    lib.hg_ssim_bwd.restype = ctypes.c_int
-    lib.hg_ssim_bwd.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, i32, i32, i32, vp]
-    lib.hg_idt_block_pixels.restype = ctypes.c_int
-    lib.hg_idt_block_pixels.argtypes = []
-    lib.hg_idt_max_bins.restype = ctypes.c_int
-    lib.hg_idt_max_bins.argtypes = []
-    lib.hg_idt_group_pixels.restype = ctypes.c_int
-    lib.hg_idt_group_pixels.argtypes = []
-    lib.hg_idt_target_chunk.restype = ctypes.c_int
-    lib.hg_idt_target_chunk.argtypes = [i32]
-    lib.hg_idt_blocks.restype = ctypes.c_int
-    lib.hg_idt_blocks.argtypes = [i64]
-    lib.hg_idt_plane_stride.restype = i64
-    lib.hg_idt_plane_stride.argtypes = [i64]
-    lib.hg_idt_workspace_bytes.restype = sz
-    lib.hg_idt_workspace_bytes.argtypes = [i64, i64, i32, i32]
-    lib.hg_idt_clear.restype = ctypes.c_int
-    lib.hg_idt_clear.argtypes = [vp, i64, vp, i64, vp]
-    lib.hg_idt_range.restype = ctypes.c_int
-    lib.hg_idt_range.argtypes = [vp, i64, i64, i64, vp, i32, vp, vp, vp]
-    lib.hg_idt_hist.restype = ctypes.c_int
-    lib.hg_idt_hist.argtypes = [vp, i64, i64, i64, vp, i32, i32, vp, vp, i32, vp]
-    lib.hg_idt_table.restype = ctypes.c_int
-    lib.hg_idt_table.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp]
-    lib.hg_idt_apply.restype = ctypes.c_int
-    lib.hg_idt_apply.argtypes = [vp, i64, vp, vp, i32, vp, vp, f32, vp, vp, i32, vp]
-    lib.hg_idt_target_tables.restype = ctypes.c_int
-    lib.hg_idt_target_tables.argtypes = [vp, i64, i64, i64, vp, i32, i32, vp, vp, vp]
-    lib.hg_idt_run.restype = ctypes.c_int
-    lib.hg_idt_run.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i32, i32, f32, vp, i32, vp, sz, vp]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 
+_SIGNATURES = _signatures()
 lib = _load()
-
-# every symbol include/hg_hist.h, hg_nets.h, hg_conv.h, hg_recolor.h, hg_augment.h, hg_linear.h, hg_wino.h and hg_post.h
-# declare
-EXPORTS = ('hg_version', 'hg_error_string', 'hg_rgbuv_hist_workspace_bytes', 'hg_rgbuv_hist_uses_proj_cache', 'hg_rgbuv_hist_route', 'hg_rgbuv_hist_fwd',
-           'hg_rgbuv_hist_bwd', 'hg_rgbuv_hist_bwd_w_workspace_bytes', 'hg_rgbuv_hist_bwd_w', 'hg_hellinger_workspace_bytes', 'hg_hellinger_fwd_bwd', 'hg_selftest_fastlog',
-           'hg_modulate_fwd', 'hg_modulate_bwd', 'hg_demod_noise_lrelu_fwd', 'hg_demod_noise_lrelu_bwd',
-           'hg_diffgrad_step', 'hg_diffgrad_step_size', 'hg_diffgrad_step_dev', 'hg_ema_update', 'hg_nets_workspace_bytes', 'hg_channel_sum', 'hg_lrelu_bwd_channel_sum', 'hg_demod_weight_term', 'hg_demod_style_grad', 'hg_demod_style_grad_workspace_bytes',
-           'hg_conv_packed_elems', 'hg_conv_pack_weights', 'hg_conv_pack_weights_both', 'hg_conv_pack_blocks', 'hg_conv_pack_weights_multi', 'hg_conv2d_fwd', 'hg_conv2d_fwd_add', 'hg_modconv2d_fwd', 'hg_conv2d_workspace_bytes', 'hg_conv2d_plan', 'hg_conv2d_route', 'hg_conv2d_dgrad',
-           'hg_conv2d_wgrad_workspace_bytes',
-           'hg_conv2d_wgrad',
-           'hg_instnorm_workspace_bytes', 'hg_instnorm_lrelu_fwd', 'hg_instnorm_lrelu_bwd', 'hg_stencil3',
-           'hg_depthwise_valid', 'hg_augment_spatial', 'hg_augment_workspace_bytes', 'hg_sample_mean',
-           'hg_augment_color', 'hg_grouped_linear_fwd', 'hg_grouped_linear_bwd_input_workspace_bytes',
-           'hg_grouped_linear_bwd_input', 'hg_grouped_linear_bwd_params',
-           'hg_wino_supported', 'hg_wino_packed_elems', 'hg_wino_pack_weights', 'hg_wino_pack_blocks', 'hg_wino_pack_weights_multi', 'hg_wino_workspace_bytes', 'hg_wino_conv2d',
-           'hg_wino_wgrad_supported', 'hg_wino_wgrad_workspace_bytes', 'hg_wino_wgrad', 'hg_wino_route', 'hg_wino_wgrad_route',
-           'hg_torgb_fwd', 'hg_torgb_bwd_workspace_bytes', 'hg_torgb_bwd', 'hg_gstage_bwd_workspace_bytes', 'hg_gstage_bwd', 'hg_noise_grad',
-           'hg_resize_axis', 'hg_pyr_down', 'hg_pyr_up_add', 'hg_color_moments_workspace_bytes', 'hg_color_moments',
-           'hg_color_affine', 'hg_u8_hwc_to_f32', 'hg_f32_to_u8_hwc', 'hg_bgu_normal_workspace_bytes', 'hg_bgu_normal',
-           'hg_bgu_slice', 'hg_srgb_to_lab', 'hg_lab_to_srgb', 'hg_delta_e_workspace_bytes', 'hg_delta_e',
-           'hg_ssim_tile', 'hg_ssim_finish_threads', 'hg_ssim_workspace_bytes', 'hg_ssim_fwd', 'hg_ssim_bwd',
-           'hg_idt_block_pixels', 'hg_idt_max_bins', 'hg_idt_group_pixels', 'hg_idt_target_chunk', 'hg_idt_blocks', 'hg_idt_plane_stride',
-           'hg_idt_workspace_bytes', 'hg_idt_clear', 'hg_idt_range', 'hg_idt_hist', 'hg_idt_table', 'hg_idt_apply',
-           'hg_idt_target_tables', 'hg_idt_run')
+EXPORTS = tuple(_SIGNATURES)
 
 
 class HgError(RuntimeError):

@@ -9,36 +9,15 @@
 //   k_de_finish  one block per sample: sums the partials in the same fixed order, mean = sum w dE / sum w
 //
 // Everything per pixel is fp64 and rounded once; no atomics, so repeats are bit-identical.
-#include "hg_common.h"
-#include "../../include/hg_hist.h"
+#include "hg_host.h"
 #include "../../include/hg_post.h"
 #include "hg_lab.h"
 
 namespace {
 
-constexpr int DE_THREADS = 256;
+constexpr int DE_THREADS = 256;   // hg_block_sum_256, hg_block_partials_sum_256
 constexpr double kDeg = 57.295779513082320877, kRad = 1.0 / kDeg;
 constexpr double k25p7 = 6103515625.0;   // 25^7
-
-// Block-wide fp64 sum for blockDim.x == 256; the result is valid in every thread and its order is fixed.
-__device__ __forceinline__ double block_sum_f64(double v, double *sm4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sm4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = (sm4[0] + sm4[1]) + (sm4[2] + sm4[3]);
-  __syncthreads();
-  return r;
-}
-
-// sum of n partials in a fixed order: thread t takes t, t + 256, ...; then block_sum_f64
-__device__ __forceinline__ double sample_sum(const double *__restrict__ part, int n, double *sm4) {
-  double s = 0.0;
-  for (int k = threadIdx.x; k < n; k += DE_THREADS) s += part[k];
-  return block_sum_f64(s, sm4);
-}
-
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
 
 // ---- forward-mode dual number: a value and N partials (N = 0: the plain value, for the instantiations without grad) -----
 template <int N>
@@ -201,9 +180,9 @@ __global__ __launch_bounds__(DE_THREADS) void k_de_wsum(const float *__restrict_
   double w = 0.0;
   if (n < HW) {
     const long long y = n / W, x = n - y * W;
-    w = (double)clamp01(weight[blockIdx.y * ws_b + y * ws_h + x * ws_w]);
+    w = (double)hg_clamp01(weight[blockIdx.y * ws_b + y * ws_h + x * ws_w]);
   }
-  const double s = block_sum_f64(w, sm4);
+  const double s = hg_block_sum_256(w, sm4);
   if (threadIdx.x == 0) wpart[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
@@ -221,7 +200,7 @@ __global__ __launch_bounds__(DE_THREADS) void k_delta_e(const float *__restrict_
   const int b = blockIdx.y;
   double inv_sw = 0.0;
   if constexpr (GRAD) {
-    const double sw = weight ? sample_sum(wpart + (size_t)b * gridDim.x, (int)gridDim.x, sm4) : (double)HW;
+    const double sw = weight ? hg_block_partials_sum_256(wpart + (size_t)b * gridDim.x, (int)gridDim.x, sm4) : (double)HW;
     inv_sw = sw > 0.0 ? 1.0 / sw : 0.0;
   }
   double we = 0.0;
@@ -229,9 +208,9 @@ __global__ __launch_bounds__(DE_THREADS) void k_delta_e(const float *__restrict_
     const long long y = n / W, x = n - y * W;
     const float *q1 = x1 + b * s1_b + y * s1_h + x * s1_w, *q2 = x2 + b * s2_b + y * s2_h + x * s2_w;
     const float r1[3] = {q1[0], q1[s1_c], q1[2 * s1_c]};
-    const double c1[3] = {(double)clamp01(r1[0]), (double)clamp01(r1[1]), (double)clamp01(r1[2])};
-    const double c2[3] = {(double)clamp01(q2[0]), (double)clamp01(q2[s2_c]), (double)clamp01(q2[2 * s2_c])};
-    const double w = weight ? (double)clamp01(weight[b * ws_b + y * ws_h + x * ws_w]) : 1.0;
+    const double c1[3] = {(double)hg_clamp01(r1[0]), (double)hg_clamp01(r1[1]), (double)hg_clamp01(r1[2])};
+    const double c2[3] = {(double)hg_clamp01(q2[0]), (double)hg_clamp01(q2[s2_c]), (double)hg_clamp01(q2[2 * s2_c])};
+    const double w = weight ? (double)hg_clamp01(weight[b * ws_b + y * ws_h + x * ws_w]) : 1.0;
     double p1[3], p2[3], dlin[3], dfp[3], unused0[3], unused1[3];
     hg_lab::srgb_to_lab_f64<GRAD>(c1, p1, dlin, dfp);
     hg_lab::srgb_to_lab_f64<false>(c2, p2, unused0, unused1);
@@ -253,7 +232,7 @@ __global__ __launch_bounds__(DE_THREADS) void k_delta_e(const float *__restrict_
       for (int j = 0; j < 3; ++j) g[j * HW] = (r1[j] >= 0.f && r1[j] <= 1.f) ? (float)(sc * dc[j]) : 0.f;   // aten's clamp mask
     }
   }
-  const double s = block_sum_f64(we, sm4);
+  const double s = hg_block_sum_256(we, sm4);
   if (threadIdx.x == 0) epart[(size_t)b * gridDim.x + blockIdx.x] = s;
 }
 
@@ -261,15 +240,15 @@ __global__ __launch_bounds__(DE_THREADS) void k_delta_e(const float *__restrict_
 __global__ __launch_bounds__(DE_THREADS) void k_de_finish(const double *__restrict__ epart, const double *__restrict__ wpart,
                                                           int nb, double hw, float *__restrict__ mean) {
   __shared__ double sm4[4];
-  const double se = sample_sum(epart + (size_t)blockIdx.x * nb, nb, sm4);
-  const double sw = wpart ? sample_sum(wpart + (size_t)blockIdx.x * nb, nb, sm4) : hw;
+  const double se = hg_block_partials_sum_256(epart + (size_t)blockIdx.x * nb, nb, sm4);
+  const double sw = wpart ? hg_block_partials_sum_256(wpart + (size_t)blockIdx.x * nb, nb, sm4) : hw;
   if (threadIdx.x == 0) mean[blockIdx.x] = sw > 0.0 ? (float)(se / sw) : 0.f;
 }
 
 long long de_blocks(int32_t B, int32_t H, int32_t W) {   // pixel blocks per sample; 0 when the sizes or the grid are refused
-  if (B <= 0 || H <= 0 || W <= 0 || B > 65535) return 0;
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
   const long long nb = ((long long)H * W + DE_THREADS - 1) / DE_THREADS;
-  return nb <= 0x7fffffffLL ? nb : 0;
+  return grid_ok(nb, B, 1) ? nb : 0;
 }
 
 }  // namespace
@@ -289,21 +268,15 @@ int hg_delta_e(const float *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_
   if (nb == 0 || workspace_bytes < hg_delta_e_workspace_bytes(B, H, W)) return HG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   double *epart = static_cast<double *>(workspace), *wpart = weight ? epart + (size_t)B * nb : nullptr;
-  const dim3 grid((unsigned)nb, (unsigned)B);
-  if (weight) {
-    hipLaunchKernelGGL(k_de_wsum, grid, dim3(DE_THREADS), 0, st, weight, (long long)ws_b, (long long)ws_h, (long long)ws_w,
-                       (int)H, (int)W, wpart);
-    HG_LAUNCH_CHECK();
-  }
-  auto kern = kind == 76 ? (grad ? k_delta_e<76, true> : k_delta_e<76, false>) : (grad ? k_delta_e<2000, true> : k_delta_e<2000, false>);
-  hipLaunchKernelGGL(kern, grid, dim3(DE_THREADS), 0, st, x1, (long long)s1_b, (long long)s1_c, (long long)s1_h, (long long)s1_w,
-                     x2, (long long)s2_b, (long long)s2_c, (long long)s2_h, (long long)s2_w, weight, (long long)ws_b,
-                     (long long)ws_h, (long long)ws_w, map, grad, (int)H, (int)W, epart, (const double *)wpart);
-  HG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_de_finish, dim3((unsigned)B), dim3(DE_THREADS), 0, st, (const double *)epart, (const double *)wpart,
-                     (int)nb, (double)H * (double)W, mean);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  const dim3 grid((unsigned)nb, (unsigned)B), block(DE_THREADS);
+  if (weight)
+    if (int rc = launch(k_de_wsum, grid, block, 0, st, weight, ws_b, ws_h, ws_w, H, W, wpart)) return rc;
+  const int rc = dispatch([&](auto KIND, auto GRAD) {
+    return launch(k_delta_e<KIND, GRAD>, grid, block, 0, st, x1, s1_b, s1_c, s1_h, s1_w, x2, s2_b, s2_c, s2_h, s2_w, weight, ws_b,
+                  ws_h, ws_w, map, grad, H, W, epart, wpart);
+  }, among<76, 2000>(kind), grad != nullptr);
+  if (rc) return rc;
+  return launch(k_de_finish, dim3((unsigned)B), block, 0, st, epart, wpart, (int)nb, (double)H * (double)W, mean);
 }
 
 }  // extern "C"

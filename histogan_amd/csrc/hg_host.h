@@ -1,5 +1,6 @@
-// hg_host.h -- host-side helpers shared by the dispatchers (hg_hist.hip, hg_conv.hip, hg_wino.hip): runtime values ->
-// template arguments, the one kernel launch, and the per-device constants the planners read.
+// hg_host.h -- host-side helpers shared by the dispatchers (hg_hist.hip, hg_conv.hip, hg_wino.hip) and by the
+// post-processing and metric launchers (hg_post.hip, hg_deltae.hip, hg_ssim.hip, hg_idt.hip): runtime values -> template
+// arguments, the one kernel launch, the limits of a grid, and the per-device constants the planners read.
 #pragma once
 #include <type_traits>
 #include "hg_common.h"
@@ -13,6 +14,11 @@ inline int ceil_log2(int v) {
   return l;
 }
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// what a launch accepts as its grid
+inline bool grid_ok(long long gx, long long gy, long long gz) {
+  return gx >= 1 && gx <= 0x7fffffffLL && gy >= 1 && gy <= 65535 && gz >= 1 && gz <= 65535;
+}
 
 // per-process caches are keyed by the CURRENT device (a process that launches on a second GPU must not plan with the first
 // one's CU count, nor skip the dynamic-LDS attribute there): arrays of kMaxDev entries indexed by cur_dev()

@@ -5,8 +5,7 @@
 // quantile search compares 128-bit products -- so the result does not depend on the order of any sum and repeats are
 // bit-identical.  The per-pixel passes are streaming work bound by HBM bandwidth: the working copy of the source is three
 // planes, four pixels (16 bytes per plane) per lane.
-#include "hg_common.h"
-#include "../../include/hg_hist.h"
+#include "hg_host.h"
 #include "../../include/hg_post.h"
 
 namespace {
@@ -284,10 +283,6 @@ __global__ __launch_bounds__(IDT_THREADS) void k_idt_table(unsigned long long *_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-struct alignas(4) IdtBytes12 {
-  uint32_t d[3];
-};
-
 // steps 4 and 5 and x += rho R^T d on the planar working copy, four pixels per lane.  LAST: clip and write the HWC output;
 // otherwise write the copy back and reduce the range of the next rotation's projections in the same pass.
 template <bool LAST, bool OU8>
@@ -331,9 +326,9 @@ __global__ __launch_bounds__(IDT_THREADS) void k_idt_apply(float *__restrict__ p
       x1 = fmaf(rho, fmaf(R.r[7], d[2], fmaf(R.r[4], d[1], R.r[1] * d[0])), x1);      // rotation's instantiations round alike
       x2 = fmaf(rho, fmaf(R.r[8], d[2], fmaf(R.r[5], d[1], R.r[2] * d[0])), x2);
       if constexpr (LAST) {
-        res[3 * j] = fminf(fmaxf(x0, 0.f), 1.f);
-        res[3 * j + 1] = fminf(fmaxf(x1, 0.f), 1.f);
-        res[3 * j + 2] = fminf(fmaxf(x2, 0.f), 1.f);
+        res[3 * j] = hg_clamp01(x0);
+        res[3 * j + 1] = hg_clamp01(x1);
+        res[3 * j + 2] = hg_clamp01(x2);
       } else {
         c[0][j] = x0; c[1][j] = x1; c[2][j] = x2;
         if (p + j < b1) {
@@ -355,12 +350,7 @@ __global__ __launch_bounds__(IDT_THREADS) void k_idt_apply(float *__restrict__ p
 #pragma unroll
       for (int i = 0; i < 12; ++i) q8[i] = (uint8_t)(res[i] * 255.f);
       if (p + 3 < n) {
-        IdtBytes12 v;
-#pragma unroll
-        for (int w = 0; w < 3; ++w)
-          v.d[w] = (uint32_t)q8[4 * w] | ((uint32_t)q8[4 * w + 1] << 8) | ((uint32_t)q8[4 * w + 2] << 16) |
-                   ((uint32_t)q8[4 * w + 3] << 24);
-        *reinterpret_cast<IdtBytes12 *>(o) = v;
+        *reinterpret_cast<HgBytes12 *>(o) = hg_pack_rgb4([&](int k) { return q8[k]; });
       } else {
         for (int i = 0; i < 3 * (int)(n - p); ++i) o[i] = q8[i];
       }
@@ -413,19 +403,15 @@ int idt_clear(uint32_t *ranges, long long n_sets, uint64_t *hist, long long n_co
   const long long items = n_sets * 6 > n_counters ? n_sets * 6 : n_counters;
   long long nb = (items + IDT_THREADS - 1) / IDT_THREADS;
   nb = nb < 1 ? 1 : (nb > IDT_MAX_BLOCKS ? IDT_MAX_BLOCKS : nb);
-  hipLaunchKernelGGL(k_idt_clear, dim3((unsigned)nb), dim3(IDT_THREADS), 0, st, ranges, n_sets,
-                     reinterpret_cast<unsigned long long *>(hist), n_counters);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_idt_clear, dim3((unsigned)nb), dim3(IDT_THREADS), 0, st, ranges, n_sets,
+                reinterpret_cast<unsigned long long *>(hist), n_counters);
 }
 
 int idt_range(const float *x, long long n, long long ps, long long cs, const float *rot, int nrot, uint32_t *ranges,
               float *planes, hipStream_t st) {
   const IdtShare s = idt_share(n, 0);
-  hipLaunchKernelGGL(k_idt_range, dim3(s.blocks), dim3(IDT_THREADS), 0, st, x, n, ps, cs, rot, nrot, ranges, planes,
-                     idt_plane_stride(n), s.share);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_idt_range, dim3(s.blocks), dim3(IDT_THREADS), 0, st, x, n, ps, cs, rot, nrot, ranges, planes, idt_plane_stride(n),
+                s.share);
 }
 
 int idt_hist(const float *x, long long n, long long ps, long long cs, const float *rot, int nrot, int bins,
@@ -433,22 +419,17 @@ int idt_hist(const float *x, long long n, long long ps, long long cs, const floa
   const IdtShare s = idt_share(n, blocks);
   const size_t lds = (size_t)nrot * 3 * bins * sizeof(uint32_t);
   unsigned long long *h = reinterpret_cast<unsigned long long *>(hist);
-  if (ps == 1 && cs % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && cs >= idt_plane_stride(n))
-    hipLaunchKernelGGL(k_idt_hist<4>, dim3(s.blocks), dim3(IDT_THREADS), lds, st, x, n, ps, cs, rot, nrot, bins, ranges, h,
-                       s.share);
-  else
-    hipLaunchKernelGGL(k_idt_hist<1>, dim3(s.blocks), dim3(IDT_THREADS), lds, st, x, n, ps, cs, rot, nrot, bins, ranges, h,
-                       s.share);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  const bool planar = ps == 1 && cs % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && cs >= idt_plane_stride(n);
+  return dispatch([&](auto PLANAR) {
+    return launch(k_idt_hist<PLANAR ? 4 : 1>, dim3(s.blocks), dim3(IDT_THREADS), lds, st, x, n, ps, cs, rot, nrot, bins, ranges, h,
+                  s.share);
+  }, planar);
 }
 
 int idt_table(uint64_t *src_hist, const uint64_t *tgt_hist, const uint32_t *tgt_range, int bins, float *map,
               uint32_t *next_range, int clear_src, hipStream_t st) {
-  hipLaunchKernelGGL(k_idt_table, dim3(3), dim3(IDT_THREADS), 0, st, reinterpret_cast<unsigned long long *>(src_hist),
-                     reinterpret_cast<const unsigned long long *>(tgt_hist), tgt_range, bins, map, next_range, clear_src);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_idt_table, dim3(3), dim3(IDT_THREADS), 0, st, reinterpret_cast<unsigned long long *>(src_hist),
+                reinterpret_cast<const unsigned long long *>(tgt_hist), tgt_range, bins, map, next_range, clear_src);
 }
 
 int idt_apply(float *planes, long long n, const float *rot, const float *rot_next, int bins, const uint32_t *range,
@@ -456,15 +437,11 @@ int idt_apply(float *planes, long long n, const float *rot, const float *rot_nex
   const IdtShare s = idt_share(n, 0);
   const size_t lds = (size_t)3 * bins * sizeof(float);
   const long long np = idt_plane_stride(n);
-#define HG_IDT_APPLY(LAST, OU8)                                                                                          \
-  hipLaunchKernelGGL((k_idt_apply<LAST, OU8>), dim3(s.blocks), dim3(IDT_THREADS), lds, st, planes, n, np, rot, rot_next,  \
-                     bins, range, map, rho, next_range, out, s.share)
-  if (rot_next) HG_IDT_APPLY(false, false);
-  else if (out_u8) HG_IDT_APPLY(true, true);
-  else HG_IDT_APPLY(true, false);
-#undef HG_IDT_APPLY
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  // the three instantiations there are: a middle rotation, the last one to fp32, the last one to uint8
+  return dispatch([&](auto END) {
+    return launch(k_idt_apply<END != 0, END == 2>, dim3(s.blocks), dim3(IDT_THREADS), lds, st, planes, n, np, rot, rot_next, bins,
+                  range, map, rho, next_range, out, s.share);
+  }, among<0, 1, 2>(rot_next ? 0 : (out_u8 ? 2 : 1)));
 }
 
 int idt_target_tables(const float *tgt, long long n, long long ps, long long cs, const float *rot, int iterations, int bins,

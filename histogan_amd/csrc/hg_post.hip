@@ -4,8 +4,7 @@
 // HBM bandwidth: one thread per output element, neighbours re-read through L1/L2, no LDS staging.  Bilateral guided
 // upsampling adds the fp64 normal equations of its grid fit (per-cell partials, then a gather) and the slice, which
 // stages the grid vertices of a pixel tile in LDS.
-#include "hg_common.h"
-#include "../../include/hg_hist.h"
+#include "hg_host.h"
 #include "../../include/hg_post.h"
 #include "hg_lab.h"
 
@@ -37,7 +36,7 @@ __global__ __launch_bounds__(256) void k_resize_axis(const void *__restrict__ xv
     const long long off = (long long)c * xs_c + (AXIS == 0 ? (long long)s * xs_h + (long long)j * xs_w
                                                            : (long long)i * xs_h + (long long)s * xs_w);
     float v = XU8 ? (float)static_cast<const uint8_t *>(xv)[off] : static_cast<const float *>(xv)[off];
-    if (clamp_in) v = fminf(fmaxf(v, 0.f), 1.f);
+    if (clamp_in) v = hg_clamp01(v);
     acc += w[t] * v;
   }
   const long long oo = (long long)c * os_c + (long long)i * os_h + (long long)j * os_w;
@@ -122,17 +121,11 @@ __global__ __launch_bounds__(256) void k_pyr_up_add(const float *__restrict__ pr
 
 // ---------------------------------------------------------------------------------------------------------------------
 // colour moments: per-block fp64 partials, then one finishing block; fixed order, so repeats are bit-identical
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ void block_sum9(double (&s)[MOM_K], double (*sm)[MOM_K]) {   // sm: [4][9] LDS
   const int wv = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < MOM_K; ++k) {
-    s[k] = wave_sum_d(s[k]);
+    s[k] = hg_wave_sum(s[k]);
     if ((threadIdx.x & 63) == 0) sm[wv][k] = s[k];
   }
   __syncthreads();
@@ -217,7 +210,7 @@ __global__ __launch_bounds__(256) void k_color_affine(const float *__restrict__ 
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     float v = d0 * k.v[3 + c] + d1 * k.v[6 + c] + d2 * k.v[9 + c] + k.v[12 + c];
-    v = fminf(fmaxf(v, 0.f), 1.f);
+    v = hg_clamp01(v);
     if constexpr (OU8) static_cast<uint8_t *>(ov)[p * 3 + c] = (uint8_t)(v * 255.f);
     else static_cast<float *>(ov)[p * 3 + c] = v;
   }
@@ -390,10 +383,6 @@ __global__ __launch_bounds__(256) void k_bgu_gather(const double *__restrict__ P
 // at the pixel that makes the row's byte address a multiple of 4, so group g of a row covers pixels s + 4 (g - 1) ..,
 // s = address & 3, and the partial groups at both ends go byte by byte.  The grid vertices the tile touches are staged
 // in LDS, each wave blends them along y for its row, and a pixel then reads 2 (x) x 2 (z) models of 12 floats.
-struct alignas(4) BguBytes12 {
-  uint32_t d[3];
-};
-
 struct BguAxis {
   int v;       // floor cell
   float f;     // fraction
@@ -442,9 +431,7 @@ __global__ __launch_bounds__(256) void k_bgu_slice(const float *__restrict__ gam
   const bool full = px0 >= 0 && px0 + 3 < W;
   uint8_t rgb[12];
   if (full && vec_in) {
-    const BguBytes12 v = *reinterpret_cast<const BguBytes12 *>(xr + 3LL * px0);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) rgb[k] = (uint8_t)(v.d[k >> 2] >> (8 * (k & 3)));
+    hg_unpack_rgb4(*reinterpret_cast<const HgBytes12 *>(xr + 3LL * px0), rgb);
   } else {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -477,14 +464,9 @@ __global__ __launch_bounds__(256) void k_bgu_slice(const float *__restrict__ gam
     uint8_t *orow = static_cast<uint8_t *>(ov) + (size_t)y * W * 3 + 3LL * px0;
     uint8_t q8[12];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) q8[k] = (uint8_t)floorf(255.f * fminf(fmaxf(res[k], 0.f), 1.f) + 0.5f);
+    for (int k = 0; k < 12; ++k) q8[k] = (uint8_t)floorf(255.f * hg_clamp01(res[k]) + 0.5f);
     if (full && (reinterpret_cast<uintptr_t>(orow) & 3) == 0) {
-      BguBytes12 v;
-#pragma unroll
-      for (int d = 0; d < 3; ++d)
-        v.d[d] = (uint32_t)q8[4 * d] | ((uint32_t)q8[4 * d + 1] << 8) | ((uint32_t)q8[4 * d + 2] << 16) |
-                 ((uint32_t)q8[4 * d + 3] << 24);
-      *reinterpret_cast<BguBytes12 *>(orow) = v;
+      *reinterpret_cast<HgBytes12 *>(orow) = hg_pack_rgb4([&](int k) { return q8[k]; });
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
@@ -524,10 +506,6 @@ bool bgu_grid_args_ok(int gh, int gw, int gd) {
   return gh >= 2 && gw >= 2 && gd >= 2 && gh <= 4096 && gw <= 4096 && gd <= BGU_MAX_GD;
 }
 
-bool grid_ok(long long gx, long long gy, long long gz) {
-  return gx >= 1 && gx <= 0x7fffffffLL && gy >= 1 && gy <= 65535 && gz >= 1 && gz <= 65535;
-}
-
 // sRGB <-> normalised CIE Lab (hg_lab.h), one pixel per thread; grid = (pixel blocks, B).  x: element strides, out: planar
 // contiguous (B, 3, H, W).  TO_LAB clamps its input to [0, 1] first (stage 0 of the histogram blocks).
 template <bool TO_LAB>
@@ -539,7 +517,7 @@ __global__ __launch_bounds__(256) void k_lab_convert(const float *__restrict__ x
   const float *px = x + blockIdx.y * xs_b + y * xs_h + xx * xs_w;
   const float c0 = px[0], c1 = px[xs_c], c2 = px[2 * xs_c];
   float o0, o1, o2;
-  if constexpr (TO_LAB) hg_lab::srgb_to_lab(fminf(fmaxf(c0, 0.f), 1.f), fminf(fmaxf(c1, 0.f), 1.f), fminf(fmaxf(c2, 0.f), 1.f), o0, o1, o2);
+  if constexpr (TO_LAB) hg_lab::srgb_to_lab(hg_clamp01(c0), hg_clamp01(c1), hg_clamp01(c2), o0, o1, o2);
   else hg_lab::lab_to_srgb(c0, c1, c2, o0, o1, o2);
   float *po = out + (long long)blockIdx.y * 3 * HW + n;
   po[0] = o0; po[HW] = o1; po[2 * HW] = o2;
@@ -551,10 +529,8 @@ int lab_convert(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_
   if (!x || !out || B <= 0 || H <= 0 || W <= 0) return HG_EINVAL;
   const long long nb = ((long long)H * W + 255) / 256;
   if (!grid_ok(nb, B, 1)) return HG_EINVAL;
-  hipLaunchKernelGGL(k_lab_convert<TO_LAB>, dim3((unsigned)nb, B), dim3(256), 0, (hipStream_t)stream, x, (long long)xs_b,
-                     (long long)xs_c, (long long)xs_h, (long long)xs_w, out, (int)H, (int)W);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_lab_convert<TO_LAB>, dim3((unsigned)nb, B), dim3(256), 0, (hipStream_t)stream, x, xs_b, xs_c, xs_h, xs_w, out, H,
+                W);
 }
 
 }  // namespace
@@ -571,26 +547,10 @@ int hg_resize_axis(const void *x, int32_t x_u8, int64_t xs_c, int64_t xs_h, int6
   const int Ho = axis == 0 ? out_len : H, Wo = axis == 0 ? W : out_len, n_in = axis == 0 ? H : W;
   const dim3 grid((Wo + 63) / 64, (Ho + 3) / 4, C);
   if (!grid_ok(grid.x, grid.y, grid.z)) return HG_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const bool xu = x_u8 != 0, ou = out_u8 != 0;
-#define HG_RESIZE_LAUNCH(XU, OU, AX)                                                                                   \
-  hipLaunchKernelGGL((k_resize_axis<XU, OU, AX>), grid, dim3(256), 0, st, x, (long long)xs_c, (long long)xs_h,         \
-                     (long long)xs_w, (int)clamp_in, out, (long long)os_c, (long long)os_h, (long long)os_w, Ho, Wo,  \
-                     n_in, weights, indices, (int)taps)
-  if (axis == 0) {
-    if (xu && ou) HG_RESIZE_LAUNCH(true, true, 0);
-    else if (xu) HG_RESIZE_LAUNCH(true, false, 0);
-    else if (ou) HG_RESIZE_LAUNCH(false, true, 0);
-    else HG_RESIZE_LAUNCH(false, false, 0);
-  } else {
-    if (xu && ou) HG_RESIZE_LAUNCH(true, true, 1);
-    else if (xu) HG_RESIZE_LAUNCH(true, false, 1);
-    else if (ou) HG_RESIZE_LAUNCH(false, true, 1);
-    else HG_RESIZE_LAUNCH(false, false, 1);
-  }
-#undef HG_RESIZE_LAUNCH
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return dispatch([&](auto XU8, auto OU8, auto AXIS) {
+    return launch(k_resize_axis<XU8, OU8, AXIS>, grid, dim3(256), 0, (hipStream_t)stream, x, xs_c, xs_h, xs_w, clamp_in, out, os_c,
+                  os_h, os_w, Ho, Wo, n_in, weights, indices, taps);
+  }, x_u8 != 0, out_u8 != 0, among<0, 1>(axis));
 }
 
 int hg_pyr_down(const float *x, float *out, int32_t C, int32_t H, int32_t W, void *stream) {
@@ -598,9 +558,7 @@ int hg_pyr_down(const float *x, float *out, int32_t C, int32_t H, int32_t W, voi
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const dim3 grid((Wo + 63) / 64, (Ho + 3) / 4, C);
   if (!grid_ok(grid.x, grid.y, grid.z)) return HG_EINVAL;
-  hipLaunchKernelGGL(k_pyr_down, grid, dim3(256), 0, (hipStream_t)stream, x, out, H, W, Ho, Wo);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_pyr_down, grid, dim3(256), 0, (hipStream_t)stream, x, out, H, W, Ho, Wo);
 }
 
 int hg_pyr_up_add(const float *prev, const float *fine_a, const float *coarse_a, float wa, const float *fine_b,
@@ -610,10 +568,7 @@ int hg_pyr_up_add(const float *prev, const float *fine_a, const float *coarse_a,
   if (wb != 0.f && (!fine_b || !coarse_b)) return HG_EINVAL;
   const dim3 grid((2 * w + 63) / 64, (2 * h + 3) / 4, C);
   if (!grid_ok(grid.x, grid.y, grid.z)) return HG_EINVAL;
-  hipLaunchKernelGGL(k_pyr_up_add, grid, dim3(256), 0, (hipStream_t)stream, prev, fine_a, coarse_a, wa, fine_b,
-                     coarse_b, wb, out, h, w);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_pyr_up_add, grid, dim3(256), 0, (hipStream_t)stream, prev, fine_a, coarse_a, wa, fine_b, coarse_b, wb, out, h, w);
 }
 
 size_t hg_color_moments_workspace_bytes(int64_t n) {
@@ -626,13 +581,9 @@ int hg_color_moments(const float *x, int64_t n, int64_t pix_stride, int64_t chan
   if (workspace_bytes < hg_color_moments_workspace_bytes(n)) return HG_EWORKSPACE;
   const int nb = mom_blocks(n);
   double *part = static_cast<double *>(workspace);
-  hipLaunchKernelGGL(k_moments_part, dim3(nb), dim3(MOM_THREADS), 0, (hipStream_t)stream, x, (long long)n,
-                     (long long)pix_stride, (long long)chan_stride, part);
-  HG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_moments_finish, dim3(1), dim3(MOM_THREADS), 0, (hipStream_t)stream, part, nb, (long long)n,
-                     moments);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = launch(k_moments_part, dim3(nb), dim3(MOM_THREADS), 0, st, x, n, pix_stride, chan_stride, part)) return rc;
+  return launch(k_moments_finish, dim3(1), dim3(MOM_THREADS), 0, st, part, nb, n, moments);
 }
 
 int hg_color_affine(const float *x, int64_t n, int64_t pix_stride, int64_t chan_stride, const float *coef, void *out,
@@ -642,34 +593,24 @@ int hg_color_affine(const float *x, int64_t n, int64_t pix_stride, int64_t chan_
   for (int i = 0; i < 15; ++i) k.v[i] = coef[i];
   const long long nb = (n + 255) / 256;
   if (!grid_ok(nb, 1, 1)) return HG_EINVAL;
-  if (out_u8)
-    hipLaunchKernelGGL(k_color_affine<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, (long long)n,
-                       (long long)pix_stride, (long long)chan_stride, k, out);
-  else
-    hipLaunchKernelGGL(k_color_affine<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, (long long)n,
-                       (long long)pix_stride, (long long)chan_stride, k, out);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return dispatch([&](auto OU8) {
+    return launch(k_color_affine<OU8>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, n, pix_stride, chan_stride, k,
+                  out);
+  }, out_u8 != 0);
 }
 
 int hg_u8_hwc_to_f32(const uint8_t *x, float *out, int32_t C, int64_t HW, void *stream) {
   if (!x || !out || C <= 0 || HW <= 0) return HG_EINVAL;
   const long long nb = (HW + 255) / 256;
   if (!grid_ok(nb, C, 1)) return HG_EINVAL;
-  hipLaunchKernelGGL(k_u8_hwc_to_f32, dim3((unsigned)nb, C), dim3(256), 0, (hipStream_t)stream, x, out, C,
-                     (long long)HW);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_u8_hwc_to_f32, dim3((unsigned)nb, C), dim3(256), 0, (hipStream_t)stream, x, out, C, HW);
 }
 
 int hg_f32_to_u8_hwc(const float *x, uint8_t *out, int32_t C, int64_t HW, void *stream) {
   if (!x || !out || C <= 0 || HW <= 0) return HG_EINVAL;
   const long long nb = (HW + 255) / 256;
   if (!grid_ok(nb, C, 1)) return HG_EINVAL;
-  hipLaunchKernelGGL(k_f32_to_u8_hwc, dim3((unsigned)nb, C), dim3(256), 0, (hipStream_t)stream, x, out, C,
-                     (long long)HW);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  return launch(k_f32_to_u8_hwc, dim3((unsigned)nb, C), dim3(256), 0, (hipStream_t)stream, x, out, C, HW);
 }
 
 size_t hg_bgu_normal_workspace_bytes(int32_t gh, int32_t gw, int32_t gd) {
@@ -691,13 +632,9 @@ int hg_bgu_normal(const float *in_ds, const float *out_ds, const float *weight, 
   double *P = static_cast<double *>(workspace);
   double *Q = P + (size_t)(gh - 1) * (gw - 1) * gd * 3 * BGU_PAIRS;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_bgu_partial, dim3(gw - 1, gh - 1), dim3(BGU_CHUNK), 0, st, in_ds, out_ds, weight, (int)h, (int)w,
-                     (int)gh, (int)gw, (int)gd, P, Q);
-  HG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_bgu_gather, dim3((unsigned)nb), dim3(256), 0, st, (const double *)P, (const double *)Q, (int)gh,
-                     (int)gw, (int)gd, slab_y, diag, off, rhs);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  if (int rc = launch(k_bgu_partial, dim3(gw - 1, gh - 1), dim3(BGU_CHUNK), 0, st, in_ds, out_ds, weight, h, w, gh, gw, gd, P, Q))
+    return rc;
+  return launch(k_bgu_gather, dim3((unsigned)nb), dim3(256), 0, st, P, Q, gh, gw, gd, slab_y, diag, off, rhs);
 }
 
 int hg_bgu_slice(const float *gamma, int32_t gh, int32_t gw, int32_t gd, const uint8_t *photo, int64_t xs_h,
@@ -711,11 +648,9 @@ int hg_bgu_slice(const float *gamma, int32_t gh, int32_t gw, int32_t gd, const u
   if (plan.lds > BGU_MAX_LDS) return HG_EUNSUPPORTED;          // a grid finer than the pixels it is sliced at
   const dim3 grid((W + 3) / 4 / BGU_TILE_GROUPS + 1, (H + BGU_TILE_ROWS - 1) / BGU_TILE_ROWS);
   if (!grid_ok(grid.x, grid.y, 1)) return HG_EINVAL;
-  hipLaunchKernelGGL(k_bgu_slice, grid, dim3(256), plan.lds, (hipStream_t)stream, gamma, (int)gh, (int)gw, (int)gd,
-                     photo, (long long)xs_h, (long long)xs_w, (long long)xs_c, out, (int)out_u8, (int)H, (int)W,
-                     plan.nyv, plan.nxv);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  // (the one kernel of this file whose dynamic LDS can pass 48 KB: launch asks for it)
+  return launch(k_bgu_slice, grid, dim3(256), plan.lds, (hipStream_t)stream, gamma, gh, gw, gd, photo, xs_h, xs_w, xs_c, out,
+                out_u8, H, W, plan.nyv, plan.nxv);
 }
 
 int hg_srgb_to_lab(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_t xs_w, float *out, int32_t B,

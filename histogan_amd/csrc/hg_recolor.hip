@@ -8,8 +8,6 @@
 
 namespace {
 
-__device__ __forceinline__ float block_sum256(float v, float *sm4) { return hg_block_sum_256(v, sm4); }
-
 // element range of chunk j of a plane of HW elements split into `chunks` pieces (multiples of 4 when HW is)
 __device__ __forceinline__ void chunk_range(int HW, int chunks, int j, int &lo, int &hi) {
   int len = (HW + chunks - 1) / chunks;
@@ -36,7 +34,7 @@ __global__ __launch_bounds__(256) void k_in_stats(const float *__restrict__ x, f
   } else {
     for (int e = lo + threadIdx.x; e < hi; e += 256) s += xp[e];
   }
-  s = block_sum256(s, sm);
+  s = hg_block_sum_256(s, sm);
   const float mean = hi > lo ? s / (float)(hi - lo) : 0.f;
   float q = 0.f;
   if (vec) {
@@ -48,7 +46,7 @@ __global__ __launch_bounds__(256) void k_in_stats(const float *__restrict__ x, f
   } else {
     for (int e = lo + threadIdx.x; e < hi; e += 256) { const float a = xp[e] - mean; q += a * a; }
   }
-  q = block_sum256(q, sm);
+  q = hg_block_sum_256(q, sm);
   if (threadIdx.x == 0) {
     float *o = part + ((size_t)blockIdx.x * chunks + blockIdx.y) * 2;
     o[0] = mean; o[1] = q;
@@ -126,8 +124,8 @@ __global__ __launch_bounds__(256) void k_in_bwd_stats(const float *__restrict__ 
   } else {
     for (int e = lo + threadIdx.x; e < hi; e += 256) { in_mx(gp[e], op[e], slope, islope, m, xh); s1 += m; s2 += m * xh; }
   }
-  s1 = block_sum256(s1, sm);
-  s2 = block_sum256(s2, sm);
+  s1 = hg_block_sum_256(s1, sm);
+  s2 = hg_block_sum_256(s2, sm);
   if (threadIdx.x == 0) {
     float *o = part + ((size_t)blockIdx.x * chunks + blockIdx.y) * 2;
     o[0] = s1; o[1] = s2;

@@ -18,15 +18,14 @@
 // can break it.
 #include <cmath>
 
-#include "hg_common.h"
-#include "../../include/hg_hist.h"
+#include "hg_host.h"
 #include "../../include/hg_post.h"
 #include "hg_lab.h"
 
 namespace {
 
 constexpr int T = HG_SSIM_TILE, R = 10, K = 11;      // tile edge, halo, taps
-constexpr int THREADS = 256;
+constexpr int THREADS = 256;                         // hg_block_sum_256, hg_block_partials_sum_256
 constexpr int FT = T + R;                            // forward: staged edge = 42; backward: edge of the recomputed maps
 constexpr int BT = T + 2 * R;                        // backward: staged edge = 52
 constexpr int EF = T * T / THREADS;                  // forward: positions per thread = 4 (also the backward's output pixels)
@@ -34,7 +33,8 @@ constexpr int EB = (FT * FT + THREADS - 1) / THREADS;   // backward: recomputed 
 constexpr double kC1 = 1e-4, kC2 = 9e-4;
 static_assert(T % 2 == 0 && T * T % THREADS == 0 && HG_SSIM_FINISH_THREADS == THREADS, "tile / block shape");
 
-enum { SRC_L = 0, SRC_RGB = 1, SRC_F64 = 2 };
+enum { SRC_L = 0, SRC_RGB = 1, SRC_F64 = 2 };   // among<SRC_L, SRC_RGB, SRC_F64>(mode): HG_SSIM_PLANES1 / 3 pick the last
+static_assert(SRC_L == HG_SSIM_L && SRC_RGB == HG_SSIM_RGB, "the image modes are their own source kind");
 
 struct Taps {
   double g[K];
@@ -44,18 +44,6 @@ struct Image {   // fp32 (B, 3, H, W) with element strides, or -- SRC_F64 -- con
   const void *p;
   long long sb, sc, sh, sw;
 };
-
-__device__ __forceinline__ double block_sum_f64(double v, double *sm4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sm4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = (sm4[0] + sm4[1]) + (sm4[2] + sm4[3]);
-  __syncthreads();
-  return r;
-}
-
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
 
 // The value exists in a register here: without it the compiler sinks a whole tap chain to its (conditional) use and keeps the
 // 11 values it read from LDS alive until then, for every position and quantity at once.
@@ -73,14 +61,14 @@ __device__ __forceinline__ void load_pair(const Image &i1, const Image &i2, int 
     y = static_cast<const double *>(i2.p)[o];
   } else if constexpr (SRC == SRC_RGB) {
     raw[0] = static_cast<const float *>(i1.p)[b * i1.sb + pl * i1.sc + gy * i1.sh + gx * i1.sw];
-    x = (double)clamp01(raw[0]);
-    y = (double)clamp01(static_cast<const float *>(i2.p)[b * i2.sb + pl * i2.sc + gy * i2.sh + gx * i2.sw]);
+    x = (double)hg_clamp01(raw[0]);
+    y = (double)hg_clamp01(static_cast<const float *>(i2.p)[b * i2.sb + pl * i2.sc + gy * i2.sh + gx * i2.sw]);
   } else {
     const float *q1 = static_cast<const float *>(i1.p) + b * i1.sb + gy * i1.sh + gx * i1.sw;
     const float *q2 = static_cast<const float *>(i2.p) + b * i2.sb + gy * i2.sh + gx * i2.sw;
     raw[0] = q1[0], raw[1] = q1[i1.sc], raw[2] = q1[2 * i1.sc];
-    const double c1[3] = {(double)clamp01(raw[0]), (double)clamp01(raw[1]), (double)clamp01(raw[2])};
-    const double c2[3] = {(double)clamp01(q2[0]), (double)clamp01(q2[i2.sc]), (double)clamp01(q2[2 * i2.sc])};
+    const double c1[3] = {(double)hg_clamp01(raw[0]), (double)hg_clamp01(raw[1]), (double)hg_clamp01(raw[2])};
+    const double c2[3] = {(double)hg_clamp01(q2[0]), (double)hg_clamp01(q2[i2.sc]), (double)hg_clamp01(q2[2 * i2.sc])};
     double lab[3], u0[3], u1[3];
     hg_lab::srgb_to_lab_f64<SLOPES>(c1, lab, dlin, dfp);
     x = lab[0] / 100.0;
@@ -217,7 +205,7 @@ __global__ __launch_bounds__(THREADS) void k_ssim_fwd(Image i1, Image i2, int np
       if (i < th && j < tw) map[((long long)b * OH + y0 + i) * OW + x0 + j] = (float)(np == 1 ? mp[e] : mp[e] / (double)np);
     }
   }
-  const double bs = block_sum_f64(sum_s, sm4), bc = block_sum_f64(sum_c, sm4);
+  const double bs = hg_block_sum_256(sum_s, sm4), bc = hg_block_sum_256(sum_c, sm4);
   if (threadIdx.x == 0) {
     const size_t nt = gridDim.x, o = (size_t)b * nt + blockIdx.x;
     part[o] = bs;
@@ -230,10 +218,7 @@ __global__ __launch_bounds__(THREADS) void k_ssim_finish(const double *__restric
                                                          double *__restrict__ means) {
   __shared__ double sm4[4];
   for (int q = 0; q < 2; ++q) {
-    const double *p = part + ((size_t)q * gridDim.x + blockIdx.x) * nt;
-    double s = 0.0;
-    for (int k = threadIdx.x; k < nt; k += THREADS) s += p[k];
-    s = block_sum_f64(s, sm4);
+    const double s = hg_block_partials_sum_256(part + ((size_t)q * gridDim.x + blockIdx.x) * nt, nt, sm4);
     if (threadIdx.x == 0) means[2 * blockIdx.x + q] = s / n;
   }
 }
@@ -370,10 +355,10 @@ int planes_of(int32_t mode) {   // 0 for an unknown mode
 
 // tiles of an h x w extent; 0 when the sizes or the grid are refused
 long long tiles(int32_t B, int32_t H, int32_t W, int32_t h, int32_t w, int *ntx) {
-  if (B <= 0 || B > 65535 || H < K || W < K) return 0;
+  if (B <= 0 || H < K || W < K) return 0;
   const long long nx = ((long long)w + T - 1) / T, ny = ((long long)h + T - 1) / T;
   *ntx = (int)nx;
-  return nx * ny <= 0x7fffffffLL ? nx * ny : 0;
+  return grid_ok(nx * ny, B, 1) ? nx * ny : 0;
 }
 
 }  // namespace
@@ -397,17 +382,15 @@ int hg_ssim_fwd(const void *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_
   const long long nt = tiles(B, H, W, H - R, W - R, &ntx);
   if (nt == 0 || workspace_bytes < hg_ssim_workspace_bytes(B, H, W)) return HG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const Image i1{x1, (long long)s1_b, (long long)s1_c, (long long)s1_h, (long long)s1_w};
-  const Image i2{x2, (long long)s2_b, (long long)s2_c, (long long)s2_h, (long long)s2_w};
+  const Image i1{x1, s1_b, s1_c, s1_h, s1_w}, i2{x2, s2_b, s2_c, s2_h, s2_w};
   double *part = static_cast<double *>(workspace);
-  auto kern = mode == HG_SSIM_L ? k_ssim_fwd<SRC_L> : mode == HG_SSIM_RGB ? k_ssim_fwd<SRC_RGB> : k_ssim_fwd<SRC_F64>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nt, (unsigned)B), dim3(THREADS), 0, st, i1, i2, np, map, pool1, pool2, (int)H, (int)W,
-                     ntx, part, taps());
-  HG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ssim_finish, dim3((unsigned)B), dim3(THREADS), 0, st, (const double *)part, (int)nt,
-                     (double)(H - R) * (double)(W - R) * (double)np, means);
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  const int rc = dispatch([&](auto SRC) {
+    return launch(k_ssim_fwd<SRC>, dim3((unsigned)nt, (unsigned)B), dim3(THREADS), 0, st, i1, i2, np, map, pool1, pool2, H, W, ntx,
+                  part, taps());
+  }, among<SRC_L, SRC_RGB, SRC_F64>(mode));
+  if (rc) return rc;
+  return launch(k_ssim_finish, dim3((unsigned)B), dim3(THREADS), 0, st, part, (int)nt,
+                (double)(H - R) * (double)(W - R) * (double)np, means);
 }
 
 int hg_ssim_bwd(const void *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_t s1_w, const void *x2, int64_t s2_b,
@@ -418,13 +401,11 @@ int hg_ssim_bwd(const void *x1, int64_t s1_b, int64_t s1_c, int64_t s1_h, int64_
   int ntx = 0;
   const long long nt = tiles(B, H, W, H, W, &ntx);
   if (nt == 0) return HG_EINVAL;
-  const Image i1{x1, (long long)s1_b, (long long)s1_c, (long long)s1_h, (long long)s1_w};
-  const Image i2{x2, (long long)s2_b, (long long)s2_c, (long long)s2_h, (long long)s2_w};
-  auto kern = mode == HG_SSIM_L ? k_ssim_bwd<SRC_L> : mode == HG_SSIM_RGB ? k_ssim_bwd<SRC_RGB> : k_ssim_bwd<SRC_F64>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nt, (unsigned)B), dim3(THREADS), 0, (hipStream_t)stream, i1, i2, np, coef, coarse, grad,
-                     (int)H, (int)W, ntx, taps());
-  HG_LAUNCH_CHECK();
-  return HG_OK;
+  const Image i1{x1, s1_b, s1_c, s1_h, s1_w}, i2{x2, s2_b, s2_c, s2_h, s2_w};
+  return dispatch([&](auto SRC) {
+    return launch(k_ssim_bwd<SRC>, dim3((unsigned)nt, (unsigned)B), dim3(THREADS), 0, (hipStream_t)stream, i1, i2, np, coef, coarse,
+                  grad, H, W, ntx, taps());
+  }, among<SRC_L, SRC_RGB, SRC_F64>(mode));
 }
 
 }  // extern "C"

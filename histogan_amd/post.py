@@ -24,7 +24,7 @@ from math import ceil
 import numpy as np
 import torch
 
-from ._lib import check, lib, need_gpu, on_device, raw_stream
+from ._lib import check, lib, need_gpu, on_device, ptr, raw_stream, workspace
 
 EPS = 2.2204e-16          # utils/color_transfer_MKL.py:3
 
@@ -90,6 +90,34 @@ def _tables(n_in, n_out, scale, method, device):
 
 
 _FOUND = 'expects a tensor on the GPU'     # need_gpu's wording here
+
+
+# ---- the argument rules of the conversions, the colour difference and SSIM (no HIP call is made) ----------------------------
+# A function that refuses an input for more than one reason raises what needs no device (ValueError) first, then need_gpu.
+def _rgb_batch(t, what, name=None):
+    """The rule "a float RGB image or batch": (single, t as (B, 3, H, W)).  name: 'pred' / 'target', for the message."""
+    if not torch.is_tensor(t) or t.dim() not in (3, 4) or t.shape[-3] != 3 or not t.is_floating_point():
+        got = f'{t.dtype} {tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f'{what}: {"expected" if name is None else name + " must be"} a float (B, 3, H, W) or (3, H, W) tensor, '
+                         f'got {got}')
+    single = t.dim() == 3
+    return single, (t.unsqueeze(0) if single else t)
+
+
+def _rgb_pair(pred, target, what):
+    """The rule "pred and target: two such images of one shape and device": (single, pred (B, 3, H, W), target)."""
+    single, p4 = _rgb_batch(pred, what, 'pred')
+    _, t4 = _rgb_batch(target, what, 'target')
+    if p4.shape != t4.shape or p4.device != t4.device:
+        raise ValueError(f'{what}: pred and target must have one shape and device, got {tuple(p4.shape)} on {p4.device} and '
+                         f'{tuple(t4.shape)} on {t4.device}')
+    return single, p4, t4
+
+
+def _detached_f32(t):
+    """`t` as the kernels read it here: detached, fp32 (the same storage when it already is), any strides."""
+    t = t.detach()
+    return t if t.dtype == torch.float32 else t.float()
 
 
 # ---- device: resize ---------------------------------------------------------------------------------------------------
@@ -173,17 +201,14 @@ def _lab_convert(x, fn, what):
     if torch.is_tensor(x) and x.requires_grad:      # before any HIP call
         raise ValueError(f'{what} is not differentiable (a data-side tool): the input requires grad.  For a Lab histogram of '
                          f'an sRGB image with a gradient use histogram_classes.LabHistBlock(from_rgb=True)')
-    need_gpu(x, what, _FOUND)
-    if x.dim() not in (3, 4) or x.shape[-3] != 3 or not x.is_floating_point():
-        raise ValueError(f'{what}: expected a float (B, 3, H, W) or (3, H, W) tensor, got {x.dtype} {tuple(x.shape)}')
-    x4 = x if x.dim() == 4 else x.unsqueeze(0)
-    if x4.dtype != torch.float32:
-        x4 = x4.float()
+    single, x4 = _rgb_batch(x, what)
+    need_gpu(x4, what, _FOUND)
+    x4 = _detached_f32(x4)
     B, _, H, W = x4.shape
     out = torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
     with on_device(x.device):
         check(fn(x4.data_ptr(), *x4.stride(), out.data_ptr(), B, H, W, raw_stream(x.device)), what)
-    return out if x.dim() == 4 else out[0]
+    return out[0] if single else out
 
 
 def srgb_to_lab(x):
@@ -214,42 +239,31 @@ def delta_e_kind(kind, what='delta_e'):
         raise ValueError(f"{what}: kind must be '76' or '2000' (dE76, CIEDE2000), not {kind!r}") from None
 
 
-def _de_image(t, what, name):
-    need_gpu(t, what, _FOUND)
-    if t.dim() != 4 or t.shape[1] != 3 or not t.is_floating_point():
-        raise ValueError(f'{what}: {name} must be a float (B, 3, H, W) or (3, H, W) tensor, got {t.dtype} {tuple(t.shape)}')
-    t = t.detach()
-    return t if t.dtype == torch.float32 else t.float()
-
-
 def _delta_e_launch(pred, target, weight, kind, want_map, want_grad, what):
-    """One hg_delta_e call on (B, 3, H, W) images: (mean (B,), map (B, H, W) or None, grad (B, 3, H, W) or None), fp32."""
-    x1, x2 = _de_image(pred, what, 'pred'), _de_image(target, what, 'target')
-    if x1.shape != x2.shape or x1.device != x2.device:
-        raise ValueError(f'{what}: pred and target must have one shape and device, got {tuple(x1.shape)} on {x1.device} and '
-                         f'{tuple(x2.shape)} on {x2.device}')
+    """One hg_delta_e call on a (B, 3, H, W) pair on the GPU (_de_batched's): (mean (B,), map (B, H, W) or None, grad
+    (B, 3, H, W) or None), fp32."""
+    x1, x2 = _detached_f32(pred), _detached_f32(target)
     B, _, H, W = x1.shape
-    w, wptr, wstr = None, None, (0, 0, 0)
+    w, wstr = None, (0, 0, 0)
     if weight is not None:
         need_gpu(weight, what, _FOUND)
-        w = weight.detach()
+        w = weight
         if w.dim() == 4 and w.shape[1] == 1:
             w = w[:, 0]
         if tuple(w.shape) != (B, H, W) or not w.is_floating_point() or w.device != x1.device:
             raise ValueError(f'{what}: weight must be a float (B, H, W) or (B, 1, H, W) map = {(B, H, W)} on {x1.device}, got '
                              f'{weight.dtype} {tuple(weight.shape)} on {weight.device}')
-        w = w if w.dtype == torch.float32 else w.float()
-        wptr, wstr = w.data_ptr(), w.stride()
+        w = _detached_f32(w)
+        wstr = w.stride()
     dev = x1.device
     with on_device(dev):
         mean = torch.empty((B,), dtype=torch.float32, device=dev)
         dmap = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_map else None
         grad = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if want_grad else None
         nb = lib.hg_delta_e_workspace_bytes(B, H, W)
-        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
-        check(lib.hg_delta_e(x1.data_ptr(), *x1.stride(), x2.data_ptr(), *x2.stride(), wptr, *wstr, kind, mean.data_ptr(),
-                             None if dmap is None else dmap.data_ptr(), None if grad is None else grad.data_ptr(), B, H, W,
-                             ws.data_ptr(), nb, raw_stream(dev)), 'hg_delta_e')
+        ws = workspace(nb, dev)
+        check(lib.hg_delta_e(x1.data_ptr(), *x1.stride(), x2.data_ptr(), *x2.stride(), ptr(w), *wstr, kind, mean.data_ptr(),
+                             ptr(dmap), ptr(grad), B, H, W, ws.data_ptr(), nb, raw_stream(dev)), 'hg_delta_e')
     return mean, dmap, grad
 
 
@@ -273,12 +287,10 @@ class DeltaEFunction(torch.autograd.Function):
 
 
 def _de_batched(pred, target, what):
-    for t, name in ((pred, 'pred'), (target, 'target')):
-        need_gpu(t, what, _FOUND)
-        if t.dim() not in (3, 4):
-            raise ValueError(f'{what}: {name} must be a float (B, 3, H, W) or (3, H, W) tensor, got {t.dtype} {tuple(t.shape)}')
-    single = pred.dim() == 3
-    return single, (pred.unsqueeze(0) if single else pred), (target.unsqueeze(0) if target.dim() == 3 else target)
+    """Every refusal of the images of delta_e / delta_e_map: (single, pred (B, 3, H, W), target), on the GPU."""
+    single, p4, t4 = _rgb_pair(pred, target, what)
+    need_gpu(p4, what, _FOUND)
+    return single, p4, t4
 
 
 def delta_e(pred, target, kind='2000', weight=None):
@@ -329,15 +341,7 @@ def ssim_channels(channels, what='ssim'):
 def _ssim_images(pred, target, channels, what, min_size):
     """Every refusal of ssim / ssim_map / ms_ssim, before any HIP call: (mode, single, pred (B, 3, H, W), target)."""
     mode = ssim_channels(channels, what)
-    for t, name in ((pred, 'pred'), (target, 'target')):
-        if not torch.is_tensor(t) or t.dim() not in (3, 4) or t.shape[-3] != 3 or not t.is_floating_point():
-            got = f'{t.dtype} {tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
-            raise ValueError(f'{what}: {name} must be a float (B, 3, H, W) or (3, H, W) tensor, got {got}')
-    single = pred.dim() == 3
-    p4, t4 = (pred.unsqueeze(0) if single else pred), (target.unsqueeze(0) if target.dim() == 3 else target)
-    if p4.shape != t4.shape or p4.device != t4.device:
-        raise ValueError(f'{what}: pred and target must have one shape and device, got {tuple(p4.shape)} on {p4.device} and '
-                         f'{tuple(t4.shape)} on {t4.device}')
+    single, p4, t4 = _rgb_pair(pred, target, what)
     B, _, H, W = p4.shape
     if min(H, W) < min_size:
         raise ValueError(f'{what}: images must be at least {min_size} x {min_size}, got {H} x {W}')
@@ -345,11 +349,6 @@ def _ssim_images(pred, target, channels, what, min_size):
         raise ValueError(f'{what}: the batch must be 1 .. 65535, got {B}')
     need_gpu(p4, what, _FOUND)
     return mode, single, p4, t4
-
-
-def _ssim_f32(t):
-    t = t.detach()
-    return t if t.dtype == torch.float32 else t.float()
 
 
 def _ssim_fwd(x1, x2, mode, want_map=False, want_pool=False):
@@ -363,11 +362,10 @@ def _ssim_fwd(x1, x2, mode, want_map=False, want_pool=False):
         smap = torch.empty((B, H - 10, W - 10), dtype=torch.float32, device=dev) if want_map else None
         pools = tuple(torch.empty((B, planes, H // 2, W // 2), dtype=torch.float64, device=dev) for _ in range(2)) if want_pool else None
         nb = lib.hg_ssim_workspace_bytes(B, H, W)
-        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
-        check(lib.hg_ssim_fwd(x1.data_ptr(), *x1.stride(), x2.data_ptr(), *x2.stride(), mode, means.data_ptr(),
-                              None if smap is None else smap.data_ptr(), None if pools is None else pools[0].data_ptr(),
-                              None if pools is None else pools[1].data_ptr(), B, H, W, ws.data_ptr(), nb, raw_stream(dev)),
-              'hg_ssim_fwd')
+        ws = workspace(nb, dev)
+        pool1, pool2 = pools or (None, None)
+        check(lib.hg_ssim_fwd(x1.data_ptr(), *x1.stride(), x2.data_ptr(), *x2.stride(), mode, means.data_ptr(), ptr(smap),
+                              ptr(pool1), ptr(pool2), B, H, W, ws.data_ptr(), nb, raw_stream(dev)), 'hg_ssim_fwd')
     return means, smap, pools
 
 
@@ -378,8 +376,8 @@ def _ssim_bwd(x1, x2, mode, coef, coarse=None):
     dev = x1.device
     with on_device(dev):
         grad = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if mode < 2 else torch.empty_like(x1)
-        check(lib.hg_ssim_bwd(x1.data_ptr(), *x1.stride(), x2.data_ptr(), *x2.stride(), mode, coef.data_ptr(),
-                              None if coarse is None else coarse.data_ptr(), grad.data_ptr(), B, H, W, raw_stream(dev)), 'hg_ssim_bwd')
+        check(lib.hg_ssim_bwd(x1.data_ptr(), *x1.stride(), x2.data_ptr(), *x2.stride(), mode, coef.data_ptr(), ptr(coarse),
+                              grad.data_ptr(), B, H, W, raw_stream(dev)), 'hg_ssim_bwd')
     return grad
 
 
@@ -389,7 +387,7 @@ class SsimFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, mode):
-        x1, x2 = _ssim_f32(pred), _ssim_f32(target)
+        x1, x2 = _detached_f32(pred), _detached_f32(target)
         means, _, _ = _ssim_fwd(x1, x2, mode)
         ctx.mode, ctx.dtype = mode, pred.dtype
         ctx.save_for_backward(x1, x2)
@@ -410,7 +408,7 @@ class MsSsimFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, mode):
         levels = len(MS_SSIM_WEIGHTS)
-        planes = [(_ssim_f32(pred), _ssim_f32(target))]
+        planes = [(_detached_f32(pred), _detached_f32(target))]
         means = []
         for s in range(levels):
             m, _, pools = _ssim_fwd(*planes[s], mode if s == 0 else mode + 2, want_pool=s + 1 < levels)
@@ -457,7 +455,7 @@ def ssim_map(pred, target, channels='L'):
     """The ssim map of `ssim`: fp32 (B, H - 10, W - 10), or (H - 10, W - 10) for (3, H, W) inputs; with 'rgb' the mean over the
     three planes.  Not differentiable: the result carries no graph whatever the inputs require."""
     mode, single, p4, t4 = _ssim_images(pred, target, channels, 'ssim_map', SSIM_WINDOW)
-    _, smap, _ = _ssim_fwd(_ssim_f32(p4), _ssim_f32(t4), mode, want_map=True)
+    _, smap, _ = _ssim_fwd(_detached_f32(p4), _detached_f32(t4), mode, want_map=True)
     return smap[0] if single else smap
 
 
@@ -485,10 +483,10 @@ def pyr_up_add(prev, fine_a=None, coarse_a=None, wa=0.0, fine_b=None, coarse_b=N
     """pyrUp(prev) + wa*(fine_a - pyrUp(coarse_a)) + wb*(fine_b - pyrUp(coarse_b)), one launch (include/hg_post.h)."""
     C, h, w = prev.shape
     out = torch.empty((C, 2 * h, 2 * w), dtype=torch.float32, device=prev.device)
-    ptr = lambda t, wt: t.data_ptr() if (t is not None and wt != 0) else None  # noqa: E731
-    check(lib.hg_pyr_up_add(prev.data_ptr(), ptr(fine_a, wa), ptr(coarse_a, wa), float(wa), ptr(fine_b, wb),
-                            ptr(coarse_b, wb), float(wb), out.data_ptr(), C, h, w, raw_stream(prev.device)),
-          'hg_pyr_up_add')
+    fa, ca = (fine_a, coarse_a) if wa != 0 else (None, None)
+    fb, cb = (fine_b, coarse_b) if wb != 0 else (None, None)
+    check(lib.hg_pyr_up_add(prev.data_ptr(), ptr(fa), ptr(ca), float(wa), ptr(fb), ptr(cb), float(wb), out.data_ptr(), C, h, w,
+                            raw_stream(prev.device)), 'hg_pyr_up_add')
     return out
 
 
@@ -614,7 +612,7 @@ def color_moments(x):
         raise ValueError('color_transfer_mkl: an image needs at least 2 pixels')
     with on_device(t.device):
         nb = lib.hg_color_moments_workspace_bytes(n)
-        ws = torch.empty(nb, dtype=torch.uint8, device=t.device)
+        ws = workspace(nb, t.device)
         mom = torch.empty(12, dtype=torch.float64, device=t.device)
         check(lib.hg_color_moments(t.data_ptr(), n, ps, cs, mom.data_ptr(), ws.data_ptr(), nb, raw_stream(t.device)),
               'hg_color_moments')
@@ -710,7 +708,7 @@ def color_transfer_idt(source, target, iterations=20, bins=256, relaxation=1.0, 
     with on_device(src.device):
         rot = torch.from_numpy(rotations.astype(np.float32)).to(src.device)
         nb = lib.hg_idt_workspace_bytes(n0, n1, iters, bins)
-        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=src.device)
+        ws = workspace(nb, src.device)
         check(lib.hg_idt_run(src.data_ptr(), n0, ps0, cs0, tgt.data_ptr(), n1, ps1, cs1, rot.data_ptr(), iters, bins,
                              float(relaxation), out.data_ptr(), int(quantize), ws.data_ptr(), nb, raw_stream(src.device)),
               'hg_idt_run')
@@ -857,8 +855,8 @@ def bgu_normal(in_ds, out_ds, weight=None, grid=None, gd=BGU_DEPTH):
         off = torch.empty((S - 1, m, m), dtype=torch.float64, device=dev)
         rhs = torch.empty((3, S, m), dtype=torch.float64, device=dev)
         nb = lib.hg_bgu_normal_workspace_bytes(gh, gw, gd)
-        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
-        check(lib.hg_bgu_normal(x.data_ptr(), o.data_ptr(), None if wt is None else wt.data_ptr(), h, w, gh, gw, gd,
+        ws = workspace(nb, dev)
+        check(lib.hg_bgu_normal(x.data_ptr(), o.data_ptr(), ptr(wt), h, w, gh, gw, gd,
                                 diag.data_ptr(), off.data_ptr(), rhs.data_ptr(), ws.data_ptr(), nb, raw_stream(dev)),
               'hg_bgu_normal')
     return diag, off, rhs

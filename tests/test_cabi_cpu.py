@@ -18,21 +18,31 @@ def L():
     return L
 
 
-def _declared_symbols():
-    syms = set()
+def _declared_prototypes():
+    """name -> number of parameters of every hg_* prototype under include/ (`void` or an empty list: 0)."""
+    protos = {}
     for fn in os.listdir(os.path.join(ROOT, 'include')):
         txt = open(os.path.join(ROOT, 'include', fn)).read()
         txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-        syms |= set(re.findall(r'\b(hg_[a-z0-9_]+)\s*\(', txt))
-    return syms
+        txt = re.sub(r'//[^\n]*', '', txt)
+        for name, params in re.findall(r'\b(hg_[a-z0-9_]+)\s*\(([^()]*)\)', txt):
+            params = params.strip()
+            protos[name] = 0 if params in ('', 'void') else params.count(',') + 1
+    return protos
 
 
 def test_exports_match_header(L):
-    declared = _declared_symbols()
+    declared = _declared_prototypes()
     assert declared, 'no declarations parsed'
     for name in declared:
         assert hasattr(L.lib, name), f'{name} declared in include/ but not exported'
-    assert set(L.EXPORTS) <= declared
+    assert isinstance(L.EXPORTS, tuple) and len(set(L.EXPORTS)) == len(L.EXPORTS)
+    assert set(L.EXPORTS) == set(declared)
+    for name in L.EXPORTS:
+        # without argtypes ctypes passes a 64-bit pointer as a C int
+        argtypes = getattr(L.lib, name).argtypes
+        assert argtypes is not None, f'{name} has no argtypes'
+        assert len(argtypes) == declared[name], f'{name}: {len(argtypes)} argtypes, {declared[name]} parameters in include/'
 
 
 def test_version_and_error_strings(L):
