@@ -235,7 +235,9 @@ __global__ __launch_bounds__(256) void k_dnl_fwd(const float *__restrict__ conv,
     for (int e = blockIdx.x * 256 + threadIdx.x; e < hw / 4; e += gridDim.x * 256) {
       const int i = (e * 4) / H, j = e * 4 - i * H;
       const float4 c = reinterpret_cast<const float4 *>(cp)[e];
-      const float4 n = *reinterpret_cast<const float4 *>(np + (size_t)i * S + j);   // S % 4 == 0 too (S >= H, pow 2)
+      // a plain 16-byte global load: 4-byte alignment is all it needs, so S % 4 != 0 (H = 4, S = 6) and a noise image at any
+      // float address are served here; the row offset i * S + j never reaches an LDS address
+      const float4 n = *reinterpret_cast<const float4 *>(np + (size_t)i * S + j);
       float4 v;
       v.x = fmaf(c.x, dd, fmaf(w, n.x, bb)); v.y = fmaf(c.y, dd, fmaf(w, n.y, bb));
       v.z = fmaf(c.z, dd, fmaf(w, n.z, bb)); v.w = fmaf(c.w, dd, fmaf(w, n.w, bb));

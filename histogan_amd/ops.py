@@ -310,10 +310,26 @@ def _glin_table(xs, ws, bs, ys, groups, gws=None, gbs=None):
     return tab
 
 
+def _aligned16(t):
+    return t.data_ptr() % 16 == 0
+
+
+def _realigned(t):
+    """f32c(t) on a 16-byte boundary: the same storage when it already is, a copy otherwise (a contiguous view into a flat
+    buffer behind an odd-sized neighbour is contiguous and misaligned)."""
+    t = f32c(t)
+    return t if _aligned16(t) else t.clone()
+
+
 def grouped_linear_supported(xs, ws):
+    """Whether hg_grouped_linear_* serves these layers.  The kernels read whole rows of the WEIGHTS 16 bytes at a time in place
+    (check_layers refuses any other address), so a weight that is a strided view, or a contiguous view into a flat parameter
+    buffer behind an odd-sized parameter, takes the caller's per-layer path; inputs and incoming gradients are small and are
+    realigned by a copy inside _GroupedLinear."""
     B, K = xs[0].shape
     return (GROUPED_STYLES and xs[0].is_cuda and B <= 64 and K % 32 == 0 and len(ws) <= 32
-            and all(w.shape[0] % 4 == 0 and w.shape[1] == K for w in ws))
+            and all(w.shape[0] % 4 == 0 and w.shape[1] == K and w.dtype == torch.float32 and w.is_contiguous() and _aligned16(w)
+                    for w in ws))
 
 
 class _GroupedLinear(torch.autograd.Function):
@@ -327,10 +343,10 @@ class _GroupedLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, groups, n_groups, *tensors):
-        xs = [t.detach().contiguous() for t in tensors[:n_groups]]
+        xs = [_realigned(t) for t in tensors[:n_groups]]
         n = (len(tensors) - n_groups) // 2
-        ws = [t.detach() for t in tensors[n_groups:n_groups + n]]
-        bs = [t.detach() for t in tensors[n_groups + n:]]
+        ws = [t.detach() for t in tensors[n_groups:n_groups + n]]      # in place: grouped_linear_supported vouches for them
+        bs = [f32c(t) for t in tensors[n_groups + n:]]
         B, K = xs[0].shape
         dev = xs[0].device
         ys = [torch.empty((B, w.shape[0]), dtype=torch.float32, device=dev) for w in ws]
@@ -349,7 +365,7 @@ class _GroupedLinear(torch.autograd.Function):
         xs, ws = list(saved[:G]), list(saved[G:])
         B, K = xs[0].shape
         dev = xs[0].device
-        gys = [(g.contiguous() if g is not None else torch.zeros((B, w.shape[0]), dtype=torch.float32, device=dev))
+        gys = [(_realigned(g) if g is not None else torch.zeros((B, w.shape[0]), dtype=torch.float32, device=dev))
                for g, w in zip(gys, ws)]
         need_x = any(ctx.needs_input_grad[2:2 + G])
         need_p = any(ctx.needs_input_grad[2 + G:])
