@@ -217,6 +217,18 @@ def _signatures():
         'hg_idt_apply': (ci, [vp, i64, vp, vp, i32, vp, vp, f32, vp, vp, i32, vp]),
         'hg_idt_target_tables': (ci, [vp, i64, i64, i64, vp, i32, i32, vp, vp, vp]),
         'hg_idt_run': (ci, [vp, i64, i64, i64, vp, i64, i64, i64, vp, i32, i32, f32, vp, i32, vp, sz, vp]),
+        'hg_palette_max_k': (ci, []),
+        'hg_palette_blocks': (ci, [i64]),
+        'hg_palette_point_stride': (i64, [i64]),
+        'hg_palette_workspace_bytes': (sz, [i32, i64, i32]),
+        'hg_palette_quantize': (ci, [vp, i64, i64, i64, i64, vp, i64, i64, i64, vp, i32, i32, i32, vp]),
+        'hg_palette_bins': (ci, [vp, i32, i64, vp, i32, vp]),
+        'hg_palette_seeds': (ci, [vp, i32, i32, vp, vp]),
+        'hg_palette_step': (ci, [vp, vp, i32, i64, vp, i32, vp, vp, i32, vp]),
+        'hg_palette_update': (ci, [vp, i32, i32, vp, i32, vp]),
+        'hg_palette_run': (ci, [vp, i64, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32,
+                                vp, vp, vp, vp, vp, sz, vp]),
+        'hg_palette_transfer': (ci, [vp, i64, i64, i64, vp, vp, vp, i32, f32, vp, vp, i32, vp]),
     }
 
 

@@ -114,6 +114,22 @@ __device__ __forceinline__ void srgb_to_lab_f64(const double (&c)[3], double (&l
   lab[2] = 200.0 * (f[1] - f[2]);
 }
 
+// The inverse of srgb_to_lab_f64: lab = (L, a, b) in Lab units, fp64 -> sRGB clipped to [0, 1], rounded once.  The same
+// pieces as lab_to_srgb, without its fp32 inputs and their 8-bit normalisation (the palette transfer of hg_palette.hip moves
+// a pixel in Lab units and comes back through this).
+__device__ __forceinline__ void lab_f64_to_srgb(const double (&lab)[3], float (&rgb)[3]) {
+  const double fy = (lab[0] + 16.0) / 116.0;
+  const double fx = fy + lab[1] / 500.0, fz = fy - lab[2] / 200.0;
+  auto finv = [](double s) { return s > kDelta ? s * s * s : (s - 4.0 / 29.0) / kSlope; };
+  const double xyz[3] = {finv(fx), finv(fy), finv(fz)};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double l = kMi[i][0] * xyz[0] + kMi[i][1] * xyz[1] + kMi[i][2] * xyz[2];
+    const double c = l <= kKneeLin ? 12.92 * l : 1.055 * pow(l, 1.0 / 2.4) - 0.055;
+    rgb[i] = (float)fmin(fmax(c, 0.0), 1.0);
+  }
+}
+
 // (d/dL, d/da, d/db) in Lab units -> (d/dr, d/dg, d/db) through the Jacobian of srgb_to_lab_f64 at the point whose slopes
 // dlin, dfp are given; fp64, not rounded.
 __device__ __forceinline__ void lab_pullback(const double (&dlin)[3], const double (&dfp)[3], const double (&dlab)[3],

@@ -15,9 +15,12 @@ two sRGB images (delta_e, delta_e_map: dE76 and CIEDE2000) as a differentiable l
 recolourings; SSIM / MS-SSIM of the lightness plane or of the components (ssim, ssim_map, ms_ssim), the structure term
 and the number reported for "structure preserved under recolouring"; and the iterative distribution transfer
 (color_transfer_idt, idt_rotations), the nonlinear colour transfer that reaches the target distributions -- bimodal, skewed,
-saturated -- an affine map cannot.
+saturated -- an affine map cannot; and palettes (palette, paired_palette, palette_labels, match_palettes, palette_histogram):
+an image described by K colours, and color_transfer_palette, the third transfer, between the two -- every pixel moves by a
+smooth blend of per-cluster shifts, so colour regions move independently and flat regions stay flat.
 """
 import ctypes
+from collections import namedtuple
 from functools import lru_cache
 from math import ceil
 
@@ -713,6 +716,254 @@ def color_transfer_idt(source, target, iterations=20, bins=256, relaxation=1.0, 
                              float(relaxation), out.data_ptr(), int(quantize), ws.data_ptr(), nb, raw_stream(src.device)),
               'hg_idt_run')
     return out, rotations
+
+
+# ---- palettes (hg_palette_*, include/hg_post.h) -----------------------------------------------------------------------
+Palette = namedtuple('Palette', 'rgb lab weight')
+Palette.__doc__ = """K colours of an image: rgb (..., K, 3) sRGB in [0, 1], lab (..., K, 3) in CIE Lab units, weight (..., K) the
+share of the image's weight each colour stands for (0: an empty cluster).  fp32, on the device."""
+PALETTE_UNIT = 128                # a palette centre is an integer number of 1/128 Lab units
+PALETTE_MAX_K = 16                # hg_palette_max_k()
+
+
+def _palette_counts(k, iterations, what):
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= PALETTE_MAX_K:
+        raise ValueError(f'{what}: k must be an integer in 1 .. {PALETTE_MAX_K}, got {k!r}')
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 0:
+        raise ValueError(f'{what}: iterations must be a non-negative integer, got {iterations!r}')
+
+
+def _palette_weight(weight, B, H, W, single, device, what):
+    """The rule "an optional weight map": None, or the float (B, H, W) view of a (H, W), (B, H, W) or (B, 1, H, W) map."""
+    if weight is None:
+        return None
+    w = weight
+    if torch.is_tensor(w):
+        if single and w.dim() == 2:
+            w = w.unsqueeze(0)
+        if w.dim() == 4 and w.shape[1] == 1:
+            w = w[:, 0]
+    if not torch.is_tensor(w) or tuple(w.shape) != (B, H, W) or not w.is_floating_point() or w.device != device:
+        got = f'{weight.dtype} {tuple(weight.shape)} on {weight.device}' if torch.is_tensor(weight) else type(weight).__name__
+        raise ValueError(f'{what}: weight must be a float (H, W), (B, H, W) or (B, 1, H, W) map = {(B, H, W)} on {device}, got {got}')
+    return w
+
+
+def _lab_units_to_rgb(lab):
+    """(B, K, 3) Lab units on the device -> (B, K, 3) sRGB through lab_to_srgb (the normalised form, rounded to fp32)."""
+    norm = torch.stack((lab[..., 0] / 100.0, (lab[..., 1] + 128.0) / 255.0, (lab[..., 2] + 128.0) / 255.0), dim=1)
+    return lab_to_srgb(norm.unsqueeze(2).float())[:, :, 0].permute(0, 2, 1).contiguous()
+
+
+def _palette_run(x4, w, other4, k, iterations, want_labels=False, blocks=0):
+    """One hg_palette_run: (centres int32 (B, K, 3), sums int64 (B, K, 4), centres_other or None, labels uint8 (B, H, W) or
+    None)."""
+    x4 = _detached_f32(x4)
+    B, _, H, W = x4.shape
+    dev = x4.device
+    wstr = (0, 0, 0)
+    if w is not None:
+        w = _detached_f32(w)
+        wstr = w.stride()
+    ostr = (0, 0, 0, 0)
+    if other4 is not None:
+        other4 = _detached_f32(other4)
+        ostr = other4.stride()
+    with on_device(dev):
+        centres = torch.empty((B, k, 3), dtype=torch.int32, device=dev)
+        sums = torch.empty((B, k, 4), dtype=torch.int64, device=dev)
+        centres_other = torch.empty((B, k, 3), dtype=torch.int32, device=dev) if other4 is not None else None
+        labels = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_labels else None
+        nb = lib.hg_palette_workspace_bytes(B, H * W, int(other4 is not None))
+        ws = workspace(nb, dev)
+        check(lib.hg_palette_run(x4.data_ptr(), *x4.stride(), ptr(w), *wstr, ptr(other4), *ostr, B, H, W, k, iterations, blocks,
+                                 centres.data_ptr(), sums.data_ptr(), ptr(centres_other), ptr(labels), ws.data_ptr(), nb,
+                                 raw_stream(dev)), 'hg_palette_run')
+    return centres, sums, centres_other, labels
+
+
+def _palettes_of(centres_list, sums, sort):
+    """Palettes that share one clustering (its int64 sums): lab = centres / 128, rgb through lab_to_srgb, weight = W_k / sum W
+    (0 without any weight); with `sort` by descending weight, stably, so that empty clusters trail."""
+    W = sums[..., 0]
+    weight = (W.double() / W.sum(dim=1, keepdim=True).clamp(min=1).double()).float()
+    order = torch.sort(W, dim=1, descending=True, stable=True)[1] if sort else None
+    out = []
+    for c in centres_list:
+        lab = c.float() / PALETTE_UNIT
+        wt = weight
+        if order is not None:
+            lab, wt = torch.gather(lab, 1, order[..., None].expand(-1, -1, 3)), torch.gather(weight, 1, order)
+        out.append(Palette(_lab_units_to_rgb(lab), lab, wt))
+    return out
+
+
+def _palette_images(image, others, k, iterations, weight, what):
+    """Every refusal of palette / paired_palette, ValueError first: (single, image (B, 3, H, W), others, weight (B, H, W))."""
+    _palette_counts(k, iterations, what)
+    single, x4 = _rgb_batch(image, what)
+    o4 = []
+    for o in others:
+        _, t4 = _rgb_batch(o, what, 'other')
+        if t4.shape != x4.shape or t4.device != x4.device:
+            raise ValueError(f'{what}: image and other must have one shape and device, got {tuple(x4.shape)} on {x4.device} and '
+                             f'{tuple(t4.shape)} on {t4.device}')
+        o4.append(t4)
+    B, _, H, W = x4.shape
+    w = _palette_weight(weight, B, H, W, single, x4.device, what)
+    if H * W > (1 << 28) - 1 or not 1 <= B <= 65535:
+        raise ValueError(f'{what}: at most 2^28 - 1 pixels per image and 65535 images, got {B} x {H} x {W}')
+    need_gpu(x4, what, _FOUND)
+    return single, x4, o4, w
+
+
+def palette(image, k=6, iterations=16, weight=None, sort=True):
+    """The K colours that describe an image: integer k-means in CIE Lab (hg_palette_run, include/hg_post.h holds the
+    definition), seeded by weighted farthest-point selection over a 16^3 grid of Lab cells and refined by `iterations` Lloyd
+    steps -- a fixed count, no convergence test, nothing read back: the whole run is enqueued on the current stream, and
+    because every sum is an integer two calls give the same bits.  image: float (3, H, W) or (B, 3, H, W) sRGB, any strides,
+    clamped to [0, 1]; weight: optional (H, W), (B, H, W) or (B, 1, H, W) map, clamped to [0, 1] (a mask, an alpha channel);
+    pixels with a NaN or infinite channel or weight do not count.  Returns Palette(rgb, lab, weight) of shapes (..., K, 3),
+    (..., K, 3), (..., K): lab the centres in Lab units (multiples of 1/128), rgb the same colours through lab_to_srgb, weight
+    each cluster's share W_k / sum W.  sort: clusters by descending weight (stable), so that empty clusters -- weight 0, which an
+    image with fewer than K distinct colours leaves -- trail."""
+    single, x4, _, w = _palette_images(image, (), k, iterations, weight, 'palette')
+    centres, sums, _, _ = _palette_run(x4, w, None, k, iterations)
+    (pal,) = _palettes_of([centres], sums, sort)
+    return Palette(*(t[0] for t in pal)) if single else pal
+
+
+def paired_palette(image, other, k=6, iterations=16, weight=None):
+    """(src, dst): the palette of `image` and, for each of its clusters, the mean Lab colour of `other` -- an image of the same
+    H x W, paired with `image` pixel by pixel, e.g. a recolouring of it -- over the cluster's pixels.  There is no correspondence
+    problem: dst[k] is where the pixels of src[k] went.  Both are sorted by descending weight and share it; an empty cluster has
+    dst == src and weight 0."""
+    single, x4, (o4,), w = _palette_images(image, (other,), k, iterations, weight, 'paired_palette')
+    centres, sums, centres_other, _ = _palette_run(x4, w, o4, k, iterations)
+    src, dst = _palettes_of([centres, centres_other], sums, True)
+    if single:
+        src, dst = Palette(*(t[0] for t in src)), Palette(*(t[0] for t in dst))
+    return src, dst
+
+
+def _palette_tensors(pal, what, name):
+    """(lab (K, 3), weight (K,)) of one un-batched palette, ValueError otherwise (no device is touched)."""
+    ok = isinstance(pal, Palette) and all(torch.is_tensor(t) for t in pal)
+    if not ok or pal.lab.dim() != 2 or pal.lab.shape[1] != 3 or not 1 <= pal.lab.shape[0] <= PALETTE_MAX_K or \
+            tuple(pal.weight.shape) != (pal.lab.shape[0],):
+        got = f'lab {tuple(pal.lab.shape)}, weight {tuple(pal.weight.shape)}' if ok else type(pal).__name__
+        raise ValueError(f'{what}: {name} must be a Palette of one image with 1 .. {PALETTE_MAX_K} colours (lab (K, 3), weight (K,)), '
+                         f'got {got}')
+    return pal.lab, pal.weight
+
+
+def palette_from_rgb(colors, weight=None):
+    """A Palette from colours typed in by a user: colors (K, 3) sRGB in [0, 1] on the device, weight (K,) or None for equal
+    shares."""
+    if not torch.is_tensor(colors) or colors.dim() != 2 or colors.shape[1] != 3 or not 1 <= colors.shape[0] <= PALETTE_MAX_K:
+        raise ValueError(f'palette_from_rgb: colors must be a (K, 3) tensor with 1 .. {PALETTE_MAX_K} rows')
+    need_gpu(colors, 'palette_from_rgb', _FOUND)
+    K = colors.shape[0]
+    rgb = colors.detach().float().clamp(0, 1)
+    norm = srgb_to_lab(rgb.t().reshape(3, 1, K))[:, 0].t()
+    lab = torch.stack((norm[:, 0] * 100.0, norm[:, 1] * 255.0 - 128.0, norm[:, 2] * 255.0 - 128.0), dim=1)
+    wt = torch.full((K,), 1.0 / K, device=rgb.device) if weight is None else weight.detach().float().to(rgb.device)
+    return Palette(rgb, lab, wt)
+
+
+def palette_labels(image, pal):
+    """The uint8 label map of `image` against the colours of `pal` (a Palette, or its lab tensor): for every pixel the index of
+    the nearest centre in Lab (integer distances, the lowest index on ties), 255 for a pixel with a non-finite channel.  (H, W)
+    for a (3, H, W) image and a (K, 3) palette, else (B, H, W) with a (B, K, 3) palette."""
+    what = 'palette_labels'
+    single, x4 = _rgb_batch(image, what)
+    lab = pal.lab if isinstance(pal, Palette) else pal
+    B, _, H, W = x4.shape
+    if torch.is_tensor(lab) and single and lab.dim() == 2:
+        lab = lab.unsqueeze(0)
+    if not torch.is_tensor(lab) or lab.dim() != 3 or lab.shape[0] != B or lab.shape[2] != 3 or not 1 <= lab.shape[1] <= PALETTE_MAX_K:
+        raise ValueError(f'{what}: the palette must hold (K, 3) Lab centres per image, 1 <= K <= {PALETTE_MAX_K}, for {B} image(s)')
+    need_gpu(x4, what, _FOUND)
+    need_gpu(lab, what, _FOUND)
+    x4 = _detached_f32(x4)
+    dev, K, n = x4.device, lab.shape[1], H * W
+    with on_device(dev):
+        centres = torch.round(lab.detach().double() * PALETTE_UNIT).to(torch.int32).contiguous()
+        points = torch.empty((B, lib.hg_palette_point_stride(n), 4), dtype=torch.int16, device=dev)
+        sums = torch.zeros((B, K, 4), dtype=torch.int64, device=dev)
+        labels = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        st = raw_stream(dev)
+        check(lib.hg_palette_quantize(x4.data_ptr(), *x4.stride(), None, 0, 0, 0, points.data_ptr(), B, H, W, st), 'hg_palette_quantize')
+        check(lib.hg_palette_step(points.data_ptr(), points.data_ptr(), B, n, centres.data_ptr(), K, sums.data_ptr(),
+                                  labels.data_ptr(), 0, st), 'hg_palette_step')
+    return labels[0] if single else labels
+
+
+def match_palettes(src, dst, by='lightness'):
+    """`dst` reordered to pair with `src` by rank of L: the darkest colour of dst lands where the darkest of src is, and so on.
+    For palettes typed in by a user, which carry no correspondence (paired_palette's need none).  Two stable torch.sort calls,
+    nothing is read back.  Returns a Palette with dst's colours and weights in src's order."""
+    if by != 'lightness':
+        raise ValueError(f"match_palettes: by must be 'lightness', not {by!r}")
+    s_lab, _ = _palette_tensors(src, 'match_palettes', 'src')
+    d_lab, _ = _palette_tensors(dst, 'match_palettes', 'dst')
+    if s_lab.shape != d_lab.shape:
+        raise ValueError(f'match_palettes: src and dst must have one K, got {s_lab.shape[0]} and {d_lab.shape[0]}')
+    need_gpu(s_lab, 'match_palettes', _FOUND)
+    need_gpu(d_lab, 'match_palettes', _FOUND)
+    rank = torch.sort(torch.sort(s_lab[:, 0], stable=True)[1], stable=True)[1]          # rank of every src colour
+    pick = torch.sort(d_lab[:, 0], stable=True)[1][rank]
+    return Palette(dst.rgb[pick], dst.lab[pick], dst.weight[pick])
+
+
+def color_transfer_palette(source, src_palette, dst_palette, sigma=None, quantize=False):
+    """Palette-based colour transfer (hg_palette_transfer): every pixel x of `source`, in CIE Lab, moves by a smooth blend of
+    the per-cluster shifts, y = x + sum_k u_k (t_k - s_k) / sum_k u_k with u_k = exp(-(|x - s_k|^2 - min_l |x - s_l|^2) / (2
+    sigma^2)) -- between color_transfer_mkl, one affine map for the whole image, and color_transfer_idt, which matches the whole
+    distribution: different colour regions move independently and local structure survives.  source: (H, W, 3) fp32 device
+    view; src_palette, dst_palette: Palettes of K colours each, colour k of the one paired with colour k of the other
+    (paired_palette gives such a pair; match_palettes pairs typed-in ones).  Clusters of weight 0 in either are not live: they
+    pull nothing.  sigma: in Lab units; None takes the mean distance over the live pairs of source colours (1 when there is one
+    colour), computed on the device -- nothing is read back between an extraction and a transfer.  Returns (out, sigma_used):
+    out (H, W, 3) fp32 clipped to [0, 1], or uint8 = (uint8)(out*255) when quantize; sigma_used a 0-d device tensor."""
+    fn = 'color_transfer_palette'
+    s_lab, s_w = _palette_tensors(src_palette, fn, 'src_palette')
+    d_lab, d_w = _palette_tensors(dst_palette, fn, 'dst_palette')
+    if s_lab.shape != d_lab.shape:
+        raise ValueError(f'{fn}: src_palette and dst_palette must have one K, got {s_lab.shape[0]} and {d_lab.shape[0]}')
+    if sigma is not None and not (isinstance(sigma, (int, float)) and 0 < float(sigma) < float('inf')):
+        raise ValueError(f'{fn}: sigma must be a positive finite number of Lab units or None, got {sigma!r}')
+    if torch.is_tensor(source) and (source.dim() != 3 or source.shape[2] != 3):
+        raise ValueError(f'{fn}: source must be an (H, W, 3) image, got {tuple(source.shape)}')
+    src, n, ps, cs = _pixels(source, 'source', fn)
+    need_gpu(s_lab, fn, _FOUND)
+    need_gpu(d_lab, fn, _FOUND)
+    dev = src.device
+    out = torch.empty(source.shape[:2] + (3,), dtype=torch.uint8 if quantize else torch.float32, device=dev)
+    with on_device(dev):
+        s32, d32 = s_lab.detach().float().contiguous(), d_lab.detach().float().contiguous()
+        live = ((s_w > 0) & (d_w > 0)).to(torch.int32).contiguous()
+        sigma_used = torch.empty((), dtype=torch.float32, device=dev)
+        check(lib.hg_palette_transfer(src.data_ptr(), n, ps, cs, s32.data_ptr(), d32.data_ptr(), live.data_ptr(), s32.shape[0],
+                                      0.0 if sigma is None else float(sigma), sigma_used.data_ptr(), out.data_ptr(), int(quantize),
+                                      raw_stream(dev)), 'hg_palette_transfer')
+    return out, sigma_used
+
+
+def palette_histogram(hist_block, pal):
+    """The histogram of a palette's K colours: `hist_block` (RGBuvHistBlock, rgChromaHistBlock or LabHistBlock) called on the
+    1 x K image of the colours with the palette weights as its `weight=` map, so a handful of colours drives whatever takes a
+    target histogram (recoloringTrainer's hist_batch among them).  A LabHistBlock built without from_rgb receives the colours
+    as the normalised Lab it bins.  pal: a Palette of one image or of a batch."""
+    if not isinstance(pal, Palette) or not torch.is_tensor(pal.rgb) or pal.rgb.dim() not in (2, 3) or pal.rgb.shape[-1] != 3:
+        raise ValueError('palette_histogram: pal must be a Palette with rgb (K, 3) or (B, K, 3)')
+    need_gpu(pal.rgb, 'palette_histogram', _FOUND)
+    rgb, lab, wt = (t if pal.rgb.dim() == 3 else t.unsqueeze(0) for t in pal)
+    if getattr(hist_block, 'from_rgb', True):
+        img = rgb.permute(0, 2, 1)
+    else:
+        img = torch.stack((lab[..., 0] / 100.0, (lab[..., 1] + 128.0) / 255.0, (lab[..., 2] + 128.0) / 255.0), dim=1)
+    return hist_block(img.unsqueeze(2).float().contiguous(), weight=wt.unsqueeze(1).float().contiguous())
 
 
 # ---- bilateral guided upsampling (upsampling/BGU.m, bguFit.m, bguSlice.m) -----------------------------------------------

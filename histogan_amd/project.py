@@ -15,7 +15,9 @@ Not here: the VGG perceptual term (see `project`; the weight-free perceptual col
 difference, `delta_e_weight`, and SSIM / MS-SSIM of the lightness plane, `ssim_weight`), face_preprocessing, command-line front ends and file I/O.  The caller
 post-processes `recolor`'s output with post.pyramid_upsampling / post.color_transfer_mkl as the reference's scripts do, or
 with post.color_transfer_idt (recoloringTrainer.evaluate's post_recoloring='idt'), the nonlinear transfer, where the
-recoloured image's whole colour distribution is wanted on the photo and not only its mean and covariance.
+recoloured image's whole colour distribution is wanted on the photo and not only its mean and covariance, or with
+post.color_transfer_palette (post_recoloring='palette'), the third transfer: post.paired_palette of the projected image and
+its recolouring gives K paired colours, and every pixel of the photo moves by a smooth blend of their shifts.
 """
 import torch
 import torch.nn.functional as F

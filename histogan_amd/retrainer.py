@@ -458,16 +458,19 @@ class recoloringTrainer():
         with the Monge-Kantorovich transfer and overwrites the same file at the photo's size.  Both need a batch of
         one (ValueError otherwise).  `post_recoloring='idt'` does the same with the iterative distribution transfer
         (post.color_transfer_idt: nonlinear, matches the output's whole colour distribution rather than its mean and
-        covariance); any other string raises ValueError, and True keeps meaning the Monge-Kantorovich map.
+        covariance), and `post_recoloring='palette'` with the palette transfer (post.paired_palette of the 256x256 input
+        and the network output, k = 8, gives the source and destination colours with no correspondence problem;
+        post.color_transfer_palette moves every pixel of the photo by a smooth blend of the per-cluster shifts); any other
+        string raises ValueError, and True keeps meaning the Monge-Kantorovich map.
         `resizing_method='BGU_native'` carries the result back with bilateral guided upsampling instead (post.bgu_upsampling: the arithmetic of the reference's upsampling/BGU.m on the network's
         8-bit output, without the JPEG round trip) and writes it at exactly the photo's size.
         `resizing_method='BGU'`, which in the reference runs an external Windows executable, raises
         NotImplementedError."""
         upscale = resizing == 'upscaling'
-        if isinstance(post_recoloring, str) and post_recoloring != 'idt':
+        if isinstance(post_recoloring, str) and post_recoloring not in ('idt', 'palette'):
             raise ValueError(f"recoloringTrainer.evaluate: post_recoloring={post_recoloring!r} (True: the Monge-Kantorovich "
-                             "linear transfer; 'idt': the iterative distribution transfer)")
-        recolor = 'idt' if post_recoloring == 'idt' else post_recoloring is True
+                             "linear transfer; 'idt': the iterative distribution transfer; 'palette': the palette transfer)")
+        recolor = post_recoloring if isinstance(post_recoloring, str) else post_recoloring is True
         if upscale and resizing_method not in ('pyramid', 'BGU_native'):
             raise NotImplementedError(f"recoloringTrainer.evaluate: resizing_method={resizing_method!r} for 'upscaling' "
                                       "(implemented: 'pyramid' and 'BGU_native'; 'BGU' runs an external executable in "
@@ -502,7 +505,7 @@ class recoloringTrainer():
             if upscale or recolor:
                 self._full_resolution(generated_images, output_name, upscale, pyramid_levels, swapping_levels,
                                       level_blending, input_image_name, original_image, recolor,
-                                      resizing_method)
+                                      resizing_method, image_batch)
             if save_input is True:
                 save_image_grid(image_batch[:img_bt_sz] if multi else image_batch,
                                 str(self.results_dir / self.name / f'{str(num)}-input.{ext}'),
@@ -510,7 +513,7 @@ class recoloringTrainer():
         return generated_images
 
     def _full_resolution(self, generated_images, output_name, upscale, levels, swapping_levels, blending,
-                         input_image_name, original_image, recolor, method='pyramid'):
+                         input_image_name, original_image, recolor, method='pyramid', image_batch=None):
         """The 'upscaling' ('pyramid' or 'BGU_native') and post_recoloring branches of evaluate
         (ReHistoGAN/rehistoGAN.py:1142-1165) on the kernels of include/hg_post.h; each writes one uint8 image through
         post.save_rgb."""
@@ -529,8 +532,12 @@ class recoloringTrainer():
             if original_image is None:
                 raise ValueError('recoloringTrainer.evaluate: post_recoloring needs original_image')
             src = torch.from_numpy(np.ascontiguousarray(original_image, dtype=np.float32)).to(self.device)
-            transfer = post.color_transfer_idt if recolor == 'idt' else post.color_transfer_mkl
-            out, _ = transfer(src, generated_images[0].permute(1, 2, 0), quantize=True)
+            if recolor == 'palette':
+                pal_src, pal_dst = post.paired_palette(image_batch[0], generated_images[0], k=8)
+                out, _ = post.color_transfer_palette(src, pal_src, pal_dst, quantize=True)
+            else:
+                transfer = post.color_transfer_idt if recolor == 'idt' else post.color_transfer_mkl
+                out, _ = transfer(src, generated_images[0].permute(1, 2, 0), quantize=True)
             post.save_rgb(out, output_name)
 
     def print_log(self):

@@ -34,6 +34,9 @@ extern "C" {
 #define HG_EIDT_ITERATIONS (-22)  /* iterations < 1, or more rotations than one call takes */
 #define HG_EIDT_RELAXATION (-23)  /* relaxation outside (0, 1]                            */
 #define HG_EIDT_PIXELS (-24)      /* a pixel count outside [1, 2^32 - 1]                  */
+/* the refusals of the palette (hg_palette_*, hg_post.h) */
+#define HG_EPALETTE_K (-25)      /* palette: K outside [1, hg_palette_max_k()]           */
+#define HG_EPALETTE_PIXELS (-26)  /* palette: a pixel count outside [1, 2^28 - 1]         */
 
 /* soft-bin kernel, RGBuvHistBlock.py:124-140 */
 #define HG_METHOD_THRESHOLDING 0

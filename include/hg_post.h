@@ -24,11 +24,15 @@
  *                             to hg_color_affine's linear one -- rotate the colour cloud, match the three 1-D marginals by
  *                             CDF matching, rotate back, repeat (no code of the reference, whose color_transfer_MKL.py took
  *                             the linear half of the same toolbox)
+ *   hg_palette_run, hg_palette_*  an image described by K colours (integer k-means in Lab, seeded from a 16^3 grid), the
+ *                             paired palette of two images, and hg_palette_transfer: every pixel moved by a smooth blend of
+ *                             per-cluster shifts, the third transfer between the affine map and the distribution transfer
+ *                             (no code of the reference)
  *
  * Conventions as in hg_hist.h: return 0 / negative HG_E* / positive hipError_t; device pointers unless stated; fp32;
  * enqueue on `stream`; never allocate or synchronise; nothing is launched for invalid arguments.  Planar images are
- * contiguous (C, H, W).  Every result is deterministic: no atomics, fixed reduction order (hg_idt_*: integer atomics
- * only, whose sums do not depend on their order).
+ * contiguous (C, H, W).  Every result is deterministic: no atomics, fixed reduction order (hg_idt_*, hg_palette_*: integer
+ * atomics only, whose sums do not depend on their order).
  */
 #ifndef HG_POST_H
 #define HG_POST_H
@@ -310,6 +314,80 @@ int hg_idt_run(const float *source, int64_t n_src, int64_t src_pix_stride, int64
                int64_t n_tgt, int64_t tgt_pix_stride, int64_t tgt_chan_stride, const float *rotations, int32_t iterations,
                int32_t bins, float relaxation, void *out, int32_t out_u8, void *workspace, size_t workspace_bytes,
                void *stream);
+
+/* Palette extraction and palette-based colour transfer (since version 114; no code of the reference).  An image is described
+ * by K colours, and a recolouring is carried to a photo by moving every pixel with a smooth blend of per-cluster shifts.
+ * Everything that decides a palette is an integer, so nothing depends on the order of a sum and repeats are bit-identical.
+ *
+ * Points.  A pixel is four little-endian 16-bit integers (qL, qa, qb, qw), 8 bytes; a batch is int16 (B, stride, 4) with
+ *   stride = hg_palette_point_stride(n) = n rounded up to a multiple of 2 (the kernels read two points, 16 bytes, per lane),
+ *   16-byte aligned.  (L, a, b) = the chain of hg_srgb_to_lab above in fp64 on the fp32 input clamped to [0, 1], unrounded, in
+ *   Lab units (hg_lab::srgb_to_lab_f64); q = rint(128 value), signed: inside the sRGB gamut |q| < 2^14, and a squared distance
+ *   is dE76^2 in units of 1/128.  qw = rint(65535 clamp(w, 0, 1)), unsigned, 65535 without a weight map.  A pixel with a
+ *   non-finite channel or weight has qw = 0 and coordinates 0, and so have the padding points between n and the stride.
+ *   1 <= n <= 2^28 - 1 pixels per image, so that every signed 64-bit sum below stays under 2^59.
+ * Bins.  16^3 cells: bL = min(max(qL, 0) / 800, 15), ba = clamp((qa + 16384) >> 11, 0, 15), bb likewise, cell = (bL 16 + ba) 16
+ *   + bb.  A cell holds int64 (W, S_L, S_a, S_b) = sum qw, sum qw (qL, qa, qb) over its points with qw > 0: int64 (B, 4096, 4).
+ *   Its mean is m = floor((2 S + W) / (2 W)) per component (floor division: nearest, halves up).
+ * Seeds.  Weighted farthest-point selection over the cells, 1 <= K <= hg_palette_max_k() = 16, one workgroup per image, on the
+ *   device.  Seed 0 = the mean of the cell of largest W, the lowest cell index on ties.  Seed j = the mean of the cell that
+ *   maximises W_i min_{l<j} d^2(m_i, seed_l), the products compared exactly (128 bits), the lowest cell index on ties.  When
+ *   the maximum is 0 the remaining seeds are copies of seed 0; without any weight every seed is (0, 0, 0).
+ * Centres.  int32 (B, K, 3), coordinates within 16 bits.  Distances d^2 are exact integers (64 bits).
+ * Lloyd step.  Two point sets of one length, `assign` and `value` (the same pointer for k-means), and K centres.  Every point
+ *   of `assign` with qw > 0 goes to the centre of least d^2, the lowest index on ties; cluster k receives W_k += qw and
+ *   S_k += qw (the coordinates of the point of `value` at the same position; its qw is not read): int64 sums (B, K, 4) =
+ *   (W, S_L, S_a, S_b), ADDED to what the caller left there.  Optionally a uint8 label per pixel, (B, n), 255 where qw = 0.
+ *   With a second image as `value` the sums give the paired palette: the mean of that image over each cluster's pixels.
+ *   A workgroup adds into 64-bit LDS counters (no bound on its share is needed: the totals stay under 2^59) and flushes
+ *   them to the global ones with 64-bit integer atomics.  There are no float atomics.
+ * Update.  c_k = floor((2 S_k + W_k) / (2 W_k)) per component; a cluster with W_k = 0 keeps its centre.
+ * Run.  quantise, bins, seeds, `iterations` >= 0 times (step, update), then one last step that leaves W, S and the labels of the
+ *   final centres.  A fixed iteration count, no convergence read-back: everything is enqueued on `stream`.  With `other` !=
+ *   NULL (a second image of the same size, its own strides) the run ends with a step whose `value` is that image and an
+ *   update into centres_other, which starts as a copy of the centres, and with an update of the centres from the sums of the
+ *   last step: both palettes are then means over the same clusters (those of the labels), t_k - s_k is the mean shift of
+ *   cluster k, an image paired with itself gives centres_other == centres, and so does an empty cluster.
+ * Transfer.  Source centres s_k and destination centres t_k, fp32 (K, 3) in Lab units, int32 live[K], on the device.  Per pixel
+ *   x = Lab(clamp(rgb, 0, 1)) in fp64 (a NaN component reads as 0); over the live k, in index order:
+ *     d_k = |x - s_k|^2, u_k = exp(-(d_k - min_l d_l) / (2 sigma^2)), y = x + sum_k u_k (t_k - s_k) / sum_k u_k
+ *   and y = x without a live centre.  The output is y through the inverse chain (fp64), clipped to [0, 1], rounded once: (n, 3)
+ *   HWC fp32 (16-byte aligned), or uint8 = (uint8)(v * 255) (truncation, 4-byte aligned) when out_u8 != 0, as hg_color_affine.
+ *   sigma > 0 is used as given; sigma <= 0 asks for the default, computed on the device in fp64 in a fixed order: the mean of
+ *   |s_i - s_j| over the live pairs i < j, and 1 when there is no pair or the mean is 0.  Either way the value used is written
+ *   to sigma_used (one device float), which the per-pixel kernel reads: no host synchronisation between an extraction and a
+ *   transfer.  Pixels are addressed as in hg_color_moments.
+ * Plan.  hg_palette_blocks(n) = the workgroups a per-point launch gives an image of n points (each a contiguous share, a
+ *   multiple of 2 points; grid = blocks x B); `blocks` = 0 takes the plan, 1 .. 1024 forces that count -- the result has the
+ *   same bits.  hg_palette_workspace_bytes(B, n, paired): the points (of both images when paired != 0), the cells and the paired
+ *   sums of hg_palette_run; 16-byte aligned.  The queries return 0 for refused arguments.
+ * Refusals, before any launch: a NULL or misaligned pointer, B outside [1, 65535], a size < 1, blocks outside [0, 1024],
+ *   iterations < 0, only one of other and centres_other, a non-positive stride or a non-finite sigma in the transfer: HG_EINVAL;
+ *   K outside [1, 16]: HG_EPALETTE_K; n (or H W) outside [1, 2^28 - 1]: HG_EPALETTE_PIXELS; a workspace below
+ *   hg_palette_workspace_bytes: HG_EWORKSPACE.
+ * hg_palette_quantize takes x as fp32 (B, 3, H, W) and the optional weight as fp32 (B, H, W), each with its own element strides
+ * (as hg_delta_e); hg_palette_bins adds into `bins` (the caller clears them); hg_palette_update zeroes the sums it has read
+ * when clear_sums != 0. */
+#define HG_PALETTE_MAX_K 16
+int hg_palette_max_k(void);
+int hg_palette_blocks(int64_t n);
+int64_t hg_palette_point_stride(int64_t n);
+size_t hg_palette_workspace_bytes(int32_t B, int64_t n, int32_t paired);
+int hg_palette_quantize(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_t xs_w, const float *weight, int64_t ws_b,
+                        int64_t ws_h, int64_t ws_w, int16_t *points, int32_t B, int32_t H, int32_t W, void *stream);
+int hg_palette_bins(const int16_t *points, int32_t B, int64_t n, int64_t *bins, int32_t blocks, void *stream);
+int hg_palette_seeds(const int64_t *bins, int32_t B, int32_t K, int32_t *centres, void *stream);
+int hg_palette_step(const int16_t *assign, const int16_t *value, int32_t B, int64_t n, const int32_t *centres, int32_t K,
+                    int64_t *sums, uint8_t *labels, int32_t blocks, void *stream);
+int hg_palette_update(int64_t *sums, int32_t B, int32_t K, int32_t *centres, int32_t clear_sums, void *stream);
+int hg_palette_run(const float *x, int64_t xs_b, int64_t xs_c, int64_t xs_h, int64_t xs_w, const float *weight, int64_t ws_b,
+                   int64_t ws_h, int64_t ws_w, const float *other, int64_t os_b, int64_t os_c, int64_t os_h, int64_t os_w,
+                   int32_t B, int32_t H, int32_t W, int32_t K, int32_t iterations, int32_t blocks, int32_t *centres,
+                   int64_t *sums, int32_t *centres_other, uint8_t *labels, void *workspace, size_t workspace_bytes,
+                   void *stream);
+int hg_palette_transfer(const float *x, int64_t n, int64_t pix_stride, int64_t chan_stride, const float *src_centres,
+                        const float *dst_centres, const int32_t *live, int32_t K, float sigma, float *sigma_used, void *out,
+                        int32_t out_u8, void *stream);
 
 #ifdef __cplusplus
 }
