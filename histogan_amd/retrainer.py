@@ -12,14 +12,13 @@ gradient buffers under data parallelism.
 
 Provenance: the step (`train`), `_recolor`, the loss plumbing and the data sources are original.  The API-compatibility
 shell -- the `recoloringTrainer.__init__` attribute block, `config` / `write_config` / `load_config`, `print_log`,
-`model_name`, `init_folders`, `clear`, `save`, `load` and `evaluate`'s parameter list -- follows the reference method for
-method (ReHistoGAN/rehistoGAN.py:721-893, 1076-1226), because its CLI, checkpoints and scripts address these names;
-none of it is on the timed path.
+`model_name`, `init_folders`, `clear` (all of these but `print_log` are `Trainer`'s own functions), `save`, `load` and
+`evaluate`'s parameter list -- follows the reference method for method (ReHistoGAN/rehistoGAN.py:721-893, 1076-1226),
+because its CLI, checkpoints and scripts address these names; none of it is on the timed path.  The discriminator phase
+and the second-stream forward of the step are `trainer.discriminator_phase` and `trainer.SideStreamForward`.
 """
-import json
 from math import floor, log2, pi
 from pathlib import Path
-from shutil import rmtree
 
 import numpy as np
 import torch
@@ -32,8 +31,8 @@ from .hist import hellinger_loss
 from .nets import Discriminator, HistVectorizer
 from .optim import DiffGrad, FlatParams
 from .renets import RecoloringEncoderDecoder, RecoloringGAN
-from .trainer import (NanException, SyntheticData, _freeze_gc_once, _Rng, cast_list, gradient_penalty,
-                      set_requires_grad)
+from .trainer import (NanException, SideStreamForward, SyntheticData, Trainer, _freeze_gc_once, _Rng, cast_list,
+                      discriminator_phase, gradient_penalty, set_requires_grad)
 
 SOBEL_X = ((1, 0, -1), (2, 0, -2), (1, 0, -1))
 SOBEL_Y = ((1, 2, 1), (0, 0, 0), (-1, -2, -1))
@@ -220,9 +219,13 @@ class recoloringTrainer():
         self.last_gp_loss = 0
         self.last_cr_loss = 0
         self.q_loss = 0
+        self.r_loss = 0
+        self.h_loss = 0
         if self.variance_loss is True:
             self.var_loss = 0
         self.rng = _Rng(self.device, rng)
+        self._side = SideStreamForward(self.device)   # the G phase's forward beside the D phase (single-GPU runs)
+        self._gc_frozen = False                       # _freeze_gc_once ran
         self.is_main = ddp.rank() == 0
         self.run_evaluate = True
         self.run_save = True
@@ -239,24 +242,10 @@ class recoloringTrainer():
                                  skip_conn_to_GAN=self.skip_conn_to_GAN, initialize_gan=self.initialize_gan,
                                  internal_hist=self.internal_hist, *args, **kwargs)
 
-    def write_config(self):
-        self.config_path.write_text(json.dumps(self.config()))
-
-    def load_config(self):
-        config = self.config() if not self.config_path.exists() else json.loads(self.config_path.read_text())
-        self.image_size = config['image_size']
-        self.network_capacity = config['network_capacity']
-        self.transparent = config['transparent']
-        self.fq_layers = config['fq_layers']
-        self.fq_dict_size = config['fq_dict_size']
-        self.attn_layers = config.pop('attn_layers', [])
-        del self.GAN
-        self.init_GAN()
-
-    def config(self):
-        return {'image_size': self.image_size, 'network_capacity': self.network_capacity,
-                'transparent': self.transparent, 'fq_layers': self.fq_layers,
-                'fq_dict_size': self.fq_dict_size, 'attn_layers': self.attn_layers}
+    # the reference's two trainers spell these six alike, and so do the two here: one copy (they only touch attributes both
+    # constructors set, and load_config calls this class's init_GAN)
+    write_config, load_config, config = Trainer.write_config, Trainer.load_config, Trainer.config
+    model_name, init_folders, clear = Trainer.model_name, Trainer.init_folders, Trainer.clear
 
     def set_synthetic_data_src(self, pool=4, seed=None):
         seed = ddp.rank() if seed is None else seed
@@ -273,11 +262,6 @@ class recoloringTrainer():
                                           hist_sampling=sampling)
 
     # ------------------------------------------------------------------------------------------
-    def _g_stream(self):
-        if getattr(self, '_gstream', None) is None:
-            self._gstream = torch.cuda.Stream(device=self.device)
-        return self._gstream
-
     def _recolor(self, image_batch, hist_batch, noise):
         """H -> encoder-decoder -> recolouring head, the four wirings of the reference (:934-952)."""
         GAN = self.GAN
@@ -322,11 +306,6 @@ class recoloringTrainer():
         # the G phase's forward on a second stream beside the discriminator's forward / backward (single-GPU runs; see
         # histogan_amd/trainer.py)
         overlap_g = acc == 1 and not ddp.is_dist()
-        if overlap_g and not getattr(self, '_warn_off', False):
-            fn = getattr(torch.autograd.graph, 'set_warn_on_accumulate_grad_stream_mismatch', None)
-            if fn is not None:
-                fn(False)
-            self._warn_off = True
         early = None
 
         # ---- discriminator phase (reference :927-969)
@@ -340,22 +319,10 @@ class recoloringTrainer():
             with torch.no_grad():       # the reference detaches this output; no graph is needed
                 generated_images = self._recolor(image_batch, hist_batch, noise)
             if overlap_g:
-                main = torch.cuda.current_stream(dev)
-                side2 = self._g_stream()
-                side2.wait_event(main.record_event())     # after the forward above (it packed this step's weights)
-                with torch.cuda.stream(side2):
-                    early = g_forward()
-            # two passes with feature quantisation (batch-dependent codebook) and on gradient-penalty steps (the double
-            # backward then covers the real half only)
-            if apply_gradient_penalty or any(q is not None for q in Disc.quantize_blocks):
-                fake_output, fake_q_loss = Disc(generated_images)
-                real_output, real_q_loss = Disc(image_batch)
-                quantize_loss = (fake_q_loss + real_q_loss).mean()
-            else:
-                both_output, both_q_loss = Disc(torch.cat((generated_images, image_batch), dim=0))
-                fake_output, real_output = both_output[:batch_size], both_output[batch_size:]
-                quantize_loss = both_q_loss.mean()
-            divergence = (F.relu(1 + real_output) + F.relu(1 - fake_output)).mean()
+                early = self._side.launch(g_forward)    # after the forward above (it packed this step's weights)
+            real_output, divergence, quantize_loss = discriminator_phase(
+                Disc, generated_images, image_batch, batch_size,
+                apply_gradient_penalty or any(q is not None for q in Disc.quantize_blocks))
             q_val = quantize_loss.detach()
             disc_loss = divergence + quantize_loss
             if apply_gradient_penalty:
@@ -370,20 +337,12 @@ class recoloringTrainer():
         # ---- generator phase (reference :971-1048)
         GAN.G_opt.zero_grad()
         set_requires_grad(Disc, False)
-        d_updated = False
         for i in range(acc):
-            if early is not None:
-                torch.cuda.current_stream(dev).wait_stream(self._g_stream())
-                for t in early:
-                    t.record_stream(torch.cuda.current_stream(dev))
-                image_batch, hist_batch, generated_images = early
-                early = None
-            else:
-                image_batch, hist_batch, generated_images = g_forward()
-            if not d_updated:           # D is updated before it scores the new fakes (reference order)
+            image_batch, hist_batch, generated_images = self._side.join(early) if early is not None else g_forward()
+            early = None
+            if i == 0:                  # D is updated before it scores the new fakes (reference order)
                 GAN._reduce_d.finish()
                 GAN.D_opt.step()
-                d_updated = True
             fake_output, _ = Disc(generated_images)
             d_loss = gamma * fake_output.mean()
             generated_histograms = self.histBlock(generated_images, pre_relu=True)   # == histBlock(F.relu(.)), reference :955
@@ -544,23 +503,10 @@ class recoloringTrainer():
         if not self.is_main:
             return
         msg = (f'\nG: {self.g_loss:.2f} | D: {self.d_loss:.2f} | GP: {self.last_gp_loss:.2f} | R: '
-               f'{getattr(self, "r_loss", 0):.2f} | H: {getattr(self, "h_loss", 0):.2f}')
+               f'{self.r_loss:.2f} | H: {self.h_loss:.2f}')
         if self.variance_loss is True:
             msg += f' | V: {self.var_loss:.2f}'
         print(msg + f' | Q: {self.q_loss:.2f}')
-
-    def model_name(self, num):
-        return str(self.models_dir / self.name / f'model_{num}.pt')
-
-    def init_folders(self):
-        (self.results_dir / self.name).mkdir(parents=True, exist_ok=True)
-        (self.models_dir / self.name).mkdir(parents=True, exist_ok=True)
-
-    def clear(self):
-        rmtree(f'./models/{self.name}', True)
-        rmtree(f'./results/{self.name}', True)
-        rmtree(str(self.config_path), True)
-        self.init_folders()
 
     def save(self, num):
         if self.is_main:

@@ -19,6 +19,10 @@ NaN recovery) -- restructured for the hardware:
   boundary.  Reading `d_loss` / `g_loss` / `h_loss` / `last_gp_loss` / `q_loss` / `pl_mean` (or print_log, save,
   evaluate) flushes what is pending first, so callers always see the values of the last finished step.
 
+The step is `_device_step` (D phase, then `_g_phase`), fed by `_EagerInputs` or -- the step a hipGraph captures,
+`_graphed_step` -- by `_StaticInputs`; `discriminator_phase` and `SideStreamForward` are shared with the ReHistoGAN trainer
+(retrainer.py).  State is declared in `Trainer.__init__`; `init_GAN` drops what was captured on the old model (`_drop_captured`).
+
 Provenance: `_device_step`, `_graphed_step`, `train`, the statistics plumbing and the data sources are original.
 The API-compatibility shell -- `EMA`, `default`, `cast_list`, `is_empty`, `gradient_penalty`, `evaluate`,
 `generate_truncated`, `print_log`, `save` / `load` / `clear`, `model_name`, `init_folders`, `config` handling and the
@@ -55,7 +59,7 @@ G_OVERLAP_DDP = os.environ.get('HG_G_OVERLAP_DDP', 'auto')
 # Plain steps replayed from a captured hipGraph (single process): HG_GRAPH = auto (default) | 1 | 0 | 2.
 #   auto: decided from the first eager plain steps -- the graph is used when the host's enqueue work IS the step (small
 #         batches, slow hosts: batch 4 at 256^2 runs 30 -> 20 ms; the enqueue time then equals the GPU-side step time,
-#         ratio ~1); a GPU-bound step stays eager, where the side-stream overlaps (conv.py, `_g_stream`) are worth 2-4 %
+#         ratio ~1); a GPU-bound step stays eager, where the side-stream overlaps (conv.py, `SideStreamForward`) are worth 2-4 %
 #         that a replayed multi-branch graph does not keep (C3: 48.3 eager vs 50.1 ms replayed at a ratio of 0.5).  The
 #         smallest ratio seen decides: the first steps of a process enqueue slowly (allocator growth, cold caches) and
 #         say nothing about the steady state.
@@ -67,23 +71,22 @@ GRAPH_GP = os.environ.get('HG_GRAPH_GP', '1') != '0'      # gradient-penalty ste
 # generator's fused backward node returns, under the rest of the backward (ddp.GradAllReduce.start_early)
 EARLY_GREDUCE = os.environ.get('HG_EARLY_GREDUCE', '1') != '0'
 LAZY_STATS = os.environ.get('HG_LAZY_STATS', '1') != '0'  # statistics of step n read while step n+1 is queued (0: blocking read-back every step)
+GRAPH_FROM = 6      # a few eager steps before the first capture: caches, workspaces, gc freeze
 
 
 def _lazy_field(name):
     """A statistic the reference keeps as a plain attribute (`self.d_loss = ...`): reading it first flushes the deferred
-    read-backs, so the value is that of the last finished step."""
-    key = '_stat_' + name
-
+    read-backs, so the value is that of the last finished step.  The values live in `Trainer._stats`."""
     def get(self):
-        if self.__dict__.get('_pending'):
+        if self._pending:
             self._drain(0, in_train=False)
         try:
-            return self.__dict__[key]
+            return self._stats[name]
         except KeyError:
             raise AttributeError(name) from None
 
     def set_(self, v):
-        self.__dict__[key] = v
+        self._stats[name] = v
     return property(get, set_)
 
 
@@ -96,6 +99,57 @@ def _cat_batches(a, b):
     out[:a.shape[0]].copy_(a)
     out[a.shape[0]:].copy_(b)
     return out
+
+
+def _no_augment(images, detach=False):
+    return images
+
+
+def discriminator_phase(Disc, fake, real, batch_size, two_passes, augment=_no_augment):
+    """The discriminator's forward of the D phase, shared by both trainers -> real_output, divergence (hinge), quantize
+    loss.  two_passes, reference order: with feature quantisation (the codebook's moving averages and its loss depend on
+    the batch) and on gradient-penalty steps (the penalty's double backward then covers the real half only, not a
+    [fake; real] batch whose fake half carries zero gradients).  Otherwise one pass over [fake; real]: samples are
+    independent, so the values are those of two passes (reference :911-912) with twice the pixels per launch on the small
+    maps.  augment(images, detach=False): DiffAugment of everything the discriminator sees (reference :905-908)."""
+    if two_passes:
+        fake_output, fake_q_loss = Disc(augment(fake, detach=True))
+        real_output, real_q_loss = Disc(augment(real))
+    else:
+        both_output, both_q_loss = Disc(_cat_batches(augment(fake, detach=True), augment(real)))
+        fake_output, real_output = both_output[:batch_size], both_output[batch_size:]
+        fake_q_loss = real_q_loss = both_q_loss * 0.5
+    divergence = (F.relu(1 + real_output) + F.relu(1 - fake_output)).mean()
+    return real_output, divergence, (fake_q_loss + real_q_loss).mean()
+
+
+class SideStreamForward:
+    """A forward pass on a second stream beside the work the current stream goes on with (the G phase's generator
+    forward beside the discriminator's forward / backward: two kernel mixes that stall on different resources, measured
+    20.4 -> 18.9 ms, tools/overlap_probe2.py).  Whether to overlap is the caller's decision."""
+
+    def __init__(self, device):
+        self.device, self.stream = device, None
+
+    def launch(self, fn):
+        """fn() on the side stream, ordered after everything enqueued on the current stream so far."""
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.device)
+            # parameters live on the default stream, part of the graph now runs on another one: the hand-over is intended
+            warn = getattr(torch.autograd.graph, 'set_warn_on_accumulate_grad_stream_mismatch', None)
+            if warn is not None:
+                warn(False)
+        self.stream.wait_event(torch.cuda.current_stream(self.device).record_event())
+        with torch.cuda.stream(self.stream):
+            return fn()
+
+    def join(self, result):
+        """The current stream waits for the side stream and takes over the tensors of `result` (all produced there)."""
+        main = torch.cuda.current_stream(self.device)
+        main.wait_stream(self.stream)
+        for t in result:
+            t.record_stream(main)
+        return result
 
 
 class NanException(Exception):
@@ -118,7 +172,7 @@ def _freeze_gc_once(owner):
     of the cyclic garbage collector walks all of them -- measured 50 ms, once every few steps, on a 62 ms step.  After
     the first step everything that will live for the whole run exists: collect once, then move the survivors to the
     permanent generation so later collections only look at young objects."""
-    if not getattr(owner, '_gc_frozen', False):
+    if not owner._gc_frozen:
         import gc
         gc.collect()
         gc.freeze()
@@ -195,6 +249,12 @@ def latent_to_w(style_vectorizer, latent_descr):
 
 def styles_def_to_tensor(styles_def):
     return torch.cat([t[:, None, :].expand(-1, n, -1) for t, n in styles_def], dim=1)
+
+
+def _hist_style(hist_vectorizer, hist_batch):
+    """The target histograms' latent as the style of the generator's first two layers, (B, 2, latent) (reference :900-902)."""
+    h_w_space = torch.unsqueeze(hist_vectorizer(hist_batch), dim=1)
+    return torch.cat((h_w_space, h_w_space), dim=1)
 
 
 def evaluate_in_chunks(max_batch_size, model, *args):
@@ -318,6 +378,55 @@ def _alpha_weight_grad(images):
     return torch.where(empty, torch.ones_like(a), a)
 
 
+class _EagerInputs:
+    """A step's inputs drawn as the step goes, in the reference's order (:889-949): per phase the latents, the noise
+    image, then the loader's batch."""
+
+    def __init__(self, tr):
+        self.tr, self.latents = tr, None     # latents: mixed or single, chosen per D pass, kept for the G phase (:891, :936)
+
+    def _draw(self):
+        tr, G = self.tr, self.tr.GAN.G
+        self.style = self.latents(tr.batch_size, G.num_layers - 2, G.latent_dim)
+        self.noise = tr.rng.image_noise(tr.batch_size, G.image_size)
+
+    def d_batch(self, gradient_penalty):
+        tr = self.tr
+        self.latents = tr.rng.mixed_list if random() < tr.mixed_prob else tr.rng.noise_list
+        self._draw()
+        batch = next(tr.loader)
+        # d D(real) / d images is only needed by the gradient penalty (the reference sets requires_grad always, :897)
+        return batch['images'].to(tr.device).detach().requires_grad_(gradient_penalty), batch['histograms'].to(tr.device)
+
+    def g_hist(self):
+        self._draw()
+        return next(self.tr.loader)['histograms'].to(self.tr.device)
+
+    def styles(self, phase, hist_batch):
+        """-> w_styles, h_w_space, noise image of `phase` ('d' | 'g')"""
+        return (*self.tr._w_and_hw(self.style, hist_batch), self.noise)
+
+
+class _StaticInputs:
+    """The same three questions answered from the static buffers `gs` a captured step reads (filled by
+    `Trainer._fill_graph_inputs`): no loader, no host-side draw, a launch sequence independent of the mixing choice."""
+
+    def __init__(self, tr, gs):
+        self.tr, self.gs = tr, gs
+
+    def d_batch(self, gradient_penalty):
+        images = self.gs['images']      # (with the penalty: same storage, d D(real) / d images)
+        return images.detach().requires_grad_(True) if gradient_penalty else images, self.gs['hist_d']
+
+    def g_hist(self):
+        return self.gs['hist_g']
+
+    def styles(self, phase, hist_batch):
+        tr, G = self.tr, self.tr.GAN.G
+        w_styles = tr._latents_static(self.gs['tt_' + phase], tr.batch_size, G.num_layers - 2, G.latent_dim)
+        return w_styles, _hist_style(tr.GAN.H, hist_batch), tr.rng.image_noise(tr.batch_size, G.image_size)
+
+
 class Trainer():
     d_loss, g_loss, h_loss = _lazy_field('d_loss'), _lazy_field('g_loss'), _lazy_field('h_loss')
     last_gp_loss, q_loss, pl_mean = _lazy_field('last_gp_loss'), _lazy_field('q_loss'), _lazy_field('pl_mean')
@@ -329,6 +438,8 @@ class Trainer():
                  hist_insz=150, aug_prob=0.0, dataset_aug_prob=0.0, aug_types=None, rng='device',
                  hist_alpha_weight=False, hist_alpha_grad=False, *args, **kwargs):
         from histogram_classes.RGBuvHistBlock import RGBuvHistBlock
+        self._stats = {}                      # values of the _lazy_field statistics (d_loss, ..., pl_mean)
+        self._pending = []                    # [(event, pinned stats, meta)] of steps whose statistics were not read yet
         # opt-in (transparent=True only): histograms weigh every pixel by its alpha -- the targets by the image's alpha
         # channel (FolderData), the generator-side histogram of the G loss by the generated alpha, detached -- so the
         # colour under transparent pixels stops counting.  Default: the reference's behaviour (alpha ignored).
@@ -389,8 +500,20 @@ class Trainer():
         self.lazy_stats = LAZY_STATS          # deferred read-back (module docstring); False: one blocking read-back per step
         self.keep_step_events = False         # bench.py: keep one timing event per step (GPU-side per-step durations)
         self.step_events = []
-        self._pending = []                    # [(event, pinned stats, meta)] of steps whose statistics were not read yet
+        self.phase_events = None              # tools/phase_probe.py: a list collects (name, event, host time) per _mark
+        self.host_enqueue_ms = float('nan')   # host time spent enqueueing the last step
+        self.last_step_graphed = False        # the last step was a hipGraph replay
         self._nan_checkpoint = None           # NaN seen outside train(): the next train() call restores and raises
+        self._host_ring = []                  # pinned host staging buffers of the read-back (_host_buffer)
+        self._last_step_ev = None             # end-of-step event of the previous step (HG_GRAPH=auto's GPU-side step time)
+        self._gc_frozen = False               # _freeze_gc_once ran
+        # hipGraph replay, for the trainer's life: the HG_GRAPH=auto decision (None: not made yet) and the host / GPU time
+        # ratios of the eager plain steps it is made from; a refused capture; the one-time log line
+        self._graph_auto, self._host_ratio, self._graph_failed, self._graph_logged = None, [], False, False
+        self._drop_captured()                 # ... and what lives as long as one model (init_GAN)
+        self._side = SideStreamForward(self.device)   # the G phase's generator forward beside the D phase
+        self._extra_streams_ok = True         # False when ranks share a GPU (decided every step in _device_step)
+        self._reduce_stream = None            # stream of the early all-reduce of G's convolution-weight gradients
         self.is_main = ddp.rank() == 0
         self.run_evaluate = True      # benchmarks switch evaluate()/save() off (excluded from the metric)
         self.run_save = True
@@ -401,10 +524,9 @@ class Trainer():
     def init_GAN(self):
         # a captured train-step graph points into the previous model's buffers: drop it (load() -> load_config() rebuilds
         # the GAN, e.g. on NaN recovery); the next eligible step captures again
-        for k in ('_graphs', '_graph', '_graph_pool', '_gs', '_gs_first'):
-            self.__dict__.pop(k, None)
-        self.__dict__.setdefault('_pending', []).clear()
-        self.__dict__.pop('_last_step_ev', None)
+        self._drop_captured()
+        self._pending.clear()
+        self._last_step_ev = None
         args, kwargs = self.GAN_params
         self.GAN = HistoGAN(lr=self.lr, image_size=self.image_size, network_capacity=self.network_capacity,
                             transparent=self.transparent, fq_layers=self.fq_layers,
@@ -446,14 +568,9 @@ class Trainer():
                                           hist_alpha_weight=self.hist_alpha_weight)
 
     # ------------------------------------------------------------------------------------------
-    def _g_stream(self):
-        if getattr(self, '_gstream', None) is None:
-            self._gstream = torch.cuda.Stream(device=self.device)
-        return self._gstream
-
     def _w_and_hw(self, style, hist_batch):
         GAN = self.GAN
-        if (hist_batch.is_cuda and (self.__dict__.get('_extra_streams_ok', True) or not torch.is_grad_enabled())
+        if (hist_batch.is_cuda and (self._extra_streams_ok or not torch.is_grad_enabled())
                 and not torch.cuda.is_current_stream_capturing()):
             # the histogram vectorizer beside the mapping network instead of behind it -- two independent chains of 8 small
             # serial GEMMs at the head of the generator forward; with autograd recording, the engine runs each chain's
@@ -462,17 +579,14 @@ class Trainer():
             main, aux = torch.cuda.current_stream(hist_batch.device), aux_stream(hist_batch.device)
             aux.wait_event(main.record_event())
             with torch.cuda.stream(aux):
-                h_w_space = torch.unsqueeze(GAN.H(hist_batch), dim=1)
-                h_w_space = torch.cat((h_w_space, h_w_space), dim=1)
+                h_w_space = _hist_style(GAN.H, hist_batch)
             hist_batch.record_stream(aux)
             w_space = styles_def_to_tensor(latent_to_w(GAN.S, style))
             main.wait_stream(aux)
             h_w_space.record_stream(main)
             return w_space, h_w_space
         w_space = latent_to_w(GAN.S, style)
-        h_w_space = GAN.H(hist_batch)
-        h_w_space = torch.unsqueeze(h_w_space, dim=1)
-        h_w_space = torch.cat((h_w_space, h_w_space), dim=1)
+        h_w_space = _hist_style(GAN.H, hist_batch)
         return styles_def_to_tensor(w_space), h_w_space
 
     # ------------------------------------------------------------------------------------------
@@ -488,14 +602,14 @@ class Trainer():
             return False
         if self.gradient_accumulate_every != 1 or self.aug_prob > 0.0 or self.rng.mode != 'device':
             return False
-        if any(q is not None for q in self.GAN.D.quantize_blocks) or getattr(self, '_graph_failed', False):
+        if any(q is not None for q in self.GAN.D.quantize_blocks) or self._graph_failed:
             return False
-        if self.steps < getattr(self, '_graph_from', 6):          # a few eager steps first: caches, workspaces, gc freeze
+        if self.steps < GRAPH_FROM:
             return False
         if self.graph_mode == 'auto':
-            use = getattr(self, '_graph_auto', None)
+            use = self._graph_auto
             if use is None:
-                r = getattr(self, '_host_ratio', [])
+                r = self._host_ratio
                 if len(r) < 2:
                     return False
                 use = self._graph_auto = min(r) > GRAPH_AUTO_RATIO
@@ -509,20 +623,27 @@ class Trainer():
     def _graph_inputs(self):
         """Static buffers the captured step reads: the D phase's batch, the G phase's target histograms, and the two
         style-mixing split points (layers styled by the first latent; all of them = no mixing)."""
-        gs = getattr(self, '_gs', None)
-        if gs is None:
+        if self._gs is None:
             b = next(self.loader)
             dev = self.device
-            gs = self._gs = dict(images=torch.empty_like(b['images']), hist_d=torch.empty_like(b['histograms']),
-                                 hist_g=torch.empty_like(b['histograms']),
-                                 tt_d=torch.zeros((), dtype=torch.int64, device=dev),
-                                 tt_g=torch.zeros((), dtype=torch.int64, device=dev))
+            self._gs = dict(images=torch.empty_like(b['images']), hist_d=torch.empty_like(b['histograms']),
+                            hist_g=torch.empty_like(b['histograms']),
+                            tt_d=torch.zeros((), dtype=torch.int64, device=dev),
+                            tt_g=torch.zeros((), dtype=torch.int64, device=dev))
             self._gs_first = b
-        return gs
+        return self._gs
+
+    def _drop_captured(self):
+        """The hipGraph replay state that points into ONE model's buffers; init_GAN starts it over.  (The decision state
+        -- _graph_auto, _host_ratio, _graph_failed, _graph_logged -- belongs to the trainer's life and stays.)"""
+        self._graphs = {}           # (gradient penalty, alpha, batch size) -> (captured graph, its statistics tensor)
+        self._graph_pool = None     # memory pool the graphs share (they are never in flight together)
+        self._gs = None             # static input buffers the captured launches read (_graph_inputs)
+        self._gs_first = None       # the batch that sized them, held back for the first fill
 
     def _fill_graph_inputs(self, gs):
         layers = self.GAN.G.num_layers - 2
-        b = self.__dict__.pop('_gs_first', None) or next(self.loader)
+        b, self._gs_first = self._gs_first or next(self.loader), None
         gs['images'].copy_(b['images'], non_blocking=True)
         gs['hist_d'].copy_(b['histograms'], non_blocking=True)
         gs['hist_g'].copy_(next(self.loader)['histograms'], non_blocking=True)
@@ -551,11 +672,11 @@ class Trainer():
         if self.graph_mode == '2':             # HG_GRAPH=2: the static-input step WITHOUT capture (A/B of the replay)
             for o in (GAN.D_opt, GAN.G_opt):
                 o.graph_mode = True
-            stats = self._device_step(alpha, gp, False, gs)
+            stats = self._device_step(alpha, gp, False, _StaticInputs(self, gs))
             for o in (GAN.D_opt, GAN.G_opt):
                 o.graph_mode = False
             return stats
-        graphs = self.__dict__.setdefault('_graphs', {})
+        graphs = self._graphs
         # alpha (the Hellinger weight) and the batch size are host scalars baked into the captured launches: the cache is
         # keyed on them, a call with another alpha captures its own graph instead of silently replaying the old value
         key = (bool(gp), float(alpha), int(self.batch_size))
@@ -568,9 +689,8 @@ class Trainer():
                 from .conv import build_pack_plans
                 build_pack_plans(self.device)
                 torch.cuda.synchronize()
-                pool = getattr(self, '_graph_pool', None)
-                with torch.cuda.graph(graph, pool=pool):
-                    stats = self._device_step(alpha, gp, False, gs)
+                with torch.cuda.graph(graph, pool=self._graph_pool):
+                    stats = self._device_step(alpha, gp, False, _StaticInputs(self, gs))
                 self._graph_pool = graph.pool()
             except Exception as e:             # capture refused (driver / library limitation): stay eager
                 for o in (GAN.D_opt, GAN.G_opt):
@@ -580,12 +700,11 @@ class Trainer():
                 torch.cuda.synchronize()
                 print(f'hipGraph capture of the train step failed ({type(e).__name__}: {e}); running eagerly', file=sys.stderr)
                 self._reset_after_failed_step()
-                return self._device_step(alpha, gp, False, None)
+                return self._device_step(alpha, gp, False, _EagerInputs(self))
             for o in (GAN.D_opt, GAN.G_opt):
                 o.graph_mode = False
             graphs[key] = (graph, stats)
-            self._graph = graph
-            if not getattr(self, '_graph_logged', False) and self.is_main:
+            if not self._graph_logged and self.is_main:
                 self._graph_logged = True
                 print(f'train step: replaying captured hipGraphs (HG_GRAPH={self.graph_mode}; latent / noise draws follow '
                       f'the static-input order -- for seed-reproducible runs pin HG_GRAPH=0 or 1)', file=sys.stderr)
@@ -607,9 +726,10 @@ class Trainer():
         GAN._reduce_g.finish()
         weights_changed()
 
-    def _device_step(self, alpha, apply_gradient_penalty, apply_path_penalty, gs=None):
-        """All device work of one optimisation step (reference :853-989), no host synchronisation.  gs: static input
-        buffers when the step is being captured as a hipGraph (None: eager).  Returns the stacked statistics
+    def _device_step(self, alpha, apply_gradient_penalty, apply_path_penalty, inputs):
+        """All device work of one optimisation step (reference :853-989), no host synchronisation.  inputs: where the
+        batch, target histograms, styles and noise come from -- `_EagerInputs`, or `_StaticInputs` for the step a hipGraph
+        captures; nothing else differs between the two.  Returns the stacked statistics
         [D loss, G loss, histogram loss, gradient penalty, quantize loss, path length]."""
         GAN = self.GAN
         dev = self.device
@@ -619,33 +739,17 @@ class Trainer():
         total_disc_loss, total_gen_loss, total_hist_loss = zero(), zero(), zero()
         gp_val, q_val, pl_len = zero(), zero(), None
 
-        batch_size = self.batch_size
-        image_size = GAN.G.image_size
-        latent_dim = GAN.G.latent_dim
-        num_layers = GAN.G.num_layers
         Disc = GAN.D
         acc = self.gradient_accumulate_every
         has_vq = any(q is not None for q in Disc.quantize_blocks)
         # DiffAugment of everything the discriminator sees (reference :873-878, 905-908, 950-951)
         aug = (lambda im, detach=False: GAN.D_aug.augment(im, prob=self.aug_prob, types=self.aug_types, detach=detach)
-               ) if self.aug_prob > 0.0 else (lambda im, detach=False: im)
-
-        def w_and_hw_static(tt_key, hist_batch):
-            w_styles = self._latents_static(gs[tt_key], batch_size, num_layers - 2, latent_dim)
-            h_w_space = torch.unsqueeze(GAN.H(hist_batch), dim=1)
-            return w_styles, torch.cat((h_w_space, h_w_space), dim=1)
+               ) if self.aug_prob > 0.0 else _no_augment
 
         def g_forward():
             """latents, noise, target histograms and the generator forward of the G phase (reference :937-949)"""
-            if gs is None:
-                style = get_latents_fn(batch_size, num_layers - 2, latent_dim)
-                noise = self.rng.image_noise(batch_size, image_size)
-                hist_batch = next(self.loader)['histograms'].to(dev)
-                w_styles, h_w_space = self._w_and_hw(style, hist_batch)
-            else:
-                hist_batch = gs['hist_g']
-                w_styles, h_w_space = w_and_hw_static('tt_g', hist_batch)
-                noise = self.rng.image_noise(batch_size, image_size)
+            hist_batch = inputs.g_hist()
+            w_styles, h_w_space, noise = inputs.styles('g', hist_batch)
             return noise, hist_batch, w_styles, h_w_space, GAN.G(w_styles, h_w_space, noise)
 
         # Under data parallelism (HG_G_OVERLAP_DDP = auto) the second-stream forward is used whenever every rank owns its GPU.
@@ -662,64 +766,22 @@ class Trainer():
             ddp_ok = not ddp.ranks_share_a_device(dev)        # (collective on first use: every rank is in its first step here)
         overlap_g = acc == 1 and ddp_ok
         self._extra_streams_ok = ddp_ok       # (ranks sharing a GPU: no further streams either -- H beside S under autograd, early all-reduce)
-        if overlap_g and not getattr(self, '_warn_off', False):
-            # parameters live on the default stream, part of the graph now runs on another one: the engine's stream
-            # hand-over is intended
-            fn = getattr(torch.autograd.graph, 'set_warn_on_accumulate_grad_stream_mismatch', None)
-            if fn is not None:
-                fn(False)
-            self._warn_off = True
         early = None
 
         # ---- discriminator phase (reference :889-932)
         GAN.D_opt.zero_grad()
         for i in range(acc):
-            if gs is None:
-                get_latents_fn = self.rng.mixed_list if random() < self.mixed_prob else self.rng.noise_list
-                style = get_latents_fn(batch_size, num_layers - 2, latent_dim)
-                noise = self.rng.image_noise(batch_size, image_size)
-                batch = next(self.loader)
-                # d D(real) / d images is only needed by the gradient penalty (the reference sets requires_grad always, :897)
-                image_batch = batch['images'].to(dev).detach().requires_grad_(apply_gradient_penalty)
-                hist_batch = batch['histograms'].to(dev)
-            else:
-                get_latents_fn = None
-                image_batch, hist_batch = gs['images'], gs['hist_d']
-                if apply_gradient_penalty:
-                    image_batch = image_batch.detach().requires_grad_(True)     # same storage: d D(real) / d images
+            image_batch, hist_batch = inputs.d_batch(apply_gradient_penalty)
             with torch.no_grad():   # the reference detaches this output; no graph is needed
-                if gs is None:
-                    w_styles, h_w_space = self._w_and_hw(style, hist_batch)
-                else:
-                    w_styles, h_w_space = w_and_hw_static('tt_d', hist_batch)
-                    noise = self.rng.image_noise(batch_size, image_size)
-                generated_images = GAN.G(w_styles, h_w_space, noise)
+                generated_images = GAN.G(*inputs.styles('d', hist_batch))
             mark('d_phase_g_forward')
             if overlap_g:
-                # The generator forward of the G phase depends on nothing the D phase produces (same generator
-                # weights, own latents): it runs on a second stream beside the discriminator's forward / backward --
-                # two kernel mixes that stall on different resources (measured 20.4 -> 18.9 ms, tools/overlap_probe2.py).
-                # Ordered after the forward above (which also packed this step's generator weights).
-                main = torch.cuda.current_stream(dev)
-                side2 = self._g_stream()
-                side2.wait_event(main.record_event())
-                with torch.cuda.stream(side2):
-                    early = g_forward()
-            # two passes, reference order: with feature quantisation (the codebook's moving averages and its loss depend
-            # on the batch) and on gradient-penalty steps (the penalty's double backward then covers the real half only,
-            # not a [fake; real] batch whose fake half carries zero gradients)
-            if has_vq or apply_gradient_penalty:
-                fake_output, fake_q_loss = Disc(aug(generated_images, True))
-                real_output, real_q_loss = Disc(aug(image_batch))
-            else:
-                # one discriminator pass over [fake; real] (samples are independent: same values as two passes,
-                # :911-912, but twice the pixels per launch on the small maps)
-                both_output, both_q_loss = Disc(_cat_batches(aug(generated_images, True), aug(image_batch)))
-                fake_output, real_output = both_output[:batch_size], both_output[batch_size:]
-                fake_q_loss = real_q_loss = both_q_loss * 0.5
+                # The generator forward of the G phase depends on nothing the D phase produces (same generator weights,
+                # own latents).  Ordered after the forward above (which also packed this step's generator weights).
+                early = self._side.launch(g_forward)
+            real_output, divergence, quantize_loss = discriminator_phase(
+                Disc, generated_images, image_batch, self.batch_size, has_vq or apply_gradient_penalty, aug)
             mark('d_forward')
-            divergence = (F.relu(1 + real_output) + F.relu(1 - fake_output)).mean()
-            quantize_loss = (fake_q_loss + real_q_loss).mean()
             q_val = quantize_loss.detach()
             disc_loss = divergence + quantize_loss
             if apply_gradient_penalty:
@@ -739,7 +801,7 @@ class Trainer():
         set_requires_grad(Disc, False)
         try:
             total_gen_loss, total_hist_loss, pl_len = self._g_phase(
-                alpha, apply_path_penalty, gs, early, g_forward, aug, total_gen_loss, total_hist_loss)
+                alpha, apply_path_penalty, early, g_forward, aug, total_gen_loss, total_hist_loss)
         finally:
             set_requires_grad(Disc, True)
         if ddp.is_dist():
@@ -754,11 +816,11 @@ class Trainer():
         return torch.stack([total_disc_loss, total_gen_loss, total_hist_loss, gp_val.reshape(()),
                             q_val.reshape(()), pl_len if pl_len is not None else zero()]).double()
 
-    def _g_phase(self, alpha, apply_path_penalty, gs, early, g_forward, aug, total_gen_loss, total_hist_loss):
-        """Generator phase of the step (reference :934-989); D's parameters are frozen by the caller."""
-        GAN, dev, Disc, acc = self.GAN, self.device, self.GAN.D, self.gradient_accumulate_every
+    def _g_phase(self, alpha, apply_path_penalty, early, g_forward, aug, total_gen_loss, total_hist_loss):
+        """Generator phase of the step (reference :934-989); D's parameters are frozen by the caller.  early: the first
+        pass's `g_forward()` already launched on the second stream (None: run it here)."""
+        GAN, Disc, acc = self.GAN, self.GAN.D, self.gradient_accumulate_every
         pl_len = None
-        d_updated = False
         def update_d():         # D must be updated before it scores the new fakes (reference order)
             if ddp.is_dist():   # bucket by bucket: the update of bucket i under the all-reduce of bucket i+1
                 GAN.D_opt.step_buckets(GAN._reduce_d)
@@ -766,23 +828,17 @@ class Trainer():
                 GAN._reduce_d.finish()
                 GAN.D_opt.step()
 
-        if early is not None:
-            # the update only needs D's gradients: enqueued before this stream waits for the second one, it runs under
-            # the tail of the G-phase generator forward when that is still in flight
-            update_d()
-            d_updated = True
         for i in range(acc):
             if early is not None:
-                torch.cuda.current_stream(dev).wait_stream(self._g_stream())
-                for t in early:
-                    t.record_stream(torch.cuda.current_stream(dev))    # produced on the second stream, read on this one
-                noise, hist_batch, w_styles, h_w_space, generated_images = early
-                early = None
-            else:
-                noise, hist_batch, w_styles, h_w_space, generated_images = g_forward()
-            if not d_updated:
+                # the update only needs D's gradients: enqueued before this stream waits for the second one, it runs under
+                # the tail of the G-phase generator forward when that is still in flight
                 update_d()
-                d_updated = True
+                forward, early = self._side.join(early), None
+            else:
+                forward = g_forward()
+                if i == 0:
+                    update_d()
+            noise, hist_batch, w_styles, h_w_space, generated_images = forward
             self._mark('g_forward_joined_d_updated')
             fake_output, _ = Disc(aug(generated_images))
             self._mark('g_phase_d_forward')
@@ -815,7 +871,7 @@ class Trainer():
             # data parallelism: at the end of the generator's fused backward node, start the all-reduce of G's
             # convolution-weight gradients.  (Updating them there in a single process was measured and dropped: 865.7
             # against 867.7 images/s without, profiles/r06_ab_early_gopt.json.)
-            early_reduce = (EARLY_GREDUCE and self.__dict__.get('_extra_streams_ok', True) and ddp.is_dist()
+            early_reduce = (EARLY_GREDUCE and self._extra_streams_ok and ddp.is_dist()
                             and acc == 1 and not apply_path_penalty
                             and not torch.cuda.is_current_stream_capturing())
             if early_reduce:
@@ -850,7 +906,7 @@ class Trainer():
             if graphed:
                 stats = self._graphed_step(alpha, apply_gradient_penalty)
             else:
-                stats = self._device_step(alpha, apply_gradient_penalty, apply_path_penalty, None)
+                stats = self._device_step(alpha, apply_gradient_penalty, apply_path_penalty, _EagerInputs(self))
         except NanException:
             raise
         except Exception:
@@ -860,8 +916,7 @@ class Trainer():
 
         # host time spent enqueueing this step (everything before the read-back); graphed: the replay call
         self.host_enqueue_ms = (perf_counter() - t_host0) * 1e3
-        self.last_step_graphed = bool(graphed) and self.graph_mode != '2' and not getattr(self, '_graph_failed', False)
-        self._t_host0 = t_host0
+        self.last_step_graphed = bool(graphed) and self.graph_mode != '2' and not self._graph_failed
 
         # ---- ONE read-back for everything the host needs (reference: >= 7 `.item()` syncs), deferred by one step: the
         # packed statistics go to pinned host memory asynchronously; what the host waits for below is the PREVIOUS
@@ -883,7 +938,7 @@ class Trainer():
         checkpoint_num = floor(self.steps / self.save_every)
         self._pending.append((ev, host, dict(step=self.steps, gp=apply_gradient_penalty, pl=apply_path_penalty,
                                              checkpoint=checkpoint_num, host_ms=self.host_enqueue_ms,
-                                             prev_ev=self.__dict__.get('_last_step_ev'),
+                                             prev_ev=self._last_step_ev,
                                              eager=not graphed)))
         self._last_step_ev = ev
         if self.keep_step_events:
@@ -910,14 +965,13 @@ class Trainer():
         """Called by the generator's fused backward node when its last convolution weight gradient is enqueued (data
         parallelism): the all-reduce of the convolution-weight region of G's flat gradient buffer starts on a stream of its
         own beside the rest of the backward (mapping networks, style projections)."""
-        st = self.__dict__.get('_reduce_stream')
-        if st is None:
-            st = self._reduce_stream = torch.cuda.Stream(device=self.device)
-        self.GAN._reduce_g.start_early(st)
+        if self._reduce_stream is None:
+            self._reduce_stream = torch.cuda.Stream(device=self.device)
+        self.GAN._reduce_g.start_early(self._reduce_stream)
 
     def _mark(self, name):
         """Phase marker of the step on the CURRENT stream (tools/phase_probe.py sets `phase_events = []`; None: no-op)."""
-        pe = self.__dict__.get('phase_events')
+        pe = self.phase_events
         if pe is not None:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
@@ -926,12 +980,11 @@ class Trainer():
     # ---- deferred statistics -----------------------------------------------------------------
     def _host_buffer(self):
         """Pinned host staging for one step's packed statistics (two rotate: one in flight, one being read)."""
-        ring = self.__dict__.setdefault('_host_ring', [])
-        for buf in ring:
+        for buf in self._host_ring:
             if not any(buf is h for _, h, _ in self._pending):
                 return buf
         buf = torch.empty(7, dtype=torch.float64).pin_memory()
-        ring.append(buf)
+        self._host_ring.append(buf)
         return buf
 
     def _drain(self, keep, in_train):
@@ -942,25 +995,25 @@ class Trainer():
             ev, host_t, meta = self._pending.pop(0)
             ev.synchronize()
             host = host_t.numpy().copy()
-            if self.graph_mode == 'auto' and self.__dict__.get('_graph_auto') is None and meta['eager'] \
+            if self.graph_mode == 'auto' and self._graph_auto is None and meta['eager'] \
                     and meta['step'] >= 2 and not (meta['gp'] or meta['pl']) and meta['prev_ev'] is not None:
                 # HG_GRAPH=auto: the host's share of an eager plain step = its enqueue time over the GPU-side time between the
                 # end-of-step events of this step and the previous one (host-bound: the two are equal; GPU-bound: the host
                 # runs ahead).  Event times, not host wall times: with the deferred read-back the host's wall time of a
                 # call says when the PREVIOUS step finished.
                 gpu_ms = meta['prev_ev'].elapsed_time(ev)
-                self.__dict__.setdefault('_host_ratio', []).append(meta['host_ms'] / max(gpu_ms, 1e-3))
+                self._host_ratio.append(meta['host_ms'] / max(gpu_ms, 1e-3))
             meta['prev_ev'] = None
             # generator loss incl. the histogram term and the gradient penalty, as the reference's checks on gen_loss /
             # disc_loss (:978, :925); under data parallelism the flag is the all-reduced one so every rank raises
             has_nan = bool(host[6] > 0 or np.isnan(host[:4]).any())
-            d = self.__dict__
-            d['_stat_d_loss'], d['_stat_g_loss'], d['_stat_h_loss'] = float(host[0]), float(host[1]), float(host[2])
+            s = self._stats         # (not through the properties: their getters drain)
+            s['d_loss'], s['g_loss'], s['h_loss'] = float(host[0]), float(host[1]), float(host[2])
             if meta['gp']:
-                d['_stat_last_gp_loss'] = float(host[3])
-            d['_stat_q_loss'] = float(host[4])
+                s['last_gp_loss'] = float(host[3])
+            s['q_loss'] = float(host[4])
             if meta['pl'] and not np.isnan(host[5]):
-                d['_stat_pl_mean'] = self.pl_length_ma.update_average(d.get('_stat_pl_mean', 0), float(host[5]))
+                s['pl_mean'] = self.pl_length_ma.update_average(s.get('pl_mean', 0), float(host[5]))
             if has_nan:
                 self._pending.clear()
                 if in_train:
@@ -1043,9 +1096,7 @@ class Trainer():
             av_torch = torch.from_numpy(self.av).to(self.device)
             tmp = trunc_psi * (tmp - av_torch) + av_torch
             w_space.append((tmp, num_layers))
-        h_w_space = H(hist_batch)
-        h_w_space = torch.unsqueeze(h_w_space, dim=1)
-        h_w_space = torch.cat((h_w_space, h_w_space), dim=1)
+        h_w_space = _hist_style(H, hist_batch)
         for i in range(int(np.log2(np.sqrt(w_space[0][0].shape[0])))):
             h_w_space = torch.cat((h_w_space, h_w_space), dim=0)
         w_styles = styles_def_to_tensor(w_space)
