@@ -127,7 +127,7 @@ class _GeneratorTrain(torch.autograd.Function):
             # (the to-RGB weight gradient straight into its flat slot when that slot has no writer yet this step)
             nd = need[2 + base:2 + base + PER_BLOCK]
             slot = C.grad_slot(wrgbp) if nd[5] and wrgbp.is_contiguous() else None
-            if slot is not None and slot[0].data_ptr() in slot[1].direct_written:
+            if slot is not None and slot[2]:
                 slot = None
             gconv2, gs_a, gs_rgb, gw_rgb, gd2, gwn2, gbn2 = gstage_bwd(out2, ga, sa, ga is not None, g_rgb, wrgb.reshape(Cr, -1),
                                                                        srgb, d2, nzt, wn2, bn2,
@@ -138,7 +138,7 @@ class _GeneratorTrain(torch.autograd.Function):
                 noise_grad(gconv2, d2, wn2, gnz, True)
             grads[base + 2] = gs_rgb
             if slot is not None:
-                slot[1].direct_written.add(slot[0].data_ptr())
+                C.mark_written(slot[0], slot[1])
             elif nd[5]:
                 grads[base + 5] = gw_rgb.reshape(wrgbp.shape)
             if nd[8]:

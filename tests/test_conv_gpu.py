@@ -212,8 +212,8 @@ def test_batched_packing_launch_matches_single_packs_and_leaves_wsq(gpu_device):
                 wt = C.pack_weights(w, mode)
                 # (a 3x3 weight with both Winograd operands is left out of the batched DIRECT pack until a launch asks for
                 # its direct operand: _direct_operand packs it then -- and the batched Winograd pack equals the single one)
-                if getattr(wt, 'wino', False) is not False:
-                    assert torch.equal(wt.wino, C._wino_pack(w.detach(), mode))
+                if wt.winograd is not None:
+                    assert torch.equal(wt.winograd, C._wino_pack(w.detach(), mode))
                 assert torch.equal(C._direct_operand(wt), C._pack_weights(w.detach(), mode))
         with torch.no_grad():
             flat.data.mul_(2.0)
