@@ -20,8 +20,8 @@ from .launch import channel_sum
 # The weight side: packed operands and their cache, flat gradient slots, the weight-gradient stream.  The launch wrappers reach
 # the two operand accessors as `_wino_u` / `_direct_operand` of THIS module: replacing `_wino_u` switches the Winograd route off.
 from .wpack import (PACK_DGRAD, PACK_FWD, WINO, _pack_weights, _wino_pack, build_pack_plans, cached,  # noqa: F401
-                    drain_pack_streams, enable_pack_cache, grad_slot, mark_written, on_wgrad_stream, pack_weights,
-                    prepack_async, register_grad_slots, side_stream, weights_changed, wino_supported)
+                    drain_pack_streams, enable_pack_cache, grad_slot, on_wgrad_stream, pack_weights, prepack_async,
+                    side_stream, weights_changed, wino_supported)
 from .wpack import direct_operand as _direct_operand
 from .wpack import wino_operand as _wino_u
 
@@ -185,14 +185,14 @@ def _direct_wgrad(w, x, g, stride):
     xc, gc = f32c(x), f32c(g)
     if _batch_pieces(xc, w, stride) != 1:
         return False
-    slot, flat, written = ws
+    slot, flat, written, index = ws
 
     def run():
         if written:
             slot.add_(conv_wgrad(xc, gc, w.shape[2], stride))
         else:
             conv_wgrad(xc, gc, w.shape[2], stride, out=slot)
-            mark_written(slot, flat)
+            flat.mark_written(index)
     on_wgrad_stream(x.device, run, (xc, gc))
     return True
 
@@ -206,7 +206,7 @@ def direct_demod_weight_term(w, gd, d, s1):
     ws = grad_slot(w)
     if ws is None:
         return False
-    slot, flat, written = ws
+    slot, flat, written, index = ws
     gd, d, s1 = f32c(gd), f32c(d), f32c(s1)
     B, N = d.shape
     K, taps = w.shape[1], w.shape[2] * w.shape[3]
@@ -215,7 +215,7 @@ def direct_demod_weight_term(w, gd, d, s1):
         with on_device(w.device):
             check(lib.hg_demod_weight_term(w.data_ptr(), gd.data_ptr(), d.data_ptr(), s1.data_ptr(), slot.data_ptr(), B, N, K,
                                            taps, int(written), raw_stream(w.device)), 'hg_demod_weight_term')
-        mark_written(slot, flat)
+        flat.mark_written(index)
     on_wgrad_stream(w.device, run, (gd, d, s1))
     return True
 

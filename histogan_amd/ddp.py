@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import NullCtx
+from .wpack import side_stream
 
 # HG_DIST_FORCE=1: take the data-parallel code paths (broadcasts, gradient / statistics / Hellinger all-reduces) whenever
 # a process group exists, even at world size 1 -- lets a 1-GPU box run the whole step through RCCL (tests/test_bench_gpu.py)
@@ -123,17 +124,29 @@ class GradAllReduce:
     def __init__(self, flat, chunks=1):
         self.flat = flat
         self.chunks = max(1, int(chunks))
-        self._work = []
-        n, c = flat.numel, self.chunks
-        step = -(-n // c)
-        step = -(-step // 1024) * 1024                      # bucket boundaries on 4 KB
-        self.ranges = [(lo, min(n, lo + step)) for lo in range(0, n, step)]
-        self._full_ranges = list(self.ranges)
+        self._full = self._split(0, flat.numel, self.chunks)     # (plans are tuples: `ranges` hands them out)
+        self._work = []            # one handle per launched bucket of the plan, None once waited for
+        self._plan = self._full    # the bucket plan in force (`ranges`)
+        self._early = 0            # leading buckets of the plan that start_early launched ...
+        self._early_gen = None     # ... in this flat.generation (None: no early start pending)
+
+    @property
+    def ranges(self):
+        return self._plan
 
     def _split(self, lo, hi, c):
         step = -(-(hi - lo) // max(1, c))
         step = max(1024, -(-step // 1024) * 1024)           # bucket boundaries on 4 KB
-        return [(a, min(hi, a + step)) for a in range(lo, hi, step)]
+        return tuple((a, min(hi, a + step)) for a in range(lo, hi, step))
+
+    def _launch(self, ranges):
+        """One asynchronous all-reduce per range (contiguous), pre-scaled where the backend cannot average."""
+        g = self.flat.grad
+        avg = _avg_in_collective()
+        if ranges and not avg:
+            g[ranges[0][0]:ranges[-1][1]].mul_(1.0 / world_size())
+        for lo, hi in ranges:
+            self._work.append(dist.all_reduce(g[lo:hi], op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, async_op=True))
 
     def start_early(self, stream):
         """The all-reduce of the flat buffer's leading convolution-weight region NOW, from `stream`: legal as soon as every one
@@ -145,43 +158,33 @@ class GradAllReduce:
         f = self.flat
         if not is_dist() or self._work or not f.conv_region_final():
             return False
-        from .conv import side_stream
         dev = f.grad.device
         if dev.type == 'cuda':
             stream.wait_stream(side_stream(dev))                                # the weight gradients and demodulation terms
             stream.wait_event(torch.cuda.current_stream(dev).record_event())    # slots written on the calling stream (to-RGB)
         n, hi = f.numel, f.n_conv
         early = self._split(0, hi, self.chunks)
-        self.ranges = early + (self._split(hi, n, max(1, self.chunks // 2)) if n > hi else [])
-        g = f.grad
-        avg = _avg_in_collective()
-        ctx = torch.cuda.stream(stream) if dev.type == 'cuda' else NullCtx()
-        with ctx:
-            if not avg:
-                g[:hi].mul_(1.0 / world_size())
-            for lo, up in early:
-                self._work.append(dist.all_reduce(g[lo:up], op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, async_op=True))
-        self._early = len(early)
+        self._plan = early + (self._split(hi, n, max(1, self.chunks // 2)) if n > hi else ())
+        self._early, self._early_gen = len(early), f.generation
+        with torch.cuda.stream(stream) if dev.type == 'cuda' else NullCtx():
+            self._launch(early)
         return True
+
+    def reset(self):
+        """Drain whatever is in flight and forget an early start: the next start() reduces the full ranges."""
+        self.finish()
+        self._plan, self._early, self._early_gen = self._full, 0, None
 
     def start(self):
         self.flat.gather()
         if not is_dist():
             return
-        early = self.__dict__.pop('_early', 0)
-        if self._work and not early:   # handles of a step that did not get to its wait (an exception in between): drain them
-            self.finish()
-        g = self.flat.grad
-        if not early:
-            self.ranges = list(self._full_ranges)
-        lo0 = self.ranges[early][0] if early < len(self.ranges) else self.flat.numel
-        if _avg_in_collective():
-            op = dist.ReduceOp.AVG
-        else:
-            op = dist.ReduceOp.SUM
-            g[lo0:].mul_(1.0 / world_size())
-        for lo, hi in self.ranges[early:]:
-            self._work.append(dist.all_reduce(g[lo:hi], op=op, async_op=True))
+        # Every bucket of the full plan -- unless start_early already launched the leading ones in THIS generation: then the
+        # rest of its plan.  (reset(): the full plan; nothing to drain or forget unless an earlier step raised before its wait.)
+        if self._early_gen != self.flat.generation:
+            self.reset()
+        self._launch(self._plan[self._early:])
+        self._early, self._early_gen = 0, None
 
     def wait(self, i):
         """The current stream waits for bucket i (no-op when not distributed / already waited for)."""

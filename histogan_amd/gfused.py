@@ -138,7 +138,7 @@ class _GeneratorTrain(torch.autograd.Function):
                 noise_grad(gconv2, d2, wn2, gnz, True)
             grads[base + 2] = gs_rgb
             if slot is not None:
-                C.mark_written(slot[0], slot[1])
+                slot[1].mark_written(slot[3])
             elif nd[5]:
                 grads[base + 5] = gw_rgb.reshape(wrgbp.shape)
             if nd[8]:
@@ -179,7 +179,9 @@ class _GeneratorTrain(torch.autograd.Function):
             grads[idx] = _add(grads[idx], gwd)
         if _N.PHASE_HOOK is not None:
             _N.PHASE_HOOK('gb_generator_blocks_done', True)
-        if AFTER_BLOCKS is not None and need_params:
+        # (a conv / to-RGB weight gradient that goes back to autograd -- a slot written before this pass, a non-contiguous
+        # weight -- reaches its flat slot only in gather(): the convolution-weight region is not final then)
+        if AFTER_BLOCKS is not None and need_params and all(grads[PER_BLOCK * i + k] is None for i in range(L) for k in (3, 4, 5)):
             AFTER_BLOCKS()
         return (g_x0, gnz, *grads)
 

@@ -6,12 +6,12 @@ one (or a few large) collectives reduce all gradients, EMA is one launch -- inst
 launches per parameter tensor (reference: torch_optimizer.DiffGrad over ~150 tensors, and the
 per-tensor EMA loop of histoGAN/histoGAN.py:698-707).
 """
-import ctypes
+import collections
 
 import torch
 
 from ._lib import check, lib, on_device, stream_of
-from .conv import weights_changed
+from .wpack import register_grad_slots, side_stream, weights_changed
 
 
 def conv_first(params):
@@ -22,66 +22,67 @@ def conv_first(params):
     return [p for p in params if p.dim() == 4] + [p for p in params if p.dim() != 4]
 
 
+# One row of FlatParams.slots: parameter `index` lives at elements [offset, offset + numel) of the flat buffers; `view`: the
+# persistent view of that range of the gradient buffer, in the parameter's shape (None without a gradient buffer).
+Slot = collections.namedtuple('Slot', 'index offset numel view')
+
+# The phases of a step's gradients (FlatParams.phase).  OPEN: between zero_grad() and gather() / close(), convolution weights
+# may get their gradient written straight into their slot; CLOSED: no more direct writes, gather() still to come; GATHERED:
+# the flat gradient buffer and every p.grad hold the step's gradients.
+CLOSED, OPEN, GATHERED = 'closed', 'open', 'gathered'
+
+
 class FlatParams:
-    """Re-home `params` (already on their final device) into one flat buffer; optionally with grads."""
+    """Re-home `params` (already on their final device) into one flat buffer; optionally with grads.  `slots` is THE layout:
+    the parameter / gradient views, `n_conv` and the direct-write registration (wpack.register_grad_slots) all come from it."""
 
     def __init__(self, params, with_grad=True):
-        self.params = []
-        seen = set()
-        for p in params:
-            if id(p) not in seen:
-                seen.add(id(p))
-                self.params.append(p)
+        self.params = list({id(p): p for p in params}.values())       # (a parameter given twice is kept once, order kept)
         if not self.params:
             raise ValueError('no parameters')
-        self.n_conv = 0       # elements of the leading run of 4-d parameters
-        for p in self.params:
-            if p.dim() != 4:
-                break
-            self.n_conv += p.numel()
         dev = self.params[0].device
         self.numel = sum(p.numel() for p in self.params)
         self.data = torch.empty(self.numel, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(self.numel, dtype=torch.float32, device=dev) if with_grad else None
+        # persistent views of every parameter's slice of the gradient buffer (gather() runs twice per step over ~150
+        # parameters: slicing + viewing them anew cost the host ~1.5 ms per call)
+        self.slots = []
         off = 0
-        for p in self.params:
+        for i, p in enumerate(self.params):
             n = p.numel()
+            self.slots.append(Slot(i, off, n, self.grad[off:off + n].view(p.shape) if with_grad else None))
             view = self.data[off:off + n].view(p.shape)
             view.copy_(p.data)
             p.data = view
             if with_grad:
-                p.grad = self.grad[off:off + n].view(p.shape)
+                p.grad = self.slots[i].view
             off += n
-        # persistent views of every parameter's slice of the gradient buffer (gather() runs twice per step over ~150
-        # parameters: slicing + viewing them anew cost the host ~1.5 ms per call)
-        self._gviews = []
+        lead = next((s for p, s in zip(self.params, self.slots) if p.dim() != 4), None)
+        self.n_conv = self.numel if lead is None else lead.offset       # elements of the leading run of 4-d parameters
+        # per-step state.  Convolution weights may get their gradient written straight into their slot (conv._direct_wgrad)
+        self.generation = 0        # the step: incremented by zero_grad()
+        self.phase = GATHERED      # (before the first zero_grad() the buffers are consistent: gather() has nothing to do)
+        self.written = set()       # indices of the slots written directly in this generation
         if with_grad:
-            off = 0
-            for p in self.params:
-                n = p.numel()
-                self._gviews.append(self.grad[off:off + n].view(p.shape))
-                off += n
-        # convolution weights may get their gradient written straight into self.grad (conv._direct_wgrad)
-        self.direct_ok = False
-        self.direct_written = set()
-        if with_grad:
-            from .conv import register_grad_slots
             register_grad_slots(self)
+
+    def slot(self, index):
+        """(slot view, self, slot already written this step, index) while direct writes are accepted, else None (wpack.grad_slot)."""
+        if self.phase != OPEN:
+            return None
+        return self.slots[index].view, self, index in self.written, index
+
+    def mark_written(self, index):
+        """Slot `index` holds a gradient of this step, written directly: the next direct write adds to it, gather() keeps it."""
+        self.written.add(index)
 
     def conv_region_final(self):
         """True when every parameter of the leading convolution-weight region (n_conv elements) has its gradient of this step
         in its flat slot, written directly (conv._direct_wgrad, the demodulation term, gfused's to-RGB write) and by nothing
         else -- the condition under which that region may be reduced / updated before gather()."""
-        if self.n_conv <= 0 or not self.direct_ok or self.grad is None:
+        if self.n_conv <= 0 or self.phase != OPEN or self.grad is None:
             return False
-        base, off = self.grad.data_ptr(), 0
-        for p in self.params:
-            if off >= self.n_conv:
-                break
-            if base + 4 * off not in self.direct_written or p.grad is not None:
-                return False
-            off += p.numel()
-        return True
+        return all(s.index in self.written and p.grad is None for p, s in zip(self.params, self.slots) if s.offset < self.n_conv)
 
     def zero_grad(self):
         """Drop the parameter gradients.  With `.grad = None` autograd's AccumulateGrad hands over the incoming gradient
@@ -89,44 +90,44 @@ class FlatParams:
         copies all of them into the flat gradient buffer with a few multi-tensor launches."""
         for p in self.params:
             p.grad = None
-        self._gathered = False
-        self.direct_written = set()
-        self.direct_ok = True
+        self.generation += 1
+        self.written = set()
+        self.phase = OPEN
+
+    def close(self):
+        """Stop accepting direct writes (wpack.grad_slot answers None from here on); gather() is still to come."""
+        if self.phase == OPEN:
+            self.phase = CLOSED
 
     def gather(self):
         """Make `self.grad` (and every `p.grad`, re-pointed to its slice) hold the gradients of the last backward
         passes; parameters that received none get zeros.  Idempotent."""
-        if getattr(self, '_gathered', True):
+        if self.phase == GATHERED:
             return
-        self.direct_ok = False
-        if self.direct_written and self.grad.is_cuda:   # weight gradients written on the side stream: order them before any reader
-            from .conv import side_stream
-            if not torch.cuda.is_current_stream_capturing():   # (captured: written on this branch)
-                torch.cuda.current_stream(self.grad.device).wait_stream(side_stream(self.grad.device))
+        self.close()
+        # weight gradients written on the side stream: order them before any reader (captured: written on this branch)
+        if self.written and self.grad.is_cuda and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(self.grad.device).wait_stream(side_stream(self.grad.device))
         dst, src, missing, both = [], [], [], []
-        off = 0
-        base = self.grad.data_ptr()
-        for p, v in zip(self.params, self._gviews):
-            n = p.numel()
+        for p, (i, _, _, v) in zip(self.params, self.slots):
             pg = p.grad
-            if base + 4 * off in self.direct_written:
-                if pg is not None and pg is not v and pg.data_ptr() != base + 4 * off:
+            if i in self.written:
+                if pg is not None and pg is not v and pg.data_ptr() != v.data_ptr():
                     both.append((v, pg))           # autograd ALSO delivered a part (a pass that recorded a graph)
             elif pg is None:
                 missing.append(v)
-            elif pg is not v and pg.data_ptr() != base + 4 * off:
+            elif pg is not v and pg.data_ptr() != v.data_ptr():
                 dst.append(v)
                 src.append(pg)
             if pg is not v:
                 p.grad = v
-            off += n
         if dst:
             torch._foreach_copy_(dst, src)
         if missing:
             torch._foreach_zero_(missing)
         if both:
             torch._foreach_add_([v for v, _ in both], [g for _, g in both])
-        self._gathered = True
+        self.phase = GATHERED
 
 
 class DiffGrad:
@@ -174,16 +175,18 @@ class DiffGrad:
         reducer.finish()
         weights_changed(f.data)
 
+    def _buffers(self, lo=0):
+        """Addresses of element `lo` of the five flat buffers, in the order the step kernels take them."""
+        f = self.flat
+        return [t.data_ptr() + 4 * lo for t in (f.data, f.grad, self.exp_avg, self.exp_avg_sq, self.previous_grad)]
+
     def _launch(self, lo, hi, step_count):
         """hg_diffgrad_step over elements [lo, hi) of the flat buffers, as step number `step_count`."""
         f = self.flat
         lr = self.param_groups[0]['lr']
-        o = 4 * lo
         with on_device(f.data.device):
-            check(lib.hg_diffgrad_step(f.data.data_ptr() + o, f.grad.data_ptr() + o, self.exp_avg.data_ptr() + o,
-                                       self.exp_avg_sq.data_ptr() + o, self.previous_grad.data_ptr() + o, hi - lo,
-                                       float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                       step_count, stream_of(f.data)), 'hg_diffgrad_step')
+            check(lib.hg_diffgrad_step(*self._buffers(lo), hi - lo, float(lr), float(self.betas[0]), float(self.betas[1]),
+                                       float(self.eps), step_count, stream_of(f.data)), 'hg_diffgrad_step')
 
     def step(self):
         f = self.flat
@@ -192,15 +195,12 @@ class DiffGrad:
             raise RuntimeError('DiffGrad: parameters are not on a GPU; no CPU implementation')
         if self.graph_mode:           # being captured: step size from device memory, counter advanced by prepare_replay()
             with on_device(f.data.device):
-                check(lib.hg_diffgrad_step_dev(f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                               self.exp_avg_sq.data_ptr(), self.previous_grad.data_ptr(), f.numel,
-                                               self._step_size_dev.data_ptr(), float(self.betas[0]),
+                check(lib.hg_diffgrad_step_dev(*self._buffers(), f.numel, self._step_size_dev.data_ptr(), float(self.betas[0]),
                                                float(self.betas[1]), float(self.eps), stream_of(f.data)),
                       'hg_diffgrad_step_dev')
-            weights_changed(f.data)
-            return
-        self.step_count += 1
-        self._launch(0, f.numel, self.step_count)
+        else:
+            self.step_count += 1
+            self._launch(0, f.numel, self.step_count)
         weights_changed(f.data)
 
 

@@ -721,9 +721,9 @@ class Trainer():
         set_requires_grad(GAN.D, True)
         for o in (GAN.D_opt, GAN.G_opt):
             o.zero_grad()
-            o.flat.direct_ok = False
-        GAN._reduce_d.finish()
-        GAN._reduce_g.finish()
+            o.flat.close()
+        GAN._reduce_d.reset()
+        GAN._reduce_g.reset()
         weights_changed()
 
     def _device_step(self, alpha, apply_gradient_penalty, apply_path_penalty, inputs):

@@ -76,7 +76,7 @@ class _Owner:
 
 
 class _Record:
-    """One registered convolution weight.  slot: (offset, numel, weakref to the FlatParams) of its flat gradient slot, or None;
+    """One registered convolution weight.  slot: (weakref to the FlatParams, index in its slot table) of its gradient slot, or None;
     geom: its sizes in the batched pack, asked once (plan_weights)."""
     __slots__ = ('key', 'ref', 'owner', 'slot', 'geom', 'stamp', 'ops', 'vals', 'wants_direct', 'wants_wino')
 
@@ -413,30 +413,20 @@ def register_grad_slots(flat):
     """Called by FlatParams: convolution weights (4-d parameters) of `flat` may receive their gradient directly.
     Only a weak reference to the owner is kept."""
     ref = weakref.ref(flat)
-    off = 0
-    for p in flat.params:
-        n = p.numel()
-        if p.dim() == 4 and flat.grad is not None:
-            _register(p).slot = (off, n, ref)
-        off += n
+    for p, s in zip(flat.params, flat.slots):
+        if p.dim() == 4:
+            _register(p).slot = (ref, s.index)
 
 
 def grad_slot(w):
-    """(slot view, owner FlatParams, slot already written this step) of a registered convolution weight whose gradient may
-    be written directly right now (between zero_grad() and gather(), plain backward), or None."""
+    """(slot view, owner FlatParams, slot already written this step, slot index for the owner's mark_written()) of a registered
+    convolution weight whose gradient may be written directly right now (between zero_grad() and gather(), plain backward), or None."""
     rec = None if torch.is_grad_enabled() else record(w)
     if rec is None or rec.slot is None:
         return None
-    off, n, ref = rec.slot
+    ref, index = rec.slot
     flat = ref()
-    if flat is None or not flat.direct_ok:
-        return None
-    slot = flat.grad[off:off + n].view(w.shape)
-    return slot, flat, slot.data_ptr() in flat.direct_written
-
-
-def mark_written(slot, flat):
-    flat.direct_written.add(slot.data_ptr())
+    return None if flat is None else flat.slot(index)
 
 
 side_stream = functools.partial(_device_stream, 'wgrad')
@@ -445,7 +435,8 @@ side_stream = functools.partial(_device_stream, 'wgrad')
 def on_wgrad_stream(device, run, reads):
     """run() on the weight-gradient stream, behind everything enqueued on the current stream; `reads`: the tensors it reads
     (the caching allocator must not recycle them under the kernel).  Overwrite-vs-accumulate of a flat gradient slot is decided
-    from the host-side set `direct_written` at ENQUEUE time: every direct write goes through here, onto ONE stream in order.
+    from the owner's host-side set of written slot indices (`FlatParams.written`) at ENQUEUE time: every direct write goes through
+    here, onto ONE stream in order.
     Inside a hipGraph capture every fork to the side stream becomes a cross-branch dependency edge (~100 per step): measured
     slower than the eager side stream; the direct write (no per-parameter copy) stays, on the capturing stream."""
     if torch.cuda.is_current_stream_capturing():

@@ -80,11 +80,9 @@ def _worker(rank, world, port, q):
         re_ = ddp.GradAllReduce(fe, 2)
         for step in range(2):
             fe.zero_grad()
-            off = 0
-            for p_ in fe.params[:2]:
-                fe.grad[off:off + p_.numel()].fill_(float(rank + 1 + step))
-                fe.direct_written.add(fe.grad.data_ptr() + 4 * off)
-                off += p_.numel()
+            for s_ in fe.slots[:2]:
+                s_.view.fill_(float(rank + 1 + step))
+                fe.mark_written(s_.index)
             assert fe.conv_region_final()
             if step == 0:
                 assert re_.start_early(None) and len(re_._work) == 2
@@ -132,6 +130,70 @@ def test_flat_grad_allreduce_world2():
     assert sorted(res) == [(0, 'ok'), (1, 'ok')], res
 
 
+def _stale_early_worker(rank, world, port, q, via_reset):
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    try:
+        from histogan_amd import ddp
+        from histogan_amd.optim import FlatParams, conv_first
+        ps = [torch.nn.Parameter(torch.zeros(7)), torch.nn.Parameter(torch.zeros(40, 8, 3, 3)), torch.nn.Parameter(torch.zeros(3, 40, 1, 1)),
+              torch.nn.Parameter(torch.zeros(2000))]
+        fe = FlatParams(conv_first(ps))
+        red = ddp.GradAllReduce(fe, 2)
+
+        def write_conv_slots():
+            for s_ in fe.slots[:2]:
+                s_.view.fill_(float(rank + 1))
+                fe.mark_written(s_.index)
+            assert fe.conv_region_final()
+        # step A: the early start happens, then the backward raises -- no start(), no wait
+        fe.zero_grad()
+        write_conv_slots()
+        assert red.start_early(None) and len(red._work) == 2
+        for w in red._work:      # (gloo reduces in place from its own threads: let step A's collectives land before step B
+            w.wait()             # refills the slots -- on a GPU the streams order the two; the handles stay where they are)
+        if via_reset:                                      # what the trainer does after a failed step
+            fe.zero_grad()
+            fe.close()
+            red.reset()
+            assert red._work == [] and red.ranges[0][0] == 0 and red.ranges[-1][1] == fe.numel
+        # step B: a whole step without an early start
+        fe.zero_grad()
+        write_conv_slots()
+        ps[0].grad = torch.full((7,), 10.0 * (rank + 1))
+        ps[3].grad = torch.full((2000,), 100.0 * (rank + 1))
+        red.start()
+        assert len(red._work) == len(red.ranges) and all(w is not None for w in red._work)     # step A's handles are gone
+        assert red.ranges[0][0] == 0 and red.ranges[-1][1] == fe.numel and all(a[1] == b[0] for a, b in zip(red.ranges, red.ranges[1:]))
+        red.finish()
+        assert red._work == []
+        want = torch.cat([torch.full((fe.n_conv,), 1.5), torch.full((7,), 15.0), torch.full((2000,), 150.0)])
+        assert torch.allclose(fe.grad, want), (fe.grad[0].item(), fe.grad[fe.n_conv].item(), fe.grad[-1].item())
+        q.put((rank, 'ok'))
+    except Exception as e:  # pragma: no cover
+        q.put((rank, repr(e)))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize('via_reset', [False, True], ids=['start() alone', 'reset() first'])
+def test_stale_early_start_does_not_reach_the_next_step(via_reset):
+    """An early start whose step never got to start() (its backward raised) must not make the next step skip the
+    convolution-weight region: start() sees the early start belongs to another generation of the flat buffer, drains its handles
+    and reduces the full ranges; reset() does the same at once."""
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_stale_early_worker, args=(r, 2, port, q, via_reset)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=120) for _ in procs]
+    for p in procs:
+        p.join(30)
+    assert sorted(res) == [(0, 'ok'), (1, 'ok')], res
+
+
 def test_single_process_is_identity():
     from histogan_amd import ddp
     from histogan_amd.optim import FlatParams
@@ -151,23 +213,23 @@ def test_flatparams_gather_with_directly_written_slots():
     """FlatParams.gather(): slices written directly (conv._direct_wgrad, here simulated on CPU) are kept, autograd-delivered
     gradients are copied in, a parameter that got both has them added, parameters without a gradient are zeroed."""
     import torch
-    from histogan_amd.optim import FlatParams
+    from histogan_amd.optim import GATHERED, OPEN, FlatParams
     ps = [torch.nn.Parameter(torch.randn(4, 3, 3, 3)), torch.nn.Parameter(torch.randn(5)),
           torch.nn.Parameter(torch.randn(2, 3, 1, 1)), torch.nn.Parameter(torch.randn(7))]
     flat = FlatParams(ps)
     flat.grad.fill_(123.0)                       # stale content of the previous step
     flat.zero_grad()
-    assert flat.direct_ok and all(p.grad is None for p in ps)
+    assert flat.phase == OPEN and all(p.grad is None for p in ps)
     base = flat.grad.data_ptr()
     offs = [0, ps[0].numel(), ps[0].numel() + ps[1].numel(), ps[0].numel() + ps[1].numel() + ps[2].numel()]
     d0, d2 = torch.randn(ps[0].shape), torch.randn(ps[2].shape)
-    flat.grad[offs[0]:offs[0] + ps[0].numel()].copy_(d0.reshape(-1)); flat.direct_written.add(base + 4 * offs[0])
-    flat.grad[offs[2]:offs[2] + ps[2].numel()].copy_(d2.reshape(-1)); flat.direct_written.add(base + 4 * offs[2])
+    flat.grad[offs[0]:offs[0] + ps[0].numel()].copy_(d0.reshape(-1)); flat.mark_written(0)
+    flat.grad[offs[2]:offs[2] + ps[2].numel()].copy_(d2.reshape(-1)); flat.mark_written(2)
     a1, a2 = torch.randn(5), torch.randn(ps[2].shape)
     ps[1].grad = a1.clone()                      # delivered by autograd only
     ps[2].grad = a2.clone()                      # delivered by autograd AND written directly
     flat.gather()
-    assert not flat.direct_ok
+    assert flat.phase == GATHERED
     assert torch.equal(ps[0].grad, d0) and torch.equal(ps[1].grad, a1) and torch.allclose(ps[2].grad, d2 + a2)
     assert torch.equal(ps[3].grad, torch.zeros(7))
     for p, o in zip(ps, offs):

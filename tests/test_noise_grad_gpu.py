@@ -6,6 +6,7 @@
    run's own LeakyReLU branches (the method of test_c3_parity_gpu.py's generator test);
 4. the chain rule between forward_(inoise=) and forward_(noise1=, noise2=);
 5. frozen weights: no weight-gradient launch, no flat-slot write, no AFTER_BLOCKS;
+   and AFTER_BLOCKS only when no convolution / to-RGB weight gradient goes back to autograd (two passes before gather());
 6. an in-place update of the noise image reaches the next forward (the cache of its transposed copy);
 7. histogan_amd.project against the same Adam steps on the oracle.
 
@@ -322,12 +323,56 @@ def test_frozen_weights_cost_no_weight_gradient(gpu_device, monkeypatch):
         if frozen:
             assert calls == {'wgrad': 0, 'direct': 0, 'after': 0}, calls
             assert all(p.grad is None for p in G.parameters())
-            assert flat.direct_written == set() and not bool(flat.grad.any())
+            assert flat.written == set() and not bool(flat.grad.any())
         else:
             assert calls == {'wgrad': WGRAD_CALLS_TRAINABLE, 'direct': WGRAD_CALLS_TRAINABLE, 'after': 1}, calls
-            assert len(flat.direct_written) >= 2 * len(G.blocks) and bool(flat.grad.any())
+            assert len(flat.written) >= 2 * len(G.blocks) and bool(flat.grad.any())
     for a, b, n in zip(res[True], res[False], ('styles', 'hists', 'noise')):
         assert relmax(_np(a), _np(b)) <= TOL, n
+
+
+def test_after_blocks_waits_for_weight_gradients_returned_to_autograd(gpu_device, monkeypatch):
+    """Two backward passes between zero_grad() and gather() (gradient accumulation).  (a) AFTER_BLOCKS announces that every
+    convolution weight of the generator has its final gradient in its flat slot: true after the first pass, not after the
+    second, whose to-RGB weight gradients go back to autograd because their slots are already written -- they reach the flat
+    buffer only in gather().  (b) After gather() the flat gradient is the sum of the two passes, against the per-block
+    autograd path (HG_GFUSED=0), at 1e-5: the tightest bar test_c3_fused_gpu.py holds a weight gradient to (test_gstage_gpu.py's
+    fused-versus-per-block comparison of every gradient allows 2e-5)."""
+    from histogan_amd import gfused
+    from histogan_amd.optim import FlatParams
+    dev = gpu_device
+    G = _generator(32, 2, 3, dev)
+    params = list(G.parameters())
+    passes = [_inputs(G, 3, seed, dev) for seed in (3, 4)]
+    want = None
+    gfused.GFUSED = False
+    try:
+        for st, hi, nz, go in passes:
+            gr = torch.autograd.grad((G(st, hi, nz) * go).sum(), params)
+            want = gr if want is None else [a + b for a, b in zip(want, gr)]
+    finally:
+        gfused.GFUSED = True
+    flat = FlatParams(params)
+    fired = []
+    monkeypatch.setattr(gfused, 'AFTER_BLOCKS', lambda: fired.append(len(flat.written)))
+    flat.zero_grad()
+    counts = []
+    for st, hi, nz, go in passes:
+        rgb = G(st, hi, nz)
+        assert type(rgb.grad_fn).__name__.startswith('_GeneratorTrain')
+        (rgb * go).sum().backward()
+        counts.append(len(fired))
+    print(f'AFTER_BLOCKS calls after pass 1, 2: {counts}')
+    assert counts == [1, 1], counts
+    assert fired[0] == 3 * len(G.blocks)                     # conv1, conv2 and to-RGB of every block, written directly
+    rgb_w = [b.to_rgb.conv.weight for b in G.blocks]
+    assert all(p.grad is not None for p in rgb_w)              # the second pass' to-RGB parts, held by autograd until gather()
+    flat.gather()
+    torch.cuda.synchronize()
+    errs = {n: relmax(_np(p.grad), _np(w)) for (n, p), w in zip(G.named_parameters(), want)}
+    print(f'sum of two passes against the per-block path: worst relmax {max(errs.values()):.2e}')
+    assert all(p.grad is s.view for p, s in zip(params, flat.slots))
+    assert max(errs.values()) <= 1e-5, max(errs.items(), key=lambda kv: kv[1])
 
 
 # ---- 6. in-place update of the noise image -------------------------------------------------------------------------

@@ -853,7 +853,7 @@ def test_generator_stages_are_the_same_bits_behind_any_pad(mode, gen_setup, gpu_
             for i, blk in enumerate(G.blocks):
                 x, rgb = blk.forward_(x, rgb, t[3 * i], t[3 * i + 1], t[3 * i + 2], inoise=noise)
         rgb.backward(gen_setup['gout'])
-        assert flat.direct_written, 'no gradient was written straight into a flat slot'
+        assert flat.written, 'no gradient was written straight into a flat slot'
         st = _named_state(G, flat, dict(rgb=rgb.detach().clone(), **{'gt%d' % i: u.grad.clone() for i, u in enumerate(t)}))
         res[pad] = _after_step(G, opt, st)
         assert all(bool(torch.isfinite(v).all()) for v in res[pad].values())
@@ -960,7 +960,7 @@ def test_discriminator_is_the_same_bits_behind_any_pad(attn, gpu_device):
         flat.zero_grad()
         logits, _ = D(x)
         logits.backward(gl)
-        assert flat.direct_written
+        assert flat.written
         res[pad] = _after_step(D, opt, _named_state(D, flat, dict(logits=logits.detach().clone())))
         assert all(bool(torch.isfinite(v).all()) for v in res[pad].values())
     for pad in PADS[1:]:
@@ -1014,7 +1014,7 @@ def test_rehistogan_flat_order_gives_the_bits_of_the_aligned_order(gpu_device):
         latent, rgb = ED(x, hist)
         gen = G(latent, rgb, hw, noise)
         gen.backward(gout)
-        assert flat.direct_written
+        assert flat.written
         res[order] = _after_step(mods, opt, _named_state(mods, flat, dict(gen=gen.detach().clone())))
         assert all(bool(torch.isfinite(v).all()) for v in res[order].values())
     assert _differing(res['retrainer'], res['conv_first']) == []

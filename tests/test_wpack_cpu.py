@@ -123,14 +123,14 @@ def test_grad_slot_lookup():
     assert W.grad_slot(ps[0]) is None and W.grad_slot(ps[2]) is None    # grad mode on
     with torch.no_grad():
         for i in (0, 2):
-            slot, owner, written = W.grad_slot(ps[i])
+            slot, owner, written, index = W.grad_slot(ps[i])
             want = flat.grad[offs[i]:offs[i] + ps[i].numel()].view(ps[i].shape)
             assert owner is flat and not written
             assert slot.data_ptr() == want.data_ptr() and slot.shape == want.shape
-        W.mark_written(slot, flat)
-        assert flat.direct_written == {slot.data_ptr()}
-        assert W.grad_slot(ps[2])[2] and not W.grad_slot(ps[0])[2]  # "already written" follows direct_written
-        flat.direct_written.add(flat.grad.data_ptr())
+        flat.mark_written(index)
+        assert index == 2 and flat.written == {2}
+        assert W.grad_slot(ps[2])[2] and not W.grad_slot(ps[0])[2]  # "already written" follows the written set
+        flat.mark_written(0)
         assert W.grad_slot(ps[0])[2]
         flat.gather()
         assert W.grad_slot(ps[0]) is None and W.grad_slot(ps[2]) is None    # after gather()
