@@ -93,6 +93,12 @@ class GlinLayer(ctypes.Structure):
                 ('gw', ctypes.c_void_p), ('gb', ctypes.c_void_p), ('N', ctypes.c_int32), ('group', ctypes.c_int32)]
 
 
+class HgDataItem(ctypes.Structure):
+    """struct hg_data_item (include/hg_data.h); histogan_amd.data lays the same 56 bytes out as a numpy record."""
+    _fields_ = [('src', ctypes.c_uint64), ('dst', ctypes.c_uint64), ('src_stride', ctypes.c_int64), ('dst_stride', ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ('n_out', 'n_keep', 'tab_off', 'in_base', 'in_len', 'flags')]
+
+
 def _signatures():
     """name -> (restype, [argtypes]) of every symbol the headers under include/ declare, grouped by header.  _load applies it
     and EXPORTS is its keys: tests/test_cabi_cpu.py holds it against the prototypes."""
@@ -229,6 +235,11 @@ def _signatures():
         'hg_palette_run': (ci, [vp, i64, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32,
                                 vp, vp, vp, vp, vp, sz, vp]),
         'hg_palette_transfer': (ci, [vp, i64, i64, i64, vp, vp, vp, i32, f32, vp, vp, i32, vp]),
+        # include/hg_data.h
+        'hg_data_max_ksize': (ci, []),
+        'hg_data_item_bytes': (ci, []),
+        'hg_data_resample_axis': (ci, [vp, i32, i32, i64, vp, vp, i32, i32, vp]),
+        'hg_data_finish': (ci, [vp, i32, i32, vp, vp]),
     }
 
 

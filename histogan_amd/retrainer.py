@@ -252,11 +252,13 @@ class recoloringTrainer():
         self.loader = SyntheticData(self.histBlock, self.batch_size, self.image_size, self.device, pool, seed)
         self.loader_evaluate = SyntheticData(self.histBlock, 4, self.image_size, self.device, 1, seed + 977)
 
-    def set_data_src(self, folder, sampling=True):
-        from .data import FolderData
-        self.loader = FolderData(folder, self.histBlock, self.batch_size, self.image_size, self.device,
-                                 transparent=self.transparent, seed=ddp.rank(), hist_sampling=sampling,
-                                 hflip=True)     # transforms.RandomHorizontalFlip(), ReHistoGAN/rehistoGAN.py:362
+    def set_data_src(self, folder, sampling=True, resident=False):
+        """resident=True: as Trainer.set_data_src -- data.ResidentFolderData feeds the loader, RGB only."""
+        from .data import FolderData, ResidentFolderData
+        self.loader = (ResidentFolderData if resident else FolderData)(
+            folder, self.histBlock, self.batch_size, self.image_size, self.device, transparent=self.transparent,
+            seed=ddp.rank(), hist_sampling=sampling,
+            hflip=True)                          # transforms.RandomHorizontalFlip(), ReHistoGAN/rehistoGAN.py:362
         self.loader_evaluate = FolderData(folder, self.histBlock, 4, self.image_size, self.device,
                                           transparent=self.transparent, seed=977 + ddp.rank(),
                                           hist_sampling=sampling)

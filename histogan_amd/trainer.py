@@ -558,11 +558,13 @@ class Trainer():
         self.loader = SyntheticData(self.histBlock, self.batch_size, self.image_size, self.device, pool, seed, ch)
         self.loader_evaluate = SyntheticData(self.histBlock, 4, min(self.image_size, 150), self.device, 1, seed + 977, ch)
 
-    def set_data_src(self, folder):
-        from .data import FolderData
-        self.loader = FolderData(folder, self.histBlock, self.batch_size, self.image_size, self.device,
-                                 transparent=self.transparent, seed=ddp.rank(), aug_prob=self.dataset_aug_prob,
-                                 hist_alpha_weight=self.hist_alpha_weight)
+    def set_data_src(self, folder, resident=False):
+        """resident=True: the training images stay on the device after their first decode (data.ResidentFolderData: the
+        same batches, made by the kernels of include/hg_data.h); RGB only -- a transparent trainer is refused."""
+        from .data import FolderData, ResidentFolderData
+        self.loader = (ResidentFolderData if resident else FolderData)(
+            folder, self.histBlock, self.batch_size, self.image_size, self.device, transparent=self.transparent,
+            seed=ddp.rank(), aug_prob=self.dataset_aug_prob, hist_alpha_weight=self.hist_alpha_weight)
         self.loader_evaluate = FolderData(folder, self.histBlock, 4, self.image_size, self.device,
                                           transparent=self.transparent, seed=977 + ddp.rank(), test=True,
                                           hist_alpha_weight=self.hist_alpha_weight)
