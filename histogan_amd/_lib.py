@@ -103,6 +103,7 @@ def _signatures():
     """name -> (restype, [argtypes]) of every symbol the headers under include/ declare, grouped by header.  _load applies it
     and EXPORTS is its keys: tests/test_cabi_cpu.py holds it against the prototypes."""
     ci, vp, sz, i32, i64, f32 = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    f64 = ctypes.c_double
     P = ctypes.POINTER
     PP, GL = P(HgHistParams), P(GlinLayer)
     return {
@@ -235,6 +236,20 @@ def _signatures():
         'hg_palette_run': (ci, [vp, i64, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32,
                                 vp, vp, vp, vp, vp, sz, vp]),
         'hg_palette_transfer': (ci, [vp, i64, i64, i64, vp, vp, vp, i32, f32, vp, vp, i32, vp]),
+        # include/hg_lut.h
+        'hg_lut_max_n': (ci, []),
+        'hg_lut_max_pixels': (i64, []),
+        'hg_lut_apply_tile': (ci, []),
+        'hg_lut_apply_lds_n': (ci, []),
+        'hg_lut_splat_lds_n': (ci, []),
+        'hg_lut_solve_lds_n': (ci, []),
+        'hg_lut_apply_blocks': (ci, [i64]),
+        'hg_lut_splat_blocks': (ci, [i64]),
+        'hg_lut_workspace_bytes': (sz, [i32]),
+        'hg_lut_apply': (ci, [vp, i32, i64, i64, i64, vp, i32, i32, vp, i32, i32, vp]),
+        'hg_lut_splat': (ci, [vp, i64, i64, vp, i64, i64, vp, i64, i32, vp, i32, vp]),
+        'hg_lut_solve': (ci, [vp, i32, f64, i32, vp, vp, sz, vp]),
+        'hg_lut_fit': (ci, [vp, i64, i64, vp, i64, i64, vp, i64, i32, f64, i32, vp, vp, sz, vp]),
         # include/hg_data.h
         'hg_data_max_ksize': (ci, []),
         'hg_data_item_bytes': (ci, []),

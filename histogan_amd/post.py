@@ -17,7 +17,10 @@ and the number reported for "structure preserved under recolouring"; and the ite
 (color_transfer_idt, idt_rotations), the nonlinear colour transfer that reaches the target distributions -- bimodal, skewed,
 saturated -- an affine map cannot; and palettes (palette, paired_palette, palette_labels, match_palettes, palette_histogram):
 an image described by K colours, and color_transfer_palette, the third transfer, between the two -- every pixel moves by a
-smooth blend of per-cluster shifts, so colour regions move independently and flat regions stay flat.
+smooth blend of per-cluster shifts, so colour regions move independently and flat regions stay flat; and 3D colour LUTs
+(include/hg_lut.h: lut_fit, lut_apply, lut_identity, lut_bake, lut_compose, save_cube, load_cube), the object people who
+grade colour exchange: the recolouring as a function of colour alone, fitted once on the 256x256 pair, applied to a photo, a
+clip or a folder in one memory-bound pass, and written as a .cube file every grading tool reads.
 """
 import ctypes
 from collections import namedtuple
@@ -964,6 +967,262 @@ def palette_histogram(hist_block, pal):
     else:
         img = torch.stack((lab[..., 0] / 100.0, (lab[..., 1] + 128.0) / 255.0, (lab[..., 2] + 128.0) / 255.0), dim=1)
     return hist_block(img.unsqueeze(2).float().contiguous(), weight=wt.unsqueeze(1).float().contiguous())
+
+
+# ---- 3D colour LUTs (hg_lut_*, include/hg_lut.h) --------------------------------------------------------------------------
+LUT_MAX_N = 65
+LUT_MAX_PIXELS = 1 << 22      # pixel pairs of one fit: the bound of the 64-bit integer sums
+LUT_LAMBDA = 0.2              # the defaults of lut_fit, from the fp64 reference on the synthetic pair
+LUT_SWEEPS = 128
+_LUT_INTERPOLATION = {'tetrahedral': 0, 'trilinear': 1}
+
+
+def _lut_size(n, fn):
+    if isinstance(n, bool) or not isinstance(n, int) or not 2 <= n <= LUT_MAX_N:
+        raise ValueError(f'{fn}: n must be an integer in [2, {LUT_MAX_N}], got {n!r}')
+    return n
+
+
+def _lut_interpolation(interpolation, fn):
+    if interpolation not in _LUT_INTERPOLATION:
+        raise ValueError(f"{fn}: interpolation must be 'tetrahedral' or 'trilinear', got {interpolation!r}")
+    return _LUT_INTERPOLATION[interpolation]
+
+
+def _lut_shape(lut, fn, name='lut'):
+    if not torch.is_tensor(lut) or lut.dim() != 4 or lut.shape[3] != 3 or not lut.shape[0] == lut.shape[1] == lut.shape[2]:
+        raise ValueError(f'{fn}: {name} must be an (N, N, N, 3) tensor, got {tuple(lut.shape) if torch.is_tensor(lut) else type(lut).__name__}')
+    if not 2 <= lut.shape[0] <= LUT_MAX_N:
+        raise ValueError(f'{fn}: {name} must have N in [2, {LUT_MAX_N}], got {lut.shape[0]}')
+    return lut.shape[0]
+
+
+def _lut_image_shape(t, fn, name, u8_ok=False):
+    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3 or t.numel() == 0:
+        raise ValueError(f'{fn}: {name} must be an (H, W, 3) image, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}')
+    if not (t.is_floating_point() or (u8_ok and t.dtype == torch.uint8)):
+        raise ValueError(f'{fn}: {name} must be a float image' + (' or uint8' if u8_ok else '') + f', got {t.dtype}')
+
+
+def lut_identity(n=33, device=None):
+    """The LUT that maps every colour to itself: fp32 (n, n, n, 3), indexed [b, g, r, c] (red fastest, the row order of a
+    .cube file), node (ir, ig, ib) holding (ir, ig, ib) / (n - 1).  device: None is the current GPU."""
+    _lut_size(n, 'lut_identity')
+    g = torch.arange(n, dtype=torch.float64, device=torch.device('cuda') if device is None else device) / (n - 1)
+    lut = torch.stack((g.view(1, 1, n).expand(n, n, n), g.view(1, n, 1).expand(n, n, n), g.view(n, 1, 1).expand(n, n, n)), dim=3)
+    return lut.float().contiguous()
+
+
+def lut_apply(image, lut, interpolation='tetrahedral', quantize=False, blocks=0):
+    """A 3D LUT applied to an image (hg_lut_apply): one memory-bound pass, no transcendental per pixel.  image: an (H, W, 3)
+    fp32 device view in [0, 1] (a CHW image's .permute(1, 2, 0) is one; any strides) or a uint8 (H, W, 3) photo read as
+    v / 255; values outside [0, 1] are clamped first and NaN reads as 0.  lut: fp32 (N, N, N, 3), 2 <= N <= 65 (lut_identity,
+    lut_fit, lut_bake, load_cube).  interpolation: 'tetrahedral' (four nodes, the default) or 'trilinear' (eight).  Returns
+    (H, W, 3) fp32 clipped to [0, 1], or uint8 = (uint8)(out*255) when quantize -- truncation, the rule of color_transfer_mkl,
+    _idt and _palette, so an identity LUT on a uint8 photo is not an exact round trip.  blocks: 0 takes the kernel's plan."""
+    fn = 'lut_apply'
+    tri = _lut_interpolation(interpolation, fn)
+    n = _lut_shape(lut, fn)
+    _lut_image_shape(image, fn, 'image', u8_ok=True)
+    need_gpu(image, fn, _FOUND)
+    need_gpu(lut, fn, _FOUND)
+    dev = image.device
+    H, W = image.shape[:2]
+    with on_device(dev):
+        table = lut.detach().float().contiguous()
+        if image.dtype == torch.uint8:
+            src, u8, ps, cs = image.contiguous(), 1, 3, 1
+        else:
+            src, _, ps, cs = _pixels(image.detach(), 'image', fn)
+            u8 = 0
+        out = torch.empty((H, W, 3), dtype=torch.uint8 if quantize else torch.float32, device=dev)
+        check(lib.hg_lut_apply(src.data_ptr(), u8, H * W, ps, cs, table.data_ptr(), n, tri, out.data_ptr(), int(quantize), blocks,
+                               raw_stream(dev)), 'hg_lut_apply')
+    return out
+
+
+def _lut_solver_args(lambda_smooth, iterations, fn):
+    lam = LUT_LAMBDA if lambda_smooth is None else lambda_smooth
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0 <= float(lam) < float('inf'):
+        raise ValueError(f'{fn}: lambda_smooth must be a non-negative finite number or None, got {lambda_smooth!r}')
+    sweeps = LUT_SWEEPS if iterations is None else iterations
+    if isinstance(sweeps, bool) or not isinstance(sweeps, int) or sweeps < 0:
+        raise ValueError(f'{fn}: iterations must be a non-negative integer or None, got {iterations!r}')
+    return float(lam), sweeps
+
+
+def _lut_pair(source, target, weight, fn):
+    _lut_image_shape(source, fn, 'source')
+    _lut_image_shape(target, fn, 'target')
+    if source.shape != target.shape:
+        raise ValueError(f'{fn}: source and target must have one size, got {tuple(source.shape)} and {tuple(target.shape)}')
+    if weight is not None and (not torch.is_tensor(weight) or tuple(weight.shape) != tuple(source.shape[:2])):
+        raise ValueError(f'{fn}: weight must be an (H, W) map of the images\' size {tuple(source.shape[:2])}, got '
+                         f'{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}')
+    if source.shape[0] * source.shape[1] > LUT_MAX_PIXELS:
+        raise ValueError(f'{fn}: at most 2^22 pixel pairs per fit (the bound of the integer sums), got {source.shape[0] * source.shape[1]}')
+    for t in (source, target) + (() if weight is None else (weight,)):
+        need_gpu(t, fn, _FOUND)
+    s, npix, sps, scs = _pixels(source.detach(), 'source', fn)
+    t, _, tps, tcs = _pixels(target.detach(), 'target', fn)
+    w = None if weight is None else weight.detach().float().contiguous()
+    return (s, sps, scs), (t, tps, tcs), w, npix
+
+
+def lut_splat(source, target, n=33, weight=None, sums=None, blocks=0):
+    """The integer normal sums of a fit (hg_lut_splat): int64 (n, n, n, 4) = (A, B_r, B_g, B_b) per lattice node, every pixel of
+    the pair splatted trilinearly onto the 8 corners of its cell.  They are integers, so they do not depend on the order of
+    the sums and add up over image pairs: pass the `sums` of earlier pairs to fit one LUT to several (2^22 pixels in all)."""
+    fn = 'lut_splat'
+    _lut_size(n, fn)
+    if sums is not None and (not torch.is_tensor(sums) or sums.dtype != torch.int64 or tuple(sums.shape) != (n, n, n, 4)
+                             or not sums.is_contiguous()):
+        raise ValueError(f'{fn}: sums must be a contiguous int64 ({n}, {n}, {n}, 4) tensor')
+    (s, sps, scs), (t, tps, tcs), w, npix = _lut_pair(source, target, weight, fn)
+    dev = s.device
+    with on_device(dev):
+        if sums is None:
+            sums = torch.zeros((n, n, n, 4), dtype=torch.int64, device=dev)
+        need_gpu(sums, fn, _FOUND)
+        check(lib.hg_lut_splat(s.data_ptr(), sps, scs, t.data_ptr(), tps, tcs, ptr(w), npix, n, sums.data_ptr(), blocks,
+                               raw_stream(dev)), 'hg_lut_splat')
+    return sums
+
+
+def lut_solve(sums, lambda_smooth=None, iterations=None):
+    """The LUT of the sums of lut_splat (hg_lut_solve): per channel (diag(a) + lambda L) d = b on the lattice -- a, b the sums
+    scaled to mean(a) = 1, L the 6-neighbour Laplacian -- by `iterations` red-black Gauss-Seidel sweeps in fp64 from d = 0, and
+    LUT = identity + d.  Where data is, the data wins; elsewhere d is the harmonic continuation of its surroundings; without
+    any data the result is the identity.  None takes LUT_LAMBDA and LUT_SWEEPS."""
+    fn = 'lut_solve'
+    lam, sweeps = _lut_solver_args(lambda_smooth, iterations, fn)
+    if not torch.is_tensor(sums) or sums.dtype != torch.int64 or sums.dim() != 4 or sums.shape[3] != 4 or \
+            not sums.shape[0] == sums.shape[1] == sums.shape[2] or not 2 <= sums.shape[0] <= LUT_MAX_N:
+        raise ValueError(f'{fn}: sums must be an int64 (N, N, N, 4) tensor with N in [2, {LUT_MAX_N}]')
+    need_gpu(sums, fn, _FOUND)
+    n, dev = sums.shape[0], sums.device
+    with on_device(dev):
+        sums = sums.contiguous()
+        nb = lib.hg_lut_workspace_bytes(n)
+        ws = workspace(nb, dev)
+        lut = torch.empty((n, n, n, 3), dtype=torch.float32, device=dev)
+        check(lib.hg_lut_solve(sums.data_ptr(), n, lam, sweeps, lut.data_ptr(), ws.data_ptr(), nb, raw_stream(dev)), 'hg_lut_solve')
+    return lut
+
+
+def lut_fit(source, target, n=33, weight=None, lambda_smooth=None, iterations=None):
+    """Fit a 3D LUT to a pixel-paired image pair (hg_lut_fit): the general smooth pointwise colour map source -> target, next
+    to color_transfer_mkl's single affine map.  source, target: (H, W, 3) fp32 device views of one size (the 256x256 input
+    and the unclamped network output: targets in [-1, 2] are representable); weight: optional (H, W) map in [0, 1].  At most 2^22
+    pixels.  lambda_smooth trades fidelity at the colours the pair has for smoothness (it does not depend on n or the image
+    size); iterations is the number of Gauss-Seidel sweeps; None takes LUT_LAMBDA and LUT_SWEEPS.  Splat and solve run on the
+    caller's stream with no read-back.  Returns the LUT, fp32 (n, n, n, 3); lut_fit(s, s) is the identity."""
+    fn = 'lut_fit'
+    _lut_size(n, fn)
+    lam, sweeps = _lut_solver_args(lambda_smooth, iterations, fn)
+    (s, sps, scs), (t, tps, tcs), w, npix = _lut_pair(source, target, weight, fn)
+    dev = s.device
+    with on_device(dev):
+        nb = lib.hg_lut_workspace_bytes(n)
+        ws = workspace(nb, dev)
+        lut = torch.empty((n, n, n, 3), dtype=torch.float32, device=dev)
+        check(lib.hg_lut_fit(s.data_ptr(), sps, scs, t.data_ptr(), tps, tcs, ptr(w), npix, n, lam, sweeps, lut.data_ptr(),
+                             ws.data_ptr(), nb, raw_stream(dev)), 'hg_lut_fit')
+    return lut
+
+
+def lut_bake(fn, n=33, device=None):
+    """Bake a pointwise colour map into a LUT: `fn` maps an (H, W, 3) fp32 image in [0, 1] to one and is evaluated on the
+    lattice viewed as an (n*n, n, 3) image.  A tuple result keeps its first element, so
+    `lambda x: color_transfer_palette(x, ps, pd)` and an MKL map bake directly.  color_transfer_idt cannot be baked: it keeps
+    no map that could be replayed on a lattice."""
+    _lut_size(n, 'lut_bake')
+    if not callable(fn):
+        raise ValueError(f'lut_bake: fn must be callable, got {type(fn).__name__}')
+    out = fn(lut_identity(n, device).view(n * n, n, 3))
+    out = out[0] if isinstance(out, tuple) else out
+    if not torch.is_tensor(out) or tuple(out.shape) != (n * n, n, 3) or not out.is_floating_point():
+        raise ValueError(f'lut_bake: fn must return a float ({n * n}, {n}, 3) image, got '
+                         f'{(out.dtype, tuple(out.shape)) if torch.is_tensor(out) else type(out).__name__}')
+    return out.detach().float().reshape(n, n, n, 3).contiguous()
+
+
+def lut_compose(first, second, interpolation='tetrahedral'):
+    """The LUT of `first` followed by `second`: `second` applied to the entries of `first` (which are clamped to [0, 1], the
+    domain of `second`, as lut_apply clamps its input; the result is clipped to [0, 1] like every lut_apply)."""
+    fn = 'lut_compose'
+    _lut_interpolation(interpolation, fn)
+    n = _lut_shape(first, fn, 'first')
+    _lut_shape(second, fn, 'second')
+    need_gpu(first, fn, _FOUND)
+    need_gpu(second, fn, _FOUND)
+    return lut_apply(first.detach().float().contiguous().view(n * n, n, 3), second, interpolation).view(n, n, n, 3)
+
+
+def save_cube(lut, path, title=None):
+    """Write a LUT as a plain .cube file: optional TITLE, LUT_3D_SIZE N, DOMAIN_MIN 0 0 0, DOMAIN_MAX 1 1 1 and N^3 rows
+    `r g b`, red fastest, with 9 significant digits -- load_cube(save_cube(l)) equals l bit for bit."""
+    n = _lut_shape(lut, 'save_cube')
+    if title is not None and (not isinstance(title, str) or '"' in title or '\n' in title or '\r' in title):
+        raise ValueError(f'save_cube: title must be a string without quotes or line breaks, got {title!r}')
+    rows = lut.detach().float().cpu().numpy().reshape(-1, 3)
+    if not np.isfinite(rows).all():
+        raise ValueError('save_cube: the LUT has non-finite entries')
+    with open(path, 'w') as f:
+        if title is not None:
+            f.write(f'TITLE "{title}"\n')
+        f.write(f'LUT_3D_SIZE {n}\nDOMAIN_MIN 0 0 0\nDOMAIN_MAX 1 1 1\n')
+        f.write(''.join('%.9g %.9g %.9g\n' % (r[0], r[1], r[2]) for r in rows))
+    return path
+
+
+def load_cube(path, device=None):
+    """Read a .cube file written by save_cube or by a grading tool: fp32 (N, N, N, 3), on `device` (None: the host).  `#`
+    comments, blank lines and TITLE are skipped.  ValueError for a 1D LUT (LUT_1D_SIZE), a domain other than [0, 1], an N
+    outside 2..65, an unknown keyword, a malformed row or a row count other than N^3."""
+    n, rows, lo, hi = None, [], (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
+
+    def triple(parts, what):
+        try:
+            vals = tuple(float(p) for p in parts)
+        except ValueError:
+            vals = ()
+        if len(vals) != 3 or len(parts) != 3:
+            raise ValueError(f'load_cube: {path}: {what} needs three numbers, got {" ".join(parts)!r}')
+        return vals
+
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if not line or line.startswith('#'):
+                continue
+            key, rest = line.split()[0], line.split()[1:]
+            if key == 'TITLE':
+                continue
+            if key == 'LUT_1D_SIZE':
+                raise ValueError(f'load_cube: {path}: 1D LUTs (LUT_1D_SIZE) are not supported')
+            if key == 'LUT_3D_SIZE':
+                if n is not None or len(rest) != 1 or not rest[0].isdigit():
+                    raise ValueError(f'load_cube: {path}: malformed or repeated LUT_3D_SIZE line {line!r}')
+                n = int(rest[0])
+                if not 2 <= n <= LUT_MAX_N:
+                    raise ValueError(f'load_cube: {path}: LUT_3D_SIZE must lie in [2, {LUT_MAX_N}], got {n}')
+            elif key == 'DOMAIN_MIN':
+                lo = triple(rest, 'DOMAIN_MIN')
+            elif key == 'DOMAIN_MAX':
+                hi = triple(rest, 'DOMAIN_MAX')
+            elif key[0].isalpha() or key[0] == '_':
+                raise ValueError(f'load_cube: {path}: unknown keyword {key!r}')
+            else:
+                rows.append(triple(line.split(), 'a table row'))
+    if n is None:
+        raise ValueError(f'load_cube: {path}: no LUT_3D_SIZE line')
+    if lo != (0.0, 0.0, 0.0) or hi != (1.0, 1.0, 1.0):
+        raise ValueError(f'load_cube: {path}: only the domain [0, 1] is supported, got DOMAIN_MIN {lo} DOMAIN_MAX {hi}')
+    if len(rows) != n ** 3:
+        raise ValueError(f'load_cube: {path}: {len(rows)} rows for LUT_3D_SIZE {n} (expected {n ** 3})')
+    lut = torch.from_numpy(np.asarray(rows, dtype=np.float64).astype(np.float32).reshape(n, n, n, 3))
+    return lut if device is None else lut.to(device)
 
 
 # ---- bilateral guided upsampling (upsampling/BGU.m, bguFit.m, bguSlice.m) -----------------------------------------------

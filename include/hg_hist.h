@@ -37,6 +37,9 @@ extern "C" {
 /* the refusals of the palette (hg_palette_*, hg_post.h) */
 #define HG_EPALETTE_K (-25)      /* palette: K outside [1, hg_palette_max_k()]           */
 #define HG_EPALETTE_PIXELS (-26)  /* palette: a pixel count outside [1, 2^28 - 1]         */
+/* the refusals of the 3D LUTs (hg_lut_*, hg_lut.h) */
+#define HG_ELUT_SIZE (-27)        /* LUT: N outside [2, hg_lut_max_n()]                   */
+#define HG_ELUT_PIXELS (-28)      /* LUT fit: more than hg_lut_max_pixels() pixel pairs   */
 
 /* soft-bin kernel, RGBuvHistBlock.py:124-140 */
 #define HG_METHOD_THRESHOLDING 0
