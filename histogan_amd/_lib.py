@@ -250,6 +250,19 @@ def _signatures():
         'hg_lut_splat': (ci, [vp, i64, i64, vp, i64, i64, vp, i64, i32, vp, i32, vp]),
         'hg_lut_solve': (ci, [vp, i32, f64, i32, vp, vp, sz, vp]),
         'hg_lut_fit': (ci, [vp, i64, i64, vp, i64, i64, vp, i64, i32, f64, i32, vp, vp, sz, vp]),
+        # include/hg_regrain.h
+        'hg_regrain_tile_h': (ci, []),
+        'hg_regrain_tile_w': (ci, []),
+        'hg_regrain_max_fused': (ci, []),
+        'hg_regrain_plan_fused': (ci, [i32, i32, i32]),
+        'hg_regrain_sweep_launches': (ci, [i32, i32]),
+        'hg_regrain_levels': (ci, [i32, i32, i32, i32]),
+        'hg_regrain_check': (ci, [i32, i32, i32, f64, i32]),
+        'hg_regrain_workspace_bytes': (sz, [i32, i32, i32]),
+        'hg_regrain_begin': (ci, [vp, i64, i64, vp, i64, i64, i32, i32, vp, vp, vp]),
+        'hg_regrain_coef': (ci, [vp, i32, i32, i32, f64, vp, vp, vp]),
+        'hg_regrain_sweep': (ci, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        'hg_regrain_finish': (ci, [vp, vp, i32, i32, vp, i32, vp]),
         # include/hg_data.h
         'hg_data_max_ksize': (ci, []),
         'hg_data_item_bytes': (ci, []),

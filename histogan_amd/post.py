@@ -20,7 +20,10 @@ an image described by K colours, and color_transfer_palette, the third transfer,
 smooth blend of per-cluster shifts, so colour regions move independently and flat regions stay flat; and 3D colour LUTs
 (include/hg_lut.h: lut_fit, lut_apply, lut_identity, lut_bake, lut_compose, save_cube, load_cube), the object people who
 grade colour exchange: the recolouring as a function of colour alone, fitted once on the 256x256 pair, applied to a photo, a
-clip or a folder in one memory-bound pass, and written as a .cube file every grading tool reads.
+clip or a folder in one memory-bound pass, and written as a .cube file every grading tool reads; and regrain
+(include/hg_regrain.h: regrain, regrain_levels), the second half of the method color_transfer_idt comes from: the colours of a
+transferred picture on the gradient field of the original photo, a multi-level damped Jacobi solve at the photo's full size
+that removes the grain a distribution transfer leaves on flat regions.
 """
 import ctypes
 from collections import namedtuple
@@ -1223,6 +1226,153 @@ def load_cube(path, device=None):
         raise ValueError(f'load_cube: {path}: {len(rows)} rows for LUT_3D_SIZE {n} (expected {n ** 3})')
     lut = torch.from_numpy(np.asarray(rows, dtype=np.float64).astype(np.float32).reshape(n, n, n, 3))
     return lut if device is None else lut.to(device)
+
+
+# ---- regrain (hg_regrain_*, include/hg_regrain.h) ---------------------------------------------------------------------------
+REGRAIN_RHO = 0.2                 # the damping of the Jacobi sweep (fp32 in the kernels)
+REGRAIN_MIN_SIDE = 20             # a coarser level exists while both of its sides exceed this
+REGRAIN_ITERATIONS = (4, 16, 32, 64, 64, 64)
+REGRAIN_MAX_FUSED = 8             # hg_regrain_max_fused()
+REGRAIN_MAX_PIXELS = 1 << 28
+
+
+def _regrain_args(iterations, smoothness, min_side, fn):
+    """(iterations as a tuple of ints, smoothness as a float, min_side as an int), or ValueError (no HIP call is made)."""
+    try:
+        its = tuple(iterations)
+    except TypeError:
+        its = None
+    if not its or any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1 for n in its):
+        raise ValueError(f'{fn}: iterations must be a non-empty sequence of positive integers, got {iterations!r}')
+    ok = not isinstance(smoothness, bool) and isinstance(smoothness, (int, float, np.floating))
+    if ok:
+        with np.errstate(over='ignore', under='ignore'):
+            ok = 0 < float(np.float32(smoothness)) < float('inf')          # the kernels take it as fp32
+    if not ok:
+        raise ValueError(f'{fn}: smoothness must be positive and finite, got {smoothness!r}')
+    if isinstance(min_side, bool) or not isinstance(min_side, (int, np.integer)) or min_side < 1:
+        raise ValueError(f'{fn}: min_side must be an integer of at least 1, got {min_side!r}')
+    return tuple(int(n) for n in its), float(smoothness), int(min_side)
+
+
+def regrain_levels(h, w, iterations=REGRAIN_ITERATIONS, min_side=REGRAIN_MIN_SIDE):
+    """The level sizes [(h, w), (ceil(h / 2), ceil(w / 2)), ...] of regrain (include/hg_regrain.h, Levels): level l + 1 exists
+    while `iterations` has an entry for it and both of its sides exceed min_side.  len() of it is hg_regrain_levels."""
+    its, _, min_side = _regrain_args(iterations, 1.0, min_side, 'regrain_levels')
+    if isinstance(h, bool) or isinstance(w, bool) or int(h) != h or int(w) != w or h < 2 or w < 2 or h * w > REGRAIN_MAX_PIXELS:
+        raise ValueError(f'regrain_levels: an image of at least 2 x 2 and at most 2^28 pixels is needed, got {h} x {w}')
+    sizes = [(int(h), int(w))]
+    while len(sizes) < len(its):
+        h2, w2 = (sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2
+        if h2 <= min_side or w2 <= min_side:
+            break
+        sizes.append((h2, w2))
+    return sizes
+
+
+def _resize_planes_into(src, dst, method='bilinear'):
+    """imresize(src, dst.shape[1:], method=method) written into `dst`: fp32 planes (C, H, W) -> contiguous fp32 (C, H', W') in
+    the caller's memory; the same kernel, tables and axis order, so the same bits."""
+    C, H, W = src.shape
+    (Ho, Wo), scale = resize_plan((H, W), dst.shape[1:])
+    order = [0, 1] if scale[0] <= scale[1] else [1, 0]
+    cur = [H, W]
+    cur_t, cur_s = src, tuple(src.stride())
+    for step, axis in enumerate(order):
+        ih, iw = cur
+        cur[axis] = (Ho, Wo)[axis]
+        h, w = cur
+        out = dst if step == 1 else torch.empty((C, h, w), dtype=torch.float32, device=src.device)
+        _resize_axis(cur_t, False, cur_s, C, ih, iw, axis, out, False, (h * w, w, 1), cur[axis], scale[axis], method, False)
+        cur_t, cur_s = out, (h * w, w, 1)
+    return dst
+
+
+def _regrain_carve(ws, sizes):
+    """The workspace of hg_regrain_workspace_bytes as per-level views: I (3), E (3), a (3), b (3), coef (4), scratch (1), each
+    rounded up to 4 floats, level 0 first."""
+    levels, off = [], 0
+    for h, w in sizes:
+        lv = {}
+        for name, c in (('I', 3), ('E', 3), ('a', 3), ('b', 3), ('coef', 4), ('scratch', 1)):
+            lv[name] = ws[off:off + c * h * w].view(c, h, w)
+            off += (c * h * w + 3) // 4 * 4
+        levels.append(lv)
+    assert off == ws.numel()
+    return levels
+
+
+def _regrain_image(t, fn, name):
+    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3 or not t.is_floating_point():
+        raise ValueError(f'{fn}: {name} must be a float (H, W, 3) image, got '
+                         f'{str(t.dtype) + " " + str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}')
+
+
+def regrain_sweep(a, b, E, coef, n, fused=0):
+    """hg_regrain_sweep on one level: n damped Jacobi sweeps from the (3, H, W) planes `a`, ping-ponging with `b`; E (3, H, W)
+    and coef (4, H, W) as hg_regrain_coef wrote it.  Returns the one of a, b that holds the result."""
+    _, H, W = a.shape
+    with on_device(a.device):
+        check(lib.hg_regrain_sweep(a.data_ptr(), b.data_ptr(), E.data_ptr(), coef.data_ptr(), H, W, n, fused, raw_stream(a.device)),
+              'hg_regrain_sweep')
+    k = fused if fused else lib.hg_regrain_plan_fused(H, W, n)
+    return b if lib.hg_regrain_sweep_launches(n, k) % 2 else a
+
+
+def regrain(original, transferred, iterations=REGRAIN_ITERATIONS, smoothness=1.0, min_side=REGRAIN_MIN_SIDE, quantize=False,
+            fused=0):
+    """Regrain (Pitie, Kokaram, Dahyot 2007), the step that follows a distribution transfer: the colours of `transferred` on
+    the gradient field of `original`, which takes out the grain and the stretched compression blocks color_transfer_idt
+    leaves on flat regions.  original, transferred: (H, W, 3) float device views of one size, H, W >= 2 (a CHW image's
+    .permute(1, 2, 0) is one; any strides).  The solver works on the offset D = result - original (include/hg_regrain.h holds
+    the definition): per level of a pyramid that halves down to min_side, iterations[l] damped Jacobi sweeps pull D towards
+    transferred - original where `original` has structure and smooth it where `original` is flat -- by `smoothness`, larger is
+    smoother -- and the coarser level's result starts the finer one.  regrain(x, x) is x bit for bit.  Returns (H, W, 3) fp32
+    clipped to [0, 1], or uint8 = (uint8)(out*255) when quantize, as the transfers.  fused: sweeps per launch of the tiled
+    kernel, 1 = one sweep per launch, 0 = the measured plan (hg_regrain_plan_fused); every setting gives the same bits.
+    Everything is enqueued on the current stream without a host read-back; two calls give the same bits."""
+    fn = 'regrain'
+    its, smoothness, min_side = _regrain_args(iterations, smoothness, min_side, fn)
+    _regrain_image(original, fn, 'original')
+    _regrain_image(transferred, fn, 'transferred')
+    if original.shape != transferred.shape:
+        raise ValueError(f'{fn}: original and transferred must have one size, got {tuple(original.shape)} and '
+                         f'{tuple(transferred.shape)}')
+    if original.device != transferred.device:
+        raise ValueError(f'{fn}: original and transferred must be on one device, got {original.device} and {transferred.device}')
+    H, W = original.shape[:2]
+    if H < 2 or W < 2 or H * W > REGRAIN_MAX_PIXELS:
+        raise ValueError(f'{fn}: an image of at least 2 x 2 and at most 2^28 pixels is needed, got {H} x {W}')
+    if isinstance(fused, bool) or not isinstance(fused, int) or not 0 <= fused <= REGRAIN_MAX_FUSED:
+        raise ValueError(f'{fn}: fused must be an integer in [0, {REGRAIN_MAX_FUSED}], got {fused!r}')
+    src, _, ps0, cs0 = _pixels(original.detach(), 'original', fn)
+    tgt, _, ps1, cs1 = _pixels(transferred.detach(), 'transferred', fn)
+    dev = src.device
+    sizes = regrain_levels(H, W, its, min_side)
+    out = torch.empty((H, W, 3), dtype=torch.uint8 if quantize else torch.float32, device=dev)
+    with on_device(dev):
+        st = raw_stream(dev)
+        nb = lib.hg_regrain_workspace_bytes(H, W, len(sizes))
+        lv = _regrain_carve(torch.empty(nb // 4, dtype=torch.float32, device=dev), sizes)
+        check(lib.hg_regrain_begin(src.data_ptr(), ps0, cs0, tgt.data_ptr(), ps1, cs1, H, W, lv[0]['I'].data_ptr(),
+                                   lv[0]['E'].data_ptr(), st), 'hg_regrain_begin')
+        for l in range(1, len(sizes)):
+            _resize_planes_into(lv[l - 1]['I'], lv[l]['I'])
+            _resize_planes_into(lv[l - 1]['E'], lv[l]['E'])
+        d = None
+        for l in range(len(sizes) - 1, -1, -1):
+            v = lv[l]
+            h, w = sizes[l]
+            check(lib.hg_regrain_coef(v['I'].data_ptr(), h, w, l, smoothness, v['coef'].data_ptr(), v['scratch'].data_ptr(), st),
+                  'hg_regrain_coef')
+            if d is None:
+                v['a'].copy_(v['E'])
+            else:
+                _resize_planes_into(d, v['a'])
+            d = regrain_sweep(v['a'], v['b'], v['E'], v['coef'], its[l], fused)
+        check(lib.hg_regrain_finish(lv[0]['I'].data_ptr(), d.data_ptr(), H, W, out.data_ptr(), int(quantize), st),
+              'hg_regrain_finish')
+    return out
 
 
 # ---- bilateral guided upsampling (upsampling/BGU.m, bguFit.m, bguSlice.m) -----------------------------------------------

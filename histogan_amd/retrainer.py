@@ -424,17 +424,19 @@ class recoloringTrainer():
         post.color_transfer_palette moves every pixel of the photo by a smooth blend of the per-cluster shifts), and
         `post_recoloring='lut'` with a 3D colour LUT (post.lut_fit of the 256x256 input and the network output at n = 33,
         post.lut_apply on the photo: the general smooth pointwise colour map, and the cheapest of the four to apply; a caller
-        who wants the .cube file calls post.save_cube on their own post.lut_fit); any other
+        who wants the .cube file calls post.save_cube on their own post.lut_fit), and `post_recoloring='idt_regrain'` with
+        the distribution transfer followed by its regrain step (post.regrain(photo, post.color_transfer_idt(photo, output)):
+        the colours of 'idt' on the gradient field of the photo, without the grain 'idt' leaves on flat regions); any other
         string raises ValueError, and True keeps meaning the Monge-Kantorovich map.
         `resizing_method='BGU_native'` carries the result back with bilateral guided upsampling instead (post.bgu_upsampling: the arithmetic of the reference's upsampling/BGU.m on the network's
         8-bit output, without the JPEG round trip) and writes it at exactly the photo's size.
         `resizing_method='BGU'`, which in the reference runs an external Windows executable, raises
         NotImplementedError."""
         upscale = resizing == 'upscaling'
-        if isinstance(post_recoloring, str) and post_recoloring not in ('idt', 'palette', 'lut'):
+        if isinstance(post_recoloring, str) and post_recoloring not in ('idt', 'palette', 'lut', 'idt_regrain'):
             raise ValueError(f"recoloringTrainer.evaluate: post_recoloring={post_recoloring!r} (True: the Monge-Kantorovich "
                              "linear transfer; 'idt': the iterative distribution transfer; 'palette': the palette transfer; "
-                             "'lut': a fitted 3D colour LUT)")
+                             "'lut': a fitted 3D colour LUT; 'idt_regrain': 'idt' followed by regrain)")
         recolor = post_recoloring if isinstance(post_recoloring, str) else post_recoloring is True
         if upscale and resizing_method not in ('pyramid', 'BGU_native'):
             raise NotImplementedError(f"recoloringTrainer.evaluate: resizing_method={resizing_method!r} for 'upscaling' "
@@ -503,6 +505,9 @@ class recoloringTrainer():
             elif recolor == 'lut':
                 lut = post.lut_fit(image_batch[0].permute(1, 2, 0), generated_images[0].permute(1, 2, 0), n=33)
                 out = post.lut_apply(src, lut, quantize=True)
+            elif recolor == 'idt_regrain':
+                moved, _ = post.color_transfer_idt(src, generated_images[0].permute(1, 2, 0))
+                out = post.regrain(src, moved, quantize=True)
             else:
                 transfer = post.color_transfer_idt if recolor == 'idt' else post.color_transfer_mkl
                 out, _ = transfer(src, generated_images[0].permute(1, 2, 0), quantize=True)

@@ -40,6 +40,11 @@ extern "C" {
 /* the refusals of the 3D LUTs (hg_lut_*, hg_lut.h) */
 #define HG_ELUT_SIZE (-27)        /* LUT: N outside [2, hg_lut_max_n()]                   */
 #define HG_ELUT_PIXELS (-28)      /* LUT fit: more than hg_lut_max_pixels() pixel pairs   */
+/* the refusals of regrain (hg_regrain_*, hg_regrain.h) */
+#define HG_EREGRAIN_SIZE (-29)        /* regrain: H or W below 2, or more than 2^28 pixels */
+#define HG_EREGRAIN_ITERATIONS (-30)  /* regrain: no level, or a level with fewer than 1 sweep */
+#define HG_EREGRAIN_SMOOTHNESS (-31)  /* regrain: smoothness not positive and finite        */
+#define HG_EREGRAIN_MIN_SIDE (-32)    /* regrain: min_side below 1                          */
 
 /* soft-bin kernel, RGBuvHistBlock.py:124-140 */
 #define HG_METHOD_THRESHOLDING 0
