@@ -250,6 +250,12 @@ def _signatures():
         'hg_lut_splat': (ci, [vp, i64, i64, vp, i64, i64, vp, i64, i32, vp, i32, vp]),
         'hg_lut_solve': (ci, [vp, i32, f64, i32, vp, vp, sz, vp]),
         'hg_lut_fit': (ci, [vp, i64, i64, vp, i64, i64, vp, i64, i32, f64, i32, vp, vp, sz, vp]),
+        'hg_lut_grad_lds_n': (ci, []),
+        'hg_lut_grad_max_pixels': (i64, []),
+        'hg_lut_grad_blocks': (ci, [i64]),
+        'hg_lut_grad_workspace_bytes': (sz, [i32]),
+        'hg_lut_apply_bwd': (ci, [vp, i32, i64, i64, i64, vp, i32, i32, vp, vp, vp, vp, sz, i32, vp]),
+        'hg_lut_adam_step': (ci, [vp, vp, vp, vp, vp, i32, f64, f64, f64, f64, f64, i32, vp]),
         # include/hg_regrain.h
         'hg_regrain_tile_h': (ci, []),
         'hg_regrain_tile_w': (ci, []),

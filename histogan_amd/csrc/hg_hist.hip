@@ -30,12 +30,13 @@
 #include "hg_lab.h"
 #include <cstdlib>
 
-#define HG_VERSION_NUM 117  // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
+#define HG_VERSION_NUM 118  // 102: hg_hist_params.struct_size (ABI guard), hg_rgbuv_hist_uses_proj_cache; 103: hg_hist_params.weight;
                              // 104: hg_bgu_normal, hg_bgu_slice (hg_post.h); 105: hg_rgbuv_hist_bwd_w (gradient of the weight map);
                              // 106: hg_rgbuv_hist_route; 107: HG_PROJ_LAB, hg_srgb_to_lab, hg_lab_to_srgb (hg_post.h); 108: hg_conv2d_route (hg_conv.h);
                              // 109: hg_noise_grad (hg_nets.h); 110: hg_delta_e (hg_post.h); 111: hg_ssim_fwd, hg_ssim_bwd (hg_post.h);
                              // 112: hg_wino_route, hg_wino_wgrad_route (hg_wino.h); 113: hg_idt_* (hg_post.h); 114: hg_palette_* (hg_post.h);
-                             // 115: hg_data_* (hg_data.h); 116: hg_lut_* (hg_lut.h); 117: hg_regrain_* (hg_regrain.h)
+                             // 115: hg_data_* (hg_data.h); 116: hg_lut_* (hg_lut.h); 117: hg_regrain_* (hg_regrain.h);
+                             // 118: hg_lut_apply_bwd, hg_lut_adam_step, hg_lut_grad_* (hg_lut.h)
 
 // Settled schedule constants of the dense kernels (DESIGN.md sections 4 and 11 hold the measurements).
 constexpr int kFwdMfmaGroup = 12;    // k_hist_fwd at configs[1]: groups of 1: 505 us, 3: 498, 6: 473, 12: 465
@@ -2441,7 +2442,7 @@ const char *hg_error_string(int code) {
     case HG_EPALETTE_K: return "palette: K must lie in [1, 16] (hg_palette_max_k)";
     case HG_EPALETTE_PIXELS: return "palette: pixel count outside [1, 2^28 - 1], the limit of the 64-bit integer sums";
     case HG_ELUT_SIZE: return "3D LUT: N must lie in [2, 65] (hg_lut_max_n)";
-    case HG_ELUT_PIXELS: return "3D LUT fit: more than 2^22 pixel pairs, the limit of the 64-bit integer sums";
+    case HG_ELUT_PIXELS: return "3D LUT: more than 2^22 pixel pairs in a fit (2^26 pixels in the backward), the limit of the 64-bit integer sums";
     case HG_EREGRAIN_SIZE: return "regrain: both sides of the image must be at least 2, and it may hold at most 2^28 pixels";
     case HG_EREGRAIN_ITERATIONS: return "regrain: iterations must name at least one level, every level at least 1 sweep";
     case HG_EREGRAIN_SMOOTHNESS: return "regrain: smoothness must be positive and finite";

@@ -21,6 +21,13 @@ constexpr int LUT_ONE = 1 << FB;
 static_assert(3 * FB + WB + DB + 1 + 22 <= 62, "the 64-bit sums of 2^22 pixels");
 static_assert((size_t)LUT_SPLAT_LDS_N * LUT_SPLAT_LDS_N * LUT_SPLAT_LDS_N * 32 <= 160 * 1024, "the splat's counters");
 static_assert((size_t)LUT_SOLVE_LDS_N * LUT_SOLVE_LDS_N * LUT_SOLVE_LDS_N * 8 + LUT_THREADS * 8 <= 160 * 1024, "the solve's lattice");
+constexpr int LUT_GRAD_LDS_N = 17;                     // 17^3 x 3 x 8 B = 117 912 B
+constexpr int LUT_GRAD_SHARE = 4096, LUT_GRAD_PLAN_BLOCKS = 256, LUT_GRAD_MAX_BLOCKS = 512;
+constexpr int LUT_GRAD_BITS = HG_LUT_GRAD_BITS;        // |contribution| <= 2^36 (1 + 2^-17)
+constexpr long long LUT_GRAD_MAX_PIXELS = 1LL << 26;   // 2^36 2^26 = 2^62
+constexpr size_t LUT_GRAD_HEADER = 16;                 // the workspace: the bits of gmax, then the sums
+static_assert(LUT_GRAD_BITS + 26 <= 62, "the 64-bit sums of 2^26 pixels");
+static_assert((size_t)LUT_GRAD_LDS_N * LUT_GRAD_LDS_N * LUT_GRAD_LDS_N * 24 <= 160 * 1024, "the backward's counters");
 
 enum { LUT_IN_F32 = 0, LUT_IN_F32_PACKED = 1, LUT_IN_U8 = 2 };
 
@@ -284,6 +291,205 @@ __global__ __launch_bounds__(LUT_THREADS) void k_lut_solve(const long long *__re
   }
 }
 
+// ---- the adjoint of the apply -----------------------------------------------------------------------------------------
+// the largest bit pattern of a finite |g|: patterns of non-negative floats order as the floats do
+__global__ __launch_bounds__(LUT_THREADS) void k_lut_grad_range(const float *__restrict__ g, long long n3, unsigned *gmax_bits) {
+  __shared__ unsigned top;
+  if (threadIdx.x == 0) top = 0u;
+  __syncthreads();
+  unsigned mine = 0u;
+  for (long long k = (long long)blockIdx.x * LUT_THREADS + threadIdx.x; k < n3; k += (long long)gridDim.x * LUT_THREADS) {
+    const unsigned b = __float_as_uint(g[k]) & 0x7fffffffu;
+    if (b < 0x7f800000u && b > mine) mine = b;
+  }
+  if (mine) atomicMax(&top, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && top) atomicMax(gmax_bits, top);
+}
+
+// E with gmax < 2^E from the bits of gmax (a subnormal gmax takes E = -126)
+__device__ __forceinline__ int lut_grad_exponent(unsigned bits) { return (int)(bits >> 23) - 126; }
+
+// gx and the integer sums of glut for one contiguous share of the pixels per workgroup.  The forward is recomputed with the
+// sequence of lut_interp, so the masks are those of the value the forward clipped.
+template <bool TRI, bool LDS, bool SUMS>
+__global__ __launch_bounds__(LUT_THREADS) void k_lut_apply_bwd(const float *__restrict__ x, long long ps, long long cs,
+                                                               const float *__restrict__ lut, int N,
+                                                               const float *__restrict__ g, long long n, float *__restrict__ gx,
+                                                               const unsigned *__restrict__ gmax_bits,
+                                                               unsigned long long *__restrict__ sums, long long share) {
+#pragma clang fp contract(off)
+  const int n9 = N * N * N * 3;
+  unsigned long long *cnt = sums;
+  double inv_u = 0.0;
+  bool scatter = false;
+  if constexpr (SUMS) {
+    const unsigned bits = *gmax_bits;
+    scatter = bits != 0u;
+    inv_u = ldexp(1.0, LUT_GRAD_BITS - lut_grad_exponent(bits));
+    if constexpr (LDS) {
+      for (int k = threadIdx.x; k < n9; k += LUT_THREADS) lut_dyn[k] = 0ull;
+      __syncthreads();
+      cnt = lut_dyn;
+    }
+  }
+  const float nm1 = (float)(N - 1);
+  const int sr = 3, sg = 3 * N, sb = 3 * N * N;
+  const long long p0 = (long long)blockIdx.x * share, p1 = p0 + share < n ? p0 + share : n;
+  for (long long p = p0 + threadIdx.x; p < p1; p += LUT_THREADS) {
+    const float *px = x + p * ps;
+    const float xin[3] = {px[0], px[cs], px[2 * cs]};
+    float gm[3];
+    int i[3];
+    float f[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float gc = g[3 * p + c];
+      gm[c] = isfinite(gc) ? gc : 0.f;
+      const float xc = hg_clamp01(xin[c]);
+      i[c] = min((int)(xc * nm1), N - 2);
+      f[c] = fmaf(xc, nm1, -(float)i[c]);
+    }
+    const int k0 = i[2] * sb + i[1] * sg + i[0] * sr;
+    const float *c0 = lut + k0;
+    float s[3] = {0.f, 0.f, 0.f};                          // sum over c of m_c g_c (slope of channel c along the axis)
+    int node[8];
+    double om[8], fd[3];                                   // the weights of the scatter, fp64 from the unrounded fractions
+    if constexpr (SUMS) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) fd[c] = (double)hg_clamp01(xin[c]) * (double)(N - 1) - (double)i[c];      // exact
+    }
+    if constexpr (TRI) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float v000 = c0[c], v100 = c0[sr + c], v010 = c0[sg + c], v110 = c0[sg + sr + c];
+        const float v001 = c0[sb + c], v101 = c0[sb + sr + c], v011 = c0[sb + sg + c], v111 = c0[sb + sg + sr + c];
+        const float e00 = lut_lerp(v000, v100, f[0]), e10 = lut_lerp(v010, v110, f[0]);
+        const float e01 = lut_lerp(v001, v101, f[0]), e11 = lut_lerp(v011, v111, f[0]);
+        const float h0 = lut_lerp(e00, e10, f[1]), h1 = lut_lerp(e01, e11, f[1]);
+        const float val = lut_lerp(h0, h1, f[2]);
+        if (!(val >= 0.f && val <= 1.f)) gm[c] = 0.f;
+        const float dr = lut_lerp(lut_lerp(v100 - v000, v110 - v010, f[1]), lut_lerp(v101 - v001, v111 - v011, f[1]), f[2]);
+        const float dg = lut_lerp(e10 - e00, e11 - e01, f[2]);
+        const float db = h1 - h0;
+        s[0] = fmaf(gm[c], dr, s[0]);
+        s[1] = fmaf(gm[c], dg, s[1]);
+        s[2] = fmaf(gm[c], db, s[2]);
+      }
+      if constexpr (SUMS) {
+        const double wr[2] = {1.0 - fd[0], fd[0]}, wg[2] = {1.0 - fd[1], fd[1]}, wb[2] = {1.0 - fd[2], fd[2]};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int jr = j & 1, jg = (j >> 1) & 1, jb = j >> 2;
+          node[j] = k0 + jr * sr + jg * sg + jb * sb;
+          om[j] = (wr[jr] * wg[jg]) * wb[jb];
+        }
+      }
+    } else {
+      int o1, o2, a1, a2, a3;                              // steps and axes by descending fraction, as lut_interp sorts them
+      float a, b, cc;
+      if (f[0] >= f[1]) {
+        if (f[1] >= f[2]) { o1 = sr; o2 = sg; a1 = 0; a2 = 1; a3 = 2; a = f[0]; b = f[1]; cc = f[2]; }
+        else if (f[0] >= f[2]) { o1 = sr; o2 = sb; a1 = 0; a2 = 2; a3 = 1; a = f[0]; b = f[2]; cc = f[1]; }
+        else { o1 = sb; o2 = sr; a1 = 2; a2 = 0; a3 = 1; a = f[2]; b = f[0]; cc = f[1]; }
+      } else {
+        if (f[2] >= f[1]) { o1 = sb; o2 = sg; a1 = 2; a2 = 1; a3 = 0; a = f[2]; b = f[1]; cc = f[0]; }
+        else if (f[2] >= f[0]) { o1 = sg; o2 = sb; a1 = 1; a2 = 2; a3 = 0; a = f[1]; b = f[2]; cc = f[0]; }
+        else { o1 = sg; o2 = sr; a1 = 1; a2 = 0; a3 = 2; a = f[1]; b = f[0]; cc = f[2]; }
+      }
+      const float *c1 = c0 + o1, *c2 = c1 + o2, *c3 = c0 + (sr + sg + sb);
+      float t1 = 0.f, t2 = 0.f, t3 = 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float v0 = c0[c], v1 = c1[c], v2 = c2[c], v3 = c3[c];
+        const float val = fmaf(cc, v3 - v2, fmaf(b, v2 - v1, fmaf(a, v1 - v0, v0)));
+        if (!(val >= 0.f && val <= 1.f)) gm[c] = 0.f;
+        t1 = fmaf(gm[c], v1 - v0, t1);
+        t2 = fmaf(gm[c], v2 - v1, t2);
+        t3 = fmaf(gm[c], v3 - v2, t3);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) s[c] = a1 == c ? t1 : (a2 == c ? t2 : t3);
+      if constexpr (SUMS) {
+        node[0] = k0; node[1] = k0 + o1; node[2] = k0 + o1 + o2; node[3] = k0 + sr + sg + sb;
+        auto along = [&](int ax) { return ax == 0 ? fd[0] : (ax == 1 ? fd[1] : fd[2]); };
+        const double ad = along(a1), bd = along(a2), cd = along(a3);
+        om[0] = 1.0 - ad; om[1] = ad - bd; om[2] = bd - cd; om[3] = cd;
+      }
+    }
+    if (gx) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) gx[3 * p + c] = xin[c] >= 0.f && xin[c] <= 1.f ? nm1 * s[c] : 0.f;
+    }
+    if constexpr (SUMS) {
+      if (scatter) {
+        double gs[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gs[c] = (double)gm[c] * inv_u;             // exact: a power of two
+#pragma unroll
+        for (int j = 0; j < (TRI ? 8 : 4); ++j) {
+          if (om[j] == 0.0) continue;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const long long q = (long long)rint(om[j] * gs[c]);
+            if (q != 0) atomicAdd(cnt + node[j] + c, (unsigned long long)q);
+          }
+        }
+      }
+    }
+  }
+  if constexpr (SUMS && LDS) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < n9; k += LUT_THREADS) {
+      const unsigned long long v = lut_dyn[k];
+      if (v) atomicAdd(sums + k, v);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_lut_grad_finish(const long long *__restrict__ sums, const unsigned *__restrict__ gmax_bits,
+                                                         int n9, float *__restrict__ glut) {
+  const unsigned bits = *gmax_bits;
+  const double u = ldexp(1.0, lut_grad_exponent(bits) - LUT_GRAD_BITS);
+  for (int k = blockIdx.x * 256 + threadIdx.x; k < n9; k += gridDim.x * 256)
+    glut[k] = bits ? (float)((double)sums[k] * u) : 0.f;
+}
+
+// gradient of the smoothness term and one Adam step, out of place.  Every line is the sequence include/hg_lut.h states.
+__global__ __launch_bounds__(256) void k_lut_adam(const float *__restrict__ lut_in, const float *__restrict__ grad,
+                                                  float *__restrict__ m, float *__restrict__ v, float *__restrict__ lut_out, int N,
+                                                  float lam_coef, float step_size, float rsbc2, float b1, float b2, float eps) {
+#pragma clang fp contract(off)
+  const int n9 = N * N * N * 3, NN = N * N;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < n9; e += gridDim.x * 256) {
+    const int k = e / 3, c = e - 3 * k;
+    const int ir = k % N, ig = (k / N) % N, ib = k / NN;
+    float total = grad[e];
+    if (lam_coef != 0.f) {
+      const float den = (float)(N - 1);
+      auto disp = [&](int kk, int jr, int jg, int jb) {
+        const int ic = c == 0 ? jr : (c == 1 ? jg : jb);
+        return lut_in[3 * kk + c] - (float)((double)ic / (double)den);
+      };
+      const float d = disp(k, ir, ig, ib);
+      float nb = 0.f;
+      int deg = 0;
+      if (ir > 0) { nb += disp(k - 1, ir - 1, ig, ib); ++deg; }
+      if (ir < N - 1) { nb += disp(k + 1, ir + 1, ig, ib); ++deg; }
+      if (ig > 0) { nb += disp(k - N, ir, ig - 1, ib); ++deg; }
+      if (ig < N - 1) { nb += disp(k + N, ir, ig + 1, ib); ++deg; }
+      if (ib > 0) { nb += disp(k - NN, ir, ig, ib - 1); ++deg; }
+      if (ib < N - 1) { nb += disp(k + NN, ir, ig, ib + 1); ++deg; }
+      total = total + lam_coef * ((float)deg * d - nb);
+    }
+    const float mi = b1 * m[e] + (1.f - b1) * total;
+    const float vi = b2 * v[e] + ((1.f - b2) * total) * total;
+    m[e] = mi;
+    v[e] = vi;
+    lut_out[e] = lut_in[e] - (step_size * mi) / (sqrtf(vi) * rsbc2 + eps);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 size_t lut_up16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -340,6 +546,15 @@ int lut_solve(const int64_t *sums, int N, double lambda, int sweeps, float *lut,
 }
 
 bool lut_solver_args_ok(double lambda, int sweeps) { return lambda >= 0.0 && lambda < INFINITY && sweeps >= 0; }
+
+size_t lut_grad_workspace(int N) { return LUT_GRAD_HEADER + lut_up16((size_t)N * N * N * 3 * sizeof(int64_t)); }
+
+int lut_grad_plan(long long n) {
+  const long long b = (n + LUT_GRAD_SHARE - 1) / LUT_GRAD_SHARE;
+  return (int)(b < 1 ? 1 : (b > LUT_GRAD_PLAN_BLOCKS ? LUT_GRAD_PLAN_BLOCKS : b));
+}
+
+bool lut_finite(double v) { return v > -INFINITY && v < INFINITY; }
 
 }  // namespace
 
@@ -412,6 +627,64 @@ int hg_lut_fit(const float *source, int64_t s_pix_stride, int64_t s_chan_stride,
   if (int rc = lut_splat(source, s_pix_stride, s_chan_stride, target, t_pix_stride, t_chan_stride, weight, n, N, sums, 0, st))
     return rc;
   return lut_solve(sums, N, lambda, sweeps, lut, base, st);
+}
+
+int hg_lut_grad_lds_n(void) { return LUT_GRAD_LDS_N; }
+int64_t hg_lut_grad_max_pixels(void) { return LUT_GRAD_MAX_PIXELS; }
+int hg_lut_grad_blocks(int64_t n) { return n < 1 || n > LUT_GRAD_MAX_PIXELS ? 0 : lut_grad_plan(n); }
+size_t hg_lut_grad_workspace_bytes(int32_t N) { return lut_check_n(N) ? 0 : lut_grad_workspace(N); }
+
+int hg_lut_apply_bwd(const void *x, int32_t x_u8, int64_t n, int64_t pix_stride, int64_t chan_stride, const float *lut, int32_t N,
+                     int32_t trilinear, const float *g, float *gx, float *glut, void *workspace, size_t workspace_bytes,
+                     int32_t blocks, void *stream) {
+  if (x_u8 || !lut_pixels_ok(static_cast<const float *>(x), pix_stride, chan_stride) || !lut || !g || (!gx && !glut) || n < 1 ||
+      blocks < 0 || blocks > LUT_GRAD_MAX_BLOCKS || !lut_aligned(lut, 3) || !lut_aligned(g, 3) || !lut_aligned(gx, 3) ||
+      !lut_aligned(glut, 3) || (glut && (!workspace || !lut_aligned(workspace, 15))))
+    return HG_EINVAL;
+  if (int rc = lut_check_n(N)) return rc;
+  if (n > LUT_GRAD_MAX_PIXELS) return HG_ELUT_PIXELS;
+  if (glut && workspace_bytes < lut_grad_workspace(N)) return HG_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int n9 = N * N * N * 3;
+  const int nb = blocks > 0 ? blocks : lut_grad_plan(n);
+  const long long share = (n + nb - 1) / nb;
+  char *base = static_cast<char *>(workspace);
+  unsigned *gmax = reinterpret_cast<unsigned *>(base);
+  unsigned long long *sums = glut ? reinterpret_cast<unsigned long long *>(base + LUT_GRAD_HEADER) : nullptr;
+  if (glut) {
+    const hipError_t e = hipMemsetAsync(base, 0, lut_grad_workspace(N), st);
+    if (e != hipSuccess) return (int)e;
+    const long long n3 = 3 * (long long)n, rb = (n3 + LUT_THREADS - 1) / LUT_THREADS;
+    if (int rc = launch(k_lut_grad_range, dim3((unsigned)(rb > 256 ? 256 : rb)), dim3(LUT_THREADS), 0, st, g, n3, gmax)) return rc;
+  }
+  const bool lds = glut && N <= LUT_GRAD_LDS_N;
+  const size_t lds_bytes = lds ? (size_t)n9 * sizeof(unsigned long long) : 0;
+  const int rc = dispatch([&](auto TRI, auto LDS, auto SUMS) {
+    if constexpr (decltype(LDS)::value && !decltype(SUMS)::value) return (int)HG_EINVAL;      // never taken: the counters serve the sums
+    else
+      return launch(k_lut_apply_bwd<TRI, LDS, SUMS>, dim3(nb), dim3(LUT_THREADS), lds_bytes, st, static_cast<const float *>(x),
+                    pix_stride, chan_stride, lut, N, g, n, gx, gmax, sums, share);
+  }, trilinear != 0, lds, glut != nullptr);
+  if (rc || !glut) return rc;
+  return launch(k_lut_grad_finish, dim3((n9 + 255) / 256 > 256 ? 256 : (n9 + 255) / 256), dim3(256), 0, st,
+                reinterpret_cast<const long long *>(sums), gmax, n9, glut);
+}
+
+int hg_lut_adam_step(const float *lut_in, const float *grad, float *exp_avg, float *exp_avg_sq, float *lut_out, int32_t N,
+                     double lambda, double lr, double beta1, double beta2, double eps, int32_t step, void *stream) {
+  if (!lut_in || !grad || !exp_avg || !exp_avg_sq || !lut_out || lut_in == lut_out || step < 1 || !lut_finite(lr) ||
+      !(lambda >= 0.0 && lut_finite(lambda)) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) ||
+      !(eps >= 0.0 && lut_finite(eps)) || !lut_aligned(lut_in, 3) || !lut_aligned(grad, 3) || !lut_aligned(exp_avg, 3) ||
+      !lut_aligned(exp_avg_sq, 3) || !lut_aligned(lut_out, 3))
+    return HG_EINVAL;
+  if (int rc = lut_check_n(N)) return rc;
+  const double edges = 3.0 * N * N * (N - 1), nm1 = (double)(N - 1);
+  const float lam_coef = (float)(lambda * (2.0 * nm1 * nm1 / edges));
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  const float step_size = (float)(lr / bc1), rsbc2 = (float)(1.0 / sqrt(bc2));
+  const int n9 = N * N * N * 3, nb = (n9 + 255) / 256;
+  return launch(k_lut_adam, dim3(nb > 1024 ? 1024 : nb), dim3(256), 0, (hipStream_t)stream, lut_in, grad, exp_avg, exp_avg_sq,
+                lut_out, N, lam_coef, step_size, rsbc2, (float)beta1, (float)beta2, (float)eps);
 }
 
 }  // extern "C"

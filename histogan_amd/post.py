@@ -20,7 +20,8 @@ an image described by K colours, and color_transfer_palette, the third transfer,
 smooth blend of per-cluster shifts, so colour regions move independently and flat regions stay flat; and 3D colour LUTs
 (include/hg_lut.h: lut_fit, lut_apply, lut_identity, lut_bake, lut_compose, save_cube, load_cube), the object people who
 grade colour exchange: the recolouring as a function of colour alone, fitted once on the 256x256 pair, applied to a photo, a
-clip or a folder in one memory-bound pass, and written as a .cube file every grading tool reads; and regrain
+clip or a folder in one memory-bound pass, and written as a .cube file every grading tool reads -- differentiable on request
+(lut_apply(differentiable=True), lut_smoothness), so that lut_refine can pull a LUT towards a target histogram; and regrain
 (include/hg_regrain.h: regrain, regrain_levels), the second half of the method color_transfer_idt comes from: the colours of a
 transferred picture on the gradient field of the original photo, a multi-level damped Jacobi solve at the photo's full size
 that removes the grain a distribution transfer leaves on flat regions.
@@ -977,6 +978,11 @@ LUT_MAX_N = 65
 LUT_MAX_PIXELS = 1 << 22      # pixel pairs of one fit: the bound of the 64-bit integer sums
 LUT_LAMBDA = 0.2              # the defaults of lut_fit, from the fp64 reference on the synthetic pair
 LUT_SWEEPS = 128
+LUT_GRAD_MAX_PIXELS = 1 << 26  # pixels of one lut_apply backward: the bound of its 64-bit integer sums
+LUT_REFINE_STEPS = 50          # the defaults of lut_refine, from the fp64 reference loop
+LUT_REFINE_LR = 5e-3
+LUT_REFINE_LAMBDA = 0.01
+LUT_ADAM_BETAS, LUT_ADAM_EPS = (0.9, 0.999), 1e-8
 _LUT_INTERPOLATION = {'tetrahedral': 0, 'trilinear': 1}
 
 
@@ -1016,19 +1022,93 @@ def lut_identity(n=33, device=None):
     return lut.float().contiguous()
 
 
-def lut_apply(image, lut, interpolation='tetrahedral', quantize=False, blocks=0):
+def _lut_apply_launch(src, npix, ps, cs, table, n, tri, blocks):
+    out = torch.empty((npix, 3), dtype=torch.float32, device=src.device)
+    check(lib.hg_lut_apply(src.data_ptr(), 0, npix, ps, cs, table.data_ptr(), n, tri, out.data_ptr(), 0, blocks,
+                           raw_stream(src.device)), 'hg_lut_apply')
+    return out
+
+
+def lut_apply_backward(image, lut, grad, interpolation='tetrahedral', want_image=True, want_lut=True, blocks=0, workspace_out=None):
+    """hg_lut_apply_bwd as it stands in the C ABI: (gx (H, W, 3) or None, glut (N, N, N, 3) or None) for the fp32 device view
+    `image`, the LUT and the upstream gradient `grad` (H, W, 3).  What lut_apply(differentiable=True) runs in its backward;
+    workspace_out: a list that receives the workspace (the bits of gmax and the integer sums, include/hg_lut.h) for inspection."""
+    fn = 'lut_apply_backward'
+    tri = _lut_interpolation(interpolation, fn)
+    n = _lut_shape(lut, fn)
+    _lut_image_shape(image, fn, 'image')
+    if not torch.is_tensor(grad) or tuple(grad.shape) != tuple(image.shape):
+        raise ValueError(f'{fn}: grad must have the image\'s shape {tuple(image.shape)}, got '
+                         f'{tuple(grad.shape) if torch.is_tensor(grad) else type(grad).__name__}')
+    if not (want_image or want_lut):
+        raise ValueError(f'{fn}: nothing to compute (want_image and want_lut are both False)')
+    for t in (image, lut, grad):
+        need_gpu(t, fn, _FOUND)
+    dev = image.device
+    with on_device(dev):
+        src, npix, ps, cs = _pixels(image.detach(), 'image', fn)
+        if npix > LUT_GRAD_MAX_PIXELS:
+            raise ValueError(f'{fn}: at most 2^26 pixels per call (the bound of the integer sums), got {npix}')
+        table, g = lut.detach().float().contiguous(), grad.detach().float().contiguous()
+        gx = torch.empty(image.shape, dtype=torch.float32, device=dev) if want_image else None
+        glut = torch.empty((n, n, n, 3), dtype=torch.float32, device=dev) if want_lut else None
+        nb = lib.hg_lut_grad_workspace_bytes(n) if want_lut else 0
+        ws = workspace(nb, dev) if want_lut else None
+        check(lib.hg_lut_apply_bwd(src.data_ptr(), 0, npix, ps, cs, table.data_ptr(), n, tri, g.data_ptr(), ptr(gx), ptr(glut),
+                                   ptr(ws), nb, blocks, raw_stream(dev)), 'hg_lut_apply_bwd')
+    if workspace_out is not None:
+        workspace_out.append(ws)
+    return gx, glut
+
+
+class LutApplyFunction(torch.autograd.Function):
+    """lut_apply(differentiable=True): the forward is hg_lut_apply on the fp32 source (the bits of the default path), the
+    backward hg_lut_apply_bwd for whichever of image / lut needs a gradient.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, image, lut, interpolation, blocks):
+        n, dev = lut.shape[0], image.device
+        with on_device(dev):
+            src, npix, ps, cs = _pixels(image.detach(), 'image', 'lut_apply')
+            table = lut.detach().float().contiguous()
+            out = _lut_apply_launch(src, npix, ps, cs, table, n, _LUT_INTERPOLATION[interpolation], blocks)
+        ctx.save_for_backward(src, table)
+        ctx.interpolation, ctx.blocks, ctx.dtypes = interpolation, blocks, (image.dtype, lut.dtype)
+        return out.view(image.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        src, table = ctx.saved_tensors
+        gx, glut = lut_apply_backward(src, table, grad, ctx.interpolation, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                      ctx.blocks)
+        return (None if gx is None else gx.to(ctx.dtypes[0]), None if glut is None else glut.to(ctx.dtypes[1]), None, None)
+
+
+def lut_apply(image, lut, interpolation='tetrahedral', quantize=False, blocks=0, differentiable=False):
     """A 3D LUT applied to an image (hg_lut_apply): one memory-bound pass, no transcendental per pixel.  image: an (H, W, 3)
     fp32 device view in [0, 1] (a CHW image's .permute(1, 2, 0) is one; any strides) or a uint8 (H, W, 3) photo read as
     v / 255; values outside [0, 1] are clamped first and NaN reads as 0.  lut: fp32 (N, N, N, 3), 2 <= N <= 65 (lut_identity,
     lut_fit, lut_bake, load_cube).  interpolation: 'tetrahedral' (four nodes, the default) or 'trilinear' (eight).  Returns
     (H, W, 3) fp32 clipped to [0, 1], or uint8 = (uint8)(out*255) when quantize -- truncation, the rule of color_transfer_mkl,
-    _idt and _palette, so an identity LUT on a uint8 photo is not an exact round trip.  blocks: 0 takes the kernel's plan."""
+    _idt and _palette, so an identity LUT on a uint8 photo is not an exact round trip.  blocks: 0 takes the kernel's plan.
+    differentiable: False (the default) detaches both operands.  True returns the same bits with a grad_fn: the backward
+    (hg_lut_apply_bwd) gives the gradient for whichever of image / lut requires one -- zero through a clipped output channel
+    and for an input channel outside [0, 1]; the LUT's gradient is summed in integers, so it has the same bits in every run.
+    A uint8 image or quantize=True has no gradient: ValueError.  At most 2^26 pixels; no double backward."""
     fn = 'lut_apply'
     tri = _lut_interpolation(interpolation, fn)
     n = _lut_shape(lut, fn)
     _lut_image_shape(image, fn, 'image', u8_ok=True)
+    if differentiable:
+        if quantize or image.dtype == torch.uint8:
+            raise ValueError(f'{fn}: differentiable=True needs a float image and quantize=False (uint8 has no gradient)')
+        if image.shape[0] * image.shape[1] > LUT_GRAD_MAX_PIXELS:
+            raise ValueError(f'{fn}: differentiable=True takes at most 2^26 pixels, got {image.shape[0] * image.shape[1]}')
     need_gpu(image, fn, _FOUND)
     need_gpu(lut, fn, _FOUND)
+    if differentiable:
+        return LutApplyFunction.apply(image, lut, interpolation, blocks)
     dev = image.device
     H, W = image.shape[:2]
     with on_device(dev):
@@ -1132,6 +1212,135 @@ def lut_fit(source, target, n=33, weight=None, lambda_smooth=None, iterations=No
         check(lib.hg_lut_fit(s.data_ptr(), sps, scs, t.data_ptr(), tps, tcs, ptr(w), npix, n, lam, sweeps, lut.data_ptr(),
                              ws.data_ptr(), nb, raw_stream(dev)), 'hg_lut_fit')
     return lut
+
+
+def lut_smoothness(lut):
+    """R(d) = (N - 1)^2 * mean over the 3 N^2 (N - 1) lattice edges of |d_i - d_j|^2 for d = lut - identity: the discretised mean
+    |grad d|^2 over the unit cube, so a weight on it means the same at every N.  A differentiable scalar from plain torch ops
+    on the LUT's device (CPU tensors too) and in its dtype; hg_lut_adam_step adds the gradient of lambda R itself."""
+    n = _lut_shape(lut, 'lut_smoothness')
+    if not lut.is_floating_point():
+        raise ValueError(f'lut_smoothness: lut must be a float tensor, got {lut.dtype}')
+    d = lut - lut_identity(n, lut.device).to(lut.dtype)
+    total = sum(((d.narrow(ax, 1, n - 1) - d.narrow(ax, 0, n - 1)) ** 2).sum() for ax in (2, 1, 0))
+    return total * ((n - 1) ** 2 / (3 * n * n * (n - 1)))
+
+
+def lut_adam_step(lut, grad, exp_avg, exp_avg_sq, step, lr=None, lambda_smooth=None, betas=LUT_ADAM_BETAS, eps=LUT_ADAM_EPS, out=None):
+    """One Adam step on a LUT (hg_lut_adam_step, one launch): the new LUT from `lut`, its gradient `grad` plus the gradient
+    of lambda_smooth * lut_smoothness, and the moments exp_avg / exp_avg_sq, which are updated in place.  step counts from 1.
+    Out of place (the smoothness term reads neighbours): returns `out` or a new tensor.  None takes LUT_REFINE_LR / _LAMBDA."""
+    fn = 'lut_adam_step'
+    n = _lut_shape(lut, fn)
+    lr = LUT_REFINE_LR if lr is None else lr
+    lam = LUT_REFINE_LAMBDA if lambda_smooth is None else lambda_smooth
+    _lut_refine_numbers(lr, lam, fn)
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f'{fn}: step must be a positive integer, got {step!r}')
+    out = torch.empty((n, n, n, 3), dtype=torch.float32, device=lut.device) if out is None else out
+    for t, name in ((lut, 'lut'), (grad, 'grad'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq'), (out, 'out')):
+        if not torch.is_tensor(t) or tuple(t.shape) != (n, n, n, 3) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f'{fn}: {name} must be a contiguous fp32 ({n}, {n}, {n}, 3) tensor')
+    if out.data_ptr() == lut.data_ptr():
+        raise ValueError(f'{fn}: out must not be the LUT itself (the step is out of place)')
+    for t in (lut, grad, exp_avg, exp_avg_sq, out):
+        need_gpu(t, fn, _FOUND)
+    with on_device(lut.device):
+        check(lib.hg_lut_adam_step(lut.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), out.data_ptr(), n,
+                                   float(lam), float(lr), betas[0], betas[1], eps, step, raw_stream(lut.device)), 'hg_lut_adam_step')
+    return out
+
+
+def _lut_refine_numbers(lr, lam, fn):
+    if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not 0 < float(lr) < float('inf'):
+        raise ValueError(f'{fn}: lr must be a positive finite number or None, got {lr!r}')
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0 <= float(lam) < float('inf'):
+        raise ValueError(f'{fn}: lambda_smooth must be a non-negative finite number or None, got {lam!r}')
+
+
+def lut_working_copy(image, hist_block, weight=None):
+    """The (h, w, 3) fp32 image, and the (h, w) weight map or None, that `hist_block` bins when it is given `image` (H, W, 3):
+    clamped to [0, 1] and, where a side exceeds the block's insz, reduced as the block reduces it ('interpolation': bilinear to
+    insz x insz; 'sampling': h x h strided samples).  The block leaves an image of this size alone."""
+    x = image.detach()
+    x = (x.float() / 255.0 if x.dtype == torch.uint8 else x.float()).clamp(0, 1).permute(2, 0, 1).unsqueeze(0).contiguous()
+    w = None if weight is None else weight.detach().float().clamp(0, 1)[None, None]
+    H, W = x.shape[2:]
+    if H > hist_block.insz or W > hist_block.insz:
+        if hist_block.resizing == 'interpolation':
+            size = (hist_block.insz, hist_block.insz)
+            x = torch.nn.functional.interpolate(x, size=size, mode='bilinear', align_corners=False)
+            w = None if w is None else torch.nn.functional.interpolate(w, size=size, mode='bilinear', align_corners=False)
+        elif hist_block.resizing == 'sampling':
+            r = torch.from_numpy(np.linspace(0, H, hist_block.h, endpoint=False).astype(np.int64)).to(x.device)
+            c = torch.from_numpy(np.linspace(0, W, hist_block.h, endpoint=False).astype(np.int64)).to(x.device)
+            x = x[:, :, r][:, :, :, c]
+            w = None if w is None else w[:, :, r][:, :, :, c]
+        else:
+            raise ValueError(f'lut_refine: the block\'s resizing must be interpolation or sampling, got {hist_block.resizing!r}')
+    return x[0].permute(1, 2, 0).contiguous(), None if w is None else w[0, 0].contiguous()
+
+
+def lut_refine(lut, image, target_hist, hist_block, steps=None, lr=None, lambda_smooth=None, interpolation='tetrahedral',
+               weight=None, return_losses=False):
+    """Refine a LUT against a target colour histogram: `steps` Adam steps from `lut` on
+        hist.hellinger_loss(target_hist, hist_block(LUT(image))) + lambda_smooth * lut_smoothness(LUT)
+    -- the loss HistoGAN is trained on, with the LUT as the only unknown.  Start from lut_identity(n) to learn a LUT for a
+    photo and a target histogram with no network at all; start from lut_fit's result to pull a fitted LUT towards the
+    histogram it was meant to reach.  image: (H, W, 3) float in [0, 1] or uint8, on the GPU; it is reduced ONCE to the working
+    copy the block would make of it (lut_working_copy), so a step costs the same for every photo size -- and what is matched
+    is the histogram of LUT(reduced photo), not of the reduced LUT(photo) (DESIGN.md section 6k has the measured difference).
+    target_hist: what hist_block returns for one image, (1, P, h, h) or (P, h, h).  hist_block: RGBuvHistBlock,
+    rgChromaHistBlock or LabHistBlock(from_rgb=True) on the GPU.  weight: optional (H, W) map for the block's per-pixel weight.
+    Each step is lut_apply, the histogram and the Hellinger loss forward and backward, hg_lut_apply_bwd and hg_lut_adam_step on
+    the caller's stream with no read-back; two runs give the same bits.  None takes LUT_REFINE_STEPS, LUT_REFINE_LR and
+    LUT_REFINE_LAMBDA.  Returns the refined LUT, fp32 (N, N, N, 3); with return_losses also a float (steps + 1,) tensor: the
+    Hellinger term before every step and for the returned LUT (one more forward), read from the device once."""
+    from .hist import hellinger_loss
+    fn = 'lut_refine'
+    _lut_interpolation(interpolation, fn)
+    n = _lut_shape(lut, fn)
+    _lut_image_shape(image, fn, 'image', u8_ok=True)
+    steps = LUT_REFINE_STEPS if steps is None else steps
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+        raise ValueError(f'{fn}: steps must be a non-negative integer or None, got {steps!r}')
+    lr = LUT_REFINE_LR if lr is None else lr
+    lam = LUT_REFINE_LAMBDA if lambda_smooth is None else lambda_smooth
+    _lut_refine_numbers(lr, lam, fn)
+    if not torch.is_tensor(target_hist) or target_hist.dim() not in (3, 4) or (target_hist.dim() == 4 and target_hist.shape[0] != 1):
+        raise ValueError(f'{fn}: target_hist must be the (1, P, h, h) or (P, h, h) histogram of one image, got '
+                         f'{tuple(target_hist.shape) if torch.is_tensor(target_hist) else type(target_hist).__name__}')
+    if not callable(hist_block) or not all(hasattr(hist_block, a) for a in ('insz', 'resizing', 'h')):
+        raise ValueError(f'{fn}: hist_block must be one of the histogram blocks (insz, resizing, h), got {type(hist_block).__name__}')
+    if weight is not None and (not torch.is_tensor(weight) or tuple(weight.shape) != tuple(image.shape[:2])):
+        raise ValueError(f'{fn}: weight must be an (H, W) map of the image\'s size {tuple(image.shape[:2])}, got '
+                         f'{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}')
+    for t in (lut, image, target_hist) + (() if weight is None else (weight,)):
+        need_gpu(t, fn, _FOUND)
+    dev = image.device
+    with on_device(dev), torch.enable_grad():
+        work, w = lut_working_copy(image, hist_block, weight)
+        target = (target_hist if target_hist.dim() == 4 else target_hist.unsqueeze(0)).detach().float().contiguous()
+        kw = {} if w is None else {'weight': w.unsqueeze(0)}
+        cur = lut.detach().float().clone(memory_format=torch.contiguous_format)
+        nxt, m, v = torch.empty_like(cur), torch.zeros_like(cur), torch.zeros_like(cur)
+        losses = torch.zeros(steps + 1, dtype=torch.float32, device=dev)
+
+        def loss_of(table):
+            out = LutApplyFunction.apply(work, table, interpolation, 0)
+            return hellinger_loss(target, hist_block(out.permute(2, 0, 1).unsqueeze(0), **kw), global_batch=False)
+
+        for k in range(steps):
+            leaf = cur.detach().requires_grad_(True)
+            loss = loss_of(leaf)
+            (glut,) = torch.autograd.grad(loss, leaf)
+            losses[k].copy_(loss.detach())
+            lut_adam_step(cur, glut.contiguous(), m, v, k + 1, lr, lam, out=nxt)
+            cur, nxt = nxt, cur
+        if return_losses:
+            with torch.no_grad():
+                losses[steps].copy_(loss_of(cur))
+    return (cur, losses.cpu()) if return_losses else cur
 
 
 def lut_bake(fn, n=33, device=None):

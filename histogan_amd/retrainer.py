@@ -424,7 +424,10 @@ class recoloringTrainer():
         post.color_transfer_palette moves every pixel of the photo by a smooth blend of the per-cluster shifts), and
         `post_recoloring='lut'` with a 3D colour LUT (post.lut_fit of the 256x256 input and the network output at n = 33,
         post.lut_apply on the photo: the general smooth pointwise colour map, and the cheapest of the four to apply; a caller
-        who wants the .cube file calls post.save_cube on their own post.lut_fit), and `post_recoloring='idt_regrain'` with
+        who wants the .cube file calls post.save_cube on their own post.lut_fit), and `post_recoloring='lut_refine'` with that
+        LUT refined against the call's own target histogram before it is applied (post.lut_refine with the trainer's
+        histogram block and its defaults: a few dozen Adam steps on the Hellinger loss the network was trained on, at the
+        block's working size whatever the photo's), and `post_recoloring='idt_regrain'` with
         the distribution transfer followed by its regrain step (post.regrain(photo, post.color_transfer_idt(photo, output)):
         the colours of 'idt' on the gradient field of the photo, without the grain 'idt' leaves on flat regions); any other
         string raises ValueError, and True keeps meaning the Monge-Kantorovich map.
@@ -433,10 +436,11 @@ class recoloringTrainer():
         `resizing_method='BGU'`, which in the reference runs an external Windows executable, raises
         NotImplementedError."""
         upscale = resizing == 'upscaling'
-        if isinstance(post_recoloring, str) and post_recoloring not in ('idt', 'palette', 'lut', 'idt_regrain'):
+        if isinstance(post_recoloring, str) and post_recoloring not in ('idt', 'palette', 'lut', 'idt_regrain', 'lut_refine'):
             raise ValueError(f"recoloringTrainer.evaluate: post_recoloring={post_recoloring!r} (True: the Monge-Kantorovich "
                              "linear transfer; 'idt': the iterative distribution transfer; 'palette': the palette transfer; "
-                             "'lut': a fitted 3D colour LUT; 'idt_regrain': 'idt' followed by regrain)")
+                             "'lut': a fitted 3D colour LUT; 'idt_regrain': 'idt' followed by regrain; 'lut_refine': 'lut' refined against the "
+                             "target histogram)")
         recolor = post_recoloring if isinstance(post_recoloring, str) else post_recoloring is True
         if upscale and resizing_method not in ('pyramid', 'BGU_native'):
             raise NotImplementedError(f"recoloringTrainer.evaluate: resizing_method={resizing_method!r} for 'upscaling' "
@@ -472,7 +476,7 @@ class recoloringTrainer():
             if upscale or recolor:
                 self._full_resolution(generated_images, output_name, upscale, pyramid_levels, swapping_levels,
                                       level_blending, input_image_name, original_image, recolor,
-                                      resizing_method, image_batch)
+                                      resizing_method, image_batch, hist_batch)
             if save_input is True:
                 save_image_grid(image_batch[:img_bt_sz] if multi else image_batch,
                                 str(self.results_dir / self.name / f'{str(num)}-input.{ext}'),
@@ -480,7 +484,7 @@ class recoloringTrainer():
         return generated_images
 
     def _full_resolution(self, generated_images, output_name, upscale, levels, swapping_levels, blending,
-                         input_image_name, original_image, recolor, method='pyramid', image_batch=None):
+                         input_image_name, original_image, recolor, method='pyramid', image_batch=None, hist_batch=None):
         """The 'upscaling' ('pyramid' or 'BGU_native') and post_recoloring branches of evaluate
         (ReHistoGAN/rehistoGAN.py:1142-1165) on the kernels of include/hg_post.h; each writes one uint8 image through
         post.save_rgb."""
@@ -502,8 +506,10 @@ class recoloringTrainer():
             if recolor == 'palette':
                 pal_src, pal_dst = post.paired_palette(image_batch[0], generated_images[0], k=8)
                 out, _ = post.color_transfer_palette(src, pal_src, pal_dst, quantize=True)
-            elif recolor == 'lut':
+            elif recolor in ('lut', 'lut_refine'):
                 lut = post.lut_fit(image_batch[0].permute(1, 2, 0), generated_images[0].permute(1, 2, 0), n=33)
+                if recolor == 'lut_refine':
+                    lut = post.lut_refine(lut, src, hist_batch, self.histBlock)
                 out = post.lut_apply(src, lut, quantize=True)
             elif recolor == 'idt_regrain':
                 moved, _ = post.color_transfer_idt(src, generated_images[0].permute(1, 2, 0))
